@@ -16,7 +16,13 @@ GPU_MAX_HW_QUEUES) keep the chip full (profiles/r03_inflight_and_schedule.log). 
 the library, what an isolated call wants — is on the line as `latency_schedule_three_in_flight` (the protocol of `value` in earlier rounds)
 and `one_batch_at_a_time` (strictly one solve after the other).  A step of this bench is one call of `bioik_solve_batch_device`.
 
-Extra objects on the JSON line:
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the headline figure and what follows
+from the timed steps themselves (success rate, steps per solve, roofline, configuration); nothing on it takes work of its own.  Every other
+measurement and check below, and the pose check of the successes under the oracle's FK, runs under `--full`.  `--dump-outputs DIR` writes
+what the last timed step computed -- solutions, fitness, success, steps of its batch, the arrays the caller of `bioik_solve_batch_device`
+receives -- as DIR/<name>.npy in float64; the queries are seeded, so the same arguments give the same inputs on every run.
+
+Extra objects on the JSON line (all but `roofline` under --full):
   roofline     the solve's kernels (k_solve_lean dominant) against the roof that binds them, FP64 vector arithmetic: ALGORITHMIC flops per solve
                (130 L_m + 40 R + 25 G_pose per exact-FK evaluation of an individual, times the evaluations counted by
                the device step counters) / mean launch duration measured with HIP events on the launch stream, vs the 78.6 TFLOP/s
@@ -76,6 +82,22 @@ def kernel_sources_hash():
 def flops_per_evaluation(n_moving, n_revolute, n_pose_goals):
     """algorithmic flops of ONE exact-FK fitness evaluation of ONE individual"""
     return 130.0 * n_moving + 40.0 * n_revolute + 25.0 * n_pose_goals
+
+
+def write_outputs(directory, arrays, limit=64_000_000, seed=0xD0):
+    """--dump-outputs: every array (first axis = query) as directory/<name>.npy in float64.  Where they would take more than `limit` bytes in
+    all, each keeps a fixed, seeded sample of its rows (the same rows for arrays of the same length), written beside it as <name>_rows.npy"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    need = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())  # (+ the row indices, should a sample be needed)
+    for name, a in arrays.items():
+        if need > limit:
+            n = a.shape[0]
+            rows = np.sort(np.random.default_rng(seed).choice(n, max(1, n * (limit - (1 << 16)) // need), replace=False))  # (64 KiB for the headers)
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _timed_device_solves(h, p, n, inputs, bufs, streams, reps):
@@ -213,6 +235,8 @@ def bench_c5(args, rank, world, gpu, dev):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, {"%s_%s" % (b, k): a for b, r in zip(("pr2", "snake"), res) for k, a in zip(("solutions", "fitness", "success", "steps"), r)})
     if rank == 0:
         n_success = float(res[0][2].sum() + res[1][2].sum())
         out = {"metric": "IK solves/sec (mixed PR2 pop=128 / 31-DOF snake pop=512 batch, sharded end to end)", "value": n_success * args.steps / elapsed, "unit": "solves/s",
@@ -369,10 +393,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, every other measurement and check of this bench (the legs named in the module docstring, "
+                         "the determinism check across streams, the pose check of the successes under the oracle's FK).  Off: set-up, warm-up, the K "
+                         "timed steps, --dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the warm-up and the K timed steps (no one-at-a-time leg, no secondary measurements): what the rocprofv3 kernel "
-                         "statistics in profiles/ are taken over, so that their average duration is that of the timed launches")
+                    help="with --full: only the warm-up, the K timed steps and their checks (no one-at-a-time leg, no secondary measurements): what the "
+                         "rocprofv3 kernel statistics in profiles/ are taken over, so that their average duration is that of the timed launches")
     ap.add_argument("--cpu-sample", type=int, default=2048)
     ap.add_argument("--config", default="c2", choices=["c2", "c5"],
                     help="c2 (default): BASELINE.json configs[1], the configuration the metric is quoted on.  c5: configs[4], a mixed PR2 / snake "
@@ -460,12 +490,13 @@ def main():
     if args.in_flight <= 0:
         args.in_flight = 3 if args.schedule == "latency" else next((k for k in (10, 8, 6, 5, 4) if args.steps % k == 0), 6)
     nfl = max(1, args.in_flight)
+    extras = args.full and not args.timed_only  # the legs beside the headline figure
     # The one-pose-per-call leg runs FIRST, while this process has no streams of its own yet: a process with two dozen hardware queues (GPU_MAX_HW_QUEUES above)
     # and more streams than that -- this one, once all its legs have run -- has its queues time-sliced by the hardware scheduler, and a lone short launch then
     # waits for its queue's turn now and then: 1 % of the calls took 8 - 10 ms and overran their timeout (profiles/r06_one_pose_queue_oversubscription.log:
     # reproduced with idle torch streams, gone with four hardware queues or fewer streams).  A MoveIt process has the plugin's streams and no others.
     one_pose = None
-    if rank == 0 and world == 1 and not args.timed_only and os.environ.get("BIOIK_BENCH_ONE_POSE", "1") != "0":
+    if rank == 0 and world == 1 and extras and os.environ.get("BIOIK_BENCH_ONE_POSE", "1") != "0":
         try:
             one_pose = one_pose_timeouts(dev, cpu=not args.no_cpu_baseline)
         except Exception as e:  # (a secondary leg must not take the headline with it)
@@ -525,14 +556,17 @@ def main():
 
     open_streams()
     elapsed, kernel_ms = timed(args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # the last timed step's results, read before any later leg reuses the buffers
+        write_outputs(args.dump_outputs, dict(zip(("solutions", "fitness", "success", "steps"), (x.cpu().numpy() for x in bufs[(args.steps - 1) % nfl]))))
     d_sol, d_fit, d_suc, d_steps = bufs[0]
     # what the timed steps produced, per stream: successes and step() calls of the batch that stream solves, times its share of the steps
     share = [len(range(k, args.steps, nfl)) for k in range(nfl)]
     succ_timed = float(sum(int(o[2].sum().item()) * share[k] for k, o in enumerate(bufs)))
     steps_timed = float(sum(float(o[3].double().sum().item()) * share[k] for k, o in enumerate(bufs)))
     # determinism across streams: batch 0 solved once more on another stream gives the same bits
-    identical = True
-    if nfl > 1:
+    identical = True if args.full else None  # (None: not checked)
+    if nfl > 1 and args.full:
         chk = (torch.empty_like(d_sol), torch.empty_like(d_fit), torch.empty_like(d_suc), torch.empty_like(d_steps))
         h.solve_batch_device(p, BATCH, d_seeds.data_ptr(), d_params.data_ptr(), chk[0].data_ptr(), chk[1].data_ptr(), chk[2].data_ptr(), chk[3].data_ptr(),
                              streams[1].cuda_stream)
@@ -542,7 +576,7 @@ def main():
     # chip filling up at the start and, mostly, the stragglers of the last batches finishing on a nearly empty chip at the end (up to 64 sequential steps each).
     # Two run lengths separate the two: what the kernels do on a full chip, and what the protocol's ends cost.
     longer = None
-    if world == 1 and not args.timed_only and args.steps >= nfl and os.environ.get("BIOIK_BENCH_LONGER", "1") != "0":
+    if world == 1 and extras and args.steps >= nfl and os.environ.get("BIOIK_BENCH_LONGER", "1") != "0":
         k3 = 3 * args.steps
         el3, _ = timed(k3, 0)
         sh3 = [len(range(k, k3, nfl)) for k in range(nfl)]
@@ -550,7 +584,7 @@ def main():
         longer = {"steps": k3, "value": suc3 / el3, "ms_per_step": 1e3 * el3 / k3,
                   "steady_ms_per_step": 1e3 * (el3 - elapsed) / (k3 - args.steps), "fixed_ms_per_run": 1e3 * (elapsed - (el3 - elapsed) / (k3 - args.steps) * args.steps)}
     sequential = latency3 = None
-    if nfl > 1 and not args.timed_only:
+    if nfl > 1 and extras:
         # the same steps strictly one after the other, and three in flight, under BIOIK_SCHEDULE_LATENCY: what an isolated call takes, and the
         # protocol of the rounds before the schedule existed
         nfl_saved, nfl = nfl, 1
@@ -582,19 +616,22 @@ def main():
     # (mode 0: the reference's own unfused expressions + libm; the checker, outside every timed region), the device's own FK only where the oracle's
     # library is not on the box
     sol = d_sol.cpu().numpy()
-    ok_idx = np.nonzero(suc)[0][:256]
-    pose_check_by = "oracle FK, reference-pinned arithmetic (mode 0)"
-    try:
-        from oracle import orc as _orc
-        _o = _orc.Oracle(template)
-        if int(_orc.lib().orc_get_trig_mode()) != 0:
-            _orc.set_trig_mode(0)
-        tips = _o.fk(sol[ok_idx]) if len(ok_idx) else np.zeros((0, T, 7))
-    except Exception as e:
-        pose_check_by = "device FK (oracle unavailable: %r)" % e
-        tips = np.stack([h.fk_genes(sol[i], sol[i][h.active_variables][None, :])[0] for i in ok_idx]) if len(ok_idx) else np.zeros((0, T, 7))
-    pos_err = float(np.linalg.norm(tips[:, 0, :3] - params[ok_idx, :3], axis=1).max()) if len(ok_idx) else 0.0
-    rot_err = float((2.0 * np.arccos(np.minimum(1.0, np.abs(np.einsum("ij,ij->i", tips[:, 0, 3:], params[ok_idx, 3:7]))))).max()) if len(ok_idx) else 0.0
+    pose_check = None
+    if args.full:
+        ok_idx = np.nonzero(suc)[0][:256]
+        pose_check_by = "oracle FK, reference-pinned arithmetic (mode 0)"
+        try:
+            from oracle import orc as _orc
+            _o = _orc.Oracle(template)
+            if int(_orc.lib().orc_get_trig_mode()) != 0:
+                _orc.set_trig_mode(0)
+            tips = _o.fk(sol[ok_idx]) if len(ok_idx) else np.zeros((0, T, 7))
+        except Exception as e:
+            pose_check_by = "device FK (oracle unavailable: %r)" % e
+            tips = np.stack([h.fk_genes(sol[i], sol[i][h.active_variables][None, :])[0] for i in ok_idx]) if len(ok_idx) else np.zeros((0, T, 7))
+        pos_err = float(np.linalg.norm(tips[:, 0, :3] - params[ok_idx, :3], axis=1).max()) if len(ok_idx) else 0.0
+        rot_err = float((2.0 * np.arccos(np.minimum(1.0, np.abs(np.einsum("ij,ij->i", tips[:, 0, 3:], params[ok_idx, 3:7]))))).max()) if len(ok_idx) else 0.0
+        pose_check = {"max_pos_err_m_of_successes": pos_err, "max_rot_err_rad_of_successes": rot_err, "pose_check": pose_check_by}
 
     # algorithmic bytes of one launch
     gens_per_step = 2 * (8 if p.mode != abi.MODE_BIO2 else 16)
@@ -644,9 +681,6 @@ def main():
         "success_rate": succ_timed / max(args.steps * BATCH, 1),
         "mean_steps_per_solve": steps_per_launch / BATCH,
         "child_evaluations_per_s": generations * POP * args.steps * world / elapsed if elapsed > 0 else 0.0,  # fitness evaluations of children (rank 0's count x ranks)
-        "max_pos_err_m_of_successes": pos_err,
-        "max_rot_err_rad_of_successes": rot_err,
-        "pose_check": pose_check_by,
         "roofline": {"bound": "fp64_valu", "achieved": alg_flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0, "peak": FP64_PEAK / 1e12, "unit": "TFLOP/s",
                      "frac": alg_flops * args.steps / elapsed / FP64_PEAK if elapsed > 0 else 0.0,  # chip level: the flops of all timed solves over the timed region's wall time
                      "frac_per_solve": alg_flops / (kernel_ms * 1e-3) / FP64_PEAK if kernel_ms > 0 else 0.0, "traffic": traffic, "traffic_provenance": traffic_note,
@@ -667,8 +701,10 @@ def main():
                              "algorithmic_bytes_per_launch": alg_bytes, "chip_level_achieved": alg_bytes * args.steps / elapsed / 1e9 if elapsed > 0 else 0.0,
                              "note": "notional: SURVEY.md section 8(d) B_gen bytes per generation if the population streamed through HBM; the population is "
                                      "LDS-resident and the measured traffic is `roofline.traffic`"}},
-        "results_identical_across_streams": identical,
     }
+    if args.full:
+        out.update(pose_check)
+        out["results_identical_across_streams"] = identical
     if longer is not None:
         longer["frac"] = alg_flops * longer["steps"] / (longer["ms_per_step"] * 1e-3 * longer["steps"]) / FP64_PEAK
         longer["steady_frac"] = alg_flops / (longer["steady_ms_per_step"] * 1e-3) / FP64_PEAK if longer["steady_ms_per_step"] > 0 else None
@@ -688,7 +724,7 @@ def main():
     # Secondary measurement (north-star layout): the population genotype array resident in HBM, genes [unit][D][pop]
     # (individual index fastest), one launch = exact-FK fitness of every individual.  Reported next to the solver line;
     # it is not what `value` measures.
-    if rank == 0 and world == 1 and os.environ.get("BIOIK_BENCH_STREAM", "1") != "0" and not args.timed_only:
+    if rank == 0 and world == 1 and os.environ.get("BIOIK_BENCH_STREAM", "1") != "0" and extras:
         units = int(os.environ.get("BIOIK_BENCH_STREAM_UNITS", "16384"))
         stream = torch.cuda.current_stream(dev)
         g = torch.rand((units, D, POP), dtype=torch.float64, device=dev) * 2.0 - 1.0
@@ -713,7 +749,7 @@ def main():
                                    "bound": "fp64_valu (the walk's arithmetic, not the 8 (D + 1) bytes per individual, limits this kernel: both roofs of SURVEY.md section 8(d) are on the line)",
                                    "layout": "genes [unit][D][pop] f64 in HBM, 512-byte segments per wavefront load"}
 
-    if rank == 0 and world == 1 and not args.timed_only:
+    if rank == 0 and world == 1 and extras:
         # the host-pointer entry point (what the plugin calls): staging into page-locked memory, one DMA each way, the launch
         ts = []
         for _ in range(6):  # (every IO slot of the handle once, untimed: its stream and its arenas are made at first use)
@@ -726,7 +762,7 @@ def main():
                                      "results_identical_to_device_entry": bool(np.array_equal(hs[0], sol) and np.array_equal(hs[2], suc)),
                                      "note": "bioik_solve_batch: host arrays in and out (PCIe-inclusive), one launch at a time; never `value`"}
 
-    if rank == 0 and world == 1 and not args.timed_only:
+    if rank == 0 and world == 1 and extras:
         # a stream of batches through the host-pointer boundary WITHOUT waiting for each: bioik_solve_batch_submit / _wait (what
         # searchPositionIKBatchAsync of the plugin calls), three solves of the handle in flight, PCIe transfers included
         host_in = [(seeds, params)] + [tuple(x.cpu().numpy() for x in inputs[k]) for k in range(1, len(inputs))]
@@ -750,7 +786,7 @@ def main():
                                                  "the solves of one handle in flight on the library's own streams; the rate a C++ caller of "
                                                  "searchPositionIKBatchAsync gets; never `value`"}
 
-    if rank == 0 and world == 1 and not args.timed_only:
+    if rank == 0 and world == 1 and extras:
         # The same queries at the REFERENCE'S OWN parameters (2 species x (2 elites + 16 children), linearised phenotypes, budget
         # 512 steps as in the cpu_baseline leg): the like-for-like figure next to cpu_baseline.value; never `value`.
         pr = abi.default_solve_params(population=16, max_steps=512, random_seed=1, fk_mode=abi.FK_LINEAR)
@@ -771,7 +807,7 @@ def main():
                                        "mean_steps_per_solve": float(bufs[0][3].cpu().numpy().mean()), "population": 16, "fk": "linear", "max_steps": 512,
                                        "batches_in_flight": nfl, "batches_timed": kr}
 
-    if rank == 0 and world == 1 and not args.timed_only:
+    if rank == 0 and world == 1 and extras:
         # The "tracking" workload of SURVEY.md section 8(d) (seed = target + N(0, 0.1 rad), as the reference's ik_test does): same
         # template, same parameters, same issue pattern; reported next to the global-seed figure, never `value`.
         tin = []
@@ -796,11 +832,11 @@ def main():
                                  "mean_steps_per_solve": float(bufs[0][3].cpu().numpy().mean()), "batches_in_flight": nfl,
                                  "sample": "4096 queries per stream, seed = target configuration + N(0, 0.1 rad) clipped to the joint limits"}
 
-    if rank == 0 and world == 1 and not args.timed_only and os.environ.get("BIOIK_BENCH_CONFIGS", "1") != "0":
+    if rank == 0 and world == 1 and extras and os.environ.get("BIOIK_BENCH_CONFIGS", "1") != "0":
         cfg_nfl = min(nfl, 10)  # (ten in flight: their steps take 50 ms each, and six launches per stream are timed)
         out["configs"] = other_configs(dev, cfg_nfl, streams[:cfg_nfl], cpu_baseline=not args.no_cpu_baseline)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.timed_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and extras:
         from oracle import orc, ref
         ns = min(args.cpu_sample, BATCH)
         # (1) the oracle (a port of the reference algorithm, reference Release flags, libm) with the SAME parameters as the
@@ -894,13 +930,13 @@ def main():
         if "reference_parameters" in out and cb.get("kind") == "reference" and cb["value"] > 0:
             out["speedup_at_reference_parameters_vs_cpu_1thread"] = out["reference_parameters"]["value"] / cb["value"]
 
-    if rank == 0 and world == 1 and not args.timed_only and os.environ.get("BIOIK_BENCH_SMALL", "1") != "0":
+    if rank == 0 and world == 1 and extras and os.environ.get("BIOIK_BENCH_SMALL", "1") != "0":
         out["small_batches"] = small_batches(h, template, dev, seeds, params, cpu=not args.no_cpu_baseline)
         out["small_batches_secondary_goals"] = small_batches_secondary(dev, cpu=not args.no_cpu_baseline)
     if one_pose is not None:
         out["one_pose_timeouts"] = one_pose
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # the figures a reader looks for first, in one object at the END of the line (what a truncated tail still shows)
         c = out.get("configs", {})
         sb = {str(e["n"]): e for e in out.get("small_batches", {}).get("sizes", [])}
@@ -923,6 +959,7 @@ def main():
             "one_pose_timeouts": [[[r3(c.get("gpu_success_rate")), r3(c.get("gpu_mean_ms")), r3(c.get("reference_success_rate")), r3(c.get("reference_mean_ms"))] for c in row["cells"]]
                                   for row in out.get("one_pose_timeouts", {}).get("rows", [])],
         }
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

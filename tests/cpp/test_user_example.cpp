@@ -1,13 +1,15 @@
-// Harness for the reference's own usage example (README.md "PR2 turning a valve", the three code blocks after line 199).  The example
-// itself is NOT in this repository: tests/test_readme_example.py cuts it out of /root/reference/README.md when that tree is present and
-// passes it in as EXAMPLE_FILE, unchanged except for the `...` placeholder line, which becomes the hook EXAMPLE_AFTER_IK.  What this file
-// provides is what the example assumes around it: a MoveIt-loaded PR2 with the link names it uses (stand-in RobotModel, PR2-like numbers),
-// a `robot_state`, a `joint_model_group` whose solver instance is the bio_ik plugin created through pluginlib, and the includes a ROS
-// program would have.  Passing means: the goal (cost) plugin interface is source compatible for this user code -- tf vectors into the
-// goal setters, BioIKKinematicsQueryOptions through RobotState::setFromIK -- and the solves go through the device path.
+// Harness for a MoveIt user program written against the goal (cost) plugin interface (tests/cpp/two_hand_lift.inc, passed in as EXAMPLE_FILE
+// by tests/test_user_example.py).  What this file provides is what such a program assumes around it: a MoveIt-loaded PR2 with grippers and
+// a head (stand-in RobotModel, PR2-like numbers), a `robot_state`, a `joint_model_group` whose solver instance is the bio_ik plugin created
+// through pluginlib, the includes a ROS program would have, and two hooks: EXAMPLE_EXPECT_TIP, by which the program reports the pose it asks of
+// a finger tip, and EXAMPLE_AFTER_IK, which it calls after every setFromIK.  Passing means: the goal (cost) plugin interface is source
+// compatible for this user code -- tf vectors and quaternions into the goal setters, BioIKKinematicsQueryOptions through RobotState::setFromIK
+// -- and the solves put every finger tip where its last goal asked.
 #include <cmath>
 #include <cstdio>
+#include <map>
 #include <memory>
+#include <string>
 
 #include <eigen_stl_containers/eigen_stl_containers.h>
 #include <moveit/kinematics_base/kinematics_base.h>
@@ -56,12 +58,20 @@ static moveit::core::RobotModelPtr pr2WithGrippersAndHead() {
     return m;
 }
 
+// what the program calls for every finger tip it sets a pose goal for: the pose it asks for (the last call's are checked at the end)
+struct ExpectedTip {
+    tf::Vector3 position;
+    tf::Quaternion orientation;
+};
+static std::map<std::string, ExpectedTip> expected_tips;
+#define EXAMPLE_EXPECT_TIP(link, position, orientation) expected_tips[link] = ExpectedTip{position, orientation};
+
 static int iterations_done = 0;
 static bool last_ok = false;
 #ifndef EXAMPLE_ITERATIONS
 #define EXAMPLE_ITERATIONS 3
 #endif
-// what stands where the example says "... // check solution validity and actually move the robot"
+// what the program calls after every setFromIK: count the iterations, stop after EXAMPLE_ITERATIONS or at the first failure
 #define EXAMPLE_AFTER_IK(ok)             \
     last_ok = (ok);                      \
     if (++iterations_done >= EXAMPLE_ITERATIONS || !last_ok) break;
@@ -81,7 +91,7 @@ int main() {
     const moveit::core::JointModelGroup* joint_model_group = static_cast<const moveit::core::RobotModel&>(*robot_model).getJointModelGroup("all");
     moveit::core::RobotState robot_state(robot_model);
     robot_state.setToDefaultValues();
-    for (const char* side : {"r", "l"}) {  // arms forward, elbows bent: a posture from which the valve is in reach
+    for (const char* side : {"r", "l"}) {  // arms forward, elbows bent: a posture from which the bar is in reach
         robot_state.setVariablePosition(std::string(side) + "_shoulder_lift_joint", 0.3);
         robot_state.setVariablePosition(std::string(side) + "_elbow_flex_joint", -1.2);
         robot_state.setVariablePosition(std::string(side) + "_wrist_flex_joint", -0.4);
@@ -93,11 +103,26 @@ int main() {
         std::printf("FAILED: %d iterations, last setFromIK %d\n", iterations_done, (int)last_ok);
         return 1;
     }
-    // the hands went where the goals of the last iteration put them (approximate solutions are allowed by the example: loose bound)
-    const Eigen::Isometry3d L = robot_state.getGlobalLinkTransform("l_gripper_l_finger_tip_link"), R = robot_state.getGlobalLinkTransform("r_gripper_r_finger_tip_link");
-    std::printf("after %d iterations: left finger tip (%.3f %.3f %.3f), right finger tip (%.3f %.3f %.3f)\n", iterations_done, L.translation().x(), L.translation().y(),
-                L.translation().z(), R.translation().x(), R.translation().y(), R.translation().z());
-    if (std::fabs(L.translation().x() - 0.7) > 0.15 || std::fabs(R.translation().x() - 0.7) > 0.15 || std::fabs(L.translation().z() - 1.0) > 0.2) return 1;
+    // every finger tip went where the goals of the last iteration put it: within 1 cm and 0.05 rad (the starting posture is 10 cm away)
+    if (expected_tips.empty()) {
+        std::printf("FAILED: the program reported no finger tip goals\n");
+        return 1;
+    }
+    bool reached = true;
+    for (const auto& e : expected_tips) {
+        const Eigen::Isometry3d T = robot_state.getGlobalLinkTransform(e.first);
+        const Eigen::Quaterniond q(T.rotation());
+        const tf::Vector3 p = e.second.position;
+        const tf::Quaternion& o = e.second.orientation;
+        const double dx = T.translation().x() - p.x(), dy = T.translation().y() - p.y(), dz = T.translation().z() - p.z();
+        const double distance = std::sqrt(dx * dx + dy * dy + dz * dz);
+        const double angle = 2.0 * std::acos(std::fmin(1.0, std::fabs(q.x() * o.x() + q.y() * o.y() + q.z() * o.z() + q.w() * o.w()) /
+                                                                std::sqrt(o.x() * o.x() + o.y() * o.y() + o.z() * o.z() + o.w() * o.w())));
+        std::printf("%s: (%.3f %.3f %.3f), goal (%.3f %.3f %.3f): %.4f m, %.4f rad\n", e.first.c_str(), T.translation().x(), T.translation().y(),
+                    T.translation().z(), p.x(), p.y(), p.z(), distance, angle);
+        reached = reached && distance < 0.01 && angle < 0.05;
+    }
+    if (!reached) return 1;
     std::printf("ok\n");
     return 0;
 }

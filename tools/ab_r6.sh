@@ -5,7 +5,7 @@ O=$1; shift; mkdir -p $O
 for spec in "$@"; do
   n=${spec%%=*}; rest=${spec#*=}; lib=${rest%%,*}; envs=""
   if [[ "$rest" == *,* ]]; then envs=$(echo "${rest#*,}" | tr ',' ' '); fi
-  env $envs BIOIK_HIP_LIBRARY=$lib BIOIK_BENCH_SMALL=0 BIOIK_BENCH_STREAM=0 python bench.py --gpus 1 --steps ${BIOIK_AB_STEPS:-20} --warmup 5 --no-cpu-baseline > $O/bench_$n.json 2> $O/bench_$n.err
+  env $envs BIOIK_HIP_LIBRARY=$lib BIOIK_BENCH_SMALL=0 BIOIK_BENCH_STREAM=0 python bench.py --full --gpus 1 --steps ${BIOIK_AB_STEPS:-20} --warmup 5 --no-cpu-baseline > $O/bench_$n.json 2> $O/bench_$n.err
   python - $O/bench_$n.json "$n" <<'PY'
 import json, sys
 try:

@@ -1,4 +1,4 @@
-run() { python bench.py --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1: configs', {k:(round(v['value']),round(v['ms_per_step'],1)) for k,v in d['configs'].items()})"; }
+run() { python bench.py --full --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1: configs', {k:(round(v['value']),round(v['ms_per_step'],1)) for k,v in d['configs'].items()})"; }
 run auto
 BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_COLUMNLESS=2 run t64_cl2
 BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_COLUMNLESS=1 run t64_cl1

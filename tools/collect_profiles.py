@@ -71,7 +71,7 @@ if len(sf) == 2:
     b = json.load(open(os.path.join(p, rnd + "_bench.json")))
     alg = b.get("streamed_fitness", {}).get("algorithmic_bytes_per_launch")
     meas = 2 * sf["FETCH_SIZE"]["mean_per_launch_KiB"] * 1024 + sf["WRITE_SIZE"]["mean_per_launch_KiB"] * 1024
-    json.dump({"kernel": "k_stream_fitness(StreamArgs)", "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python bench.py --no-cpu-baseline --steps 2 --warmup 1",
+    json.dump({"kernel": "k_stream_fitness(StreamArgs)", "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python bench.py --full --no-cpu-baseline --steps 2 --warmup 1",
                "counters": sf, "measured_hbm_bytes_per_launch": meas, "algorithmic_bytes_per_launch": alg, "measured_over_algorithmic": meas / alg if alg else None,
                "note": "genes [unit][D][pop] f64 streamed once (FETCH_SIZE x 2: gfx950 tallies 128-B requests as 64 B), fitness written once; "
                        "a ratio near 1 = every gene byte crosses the HBM interface once, in full 512-byte wavefront segments"},

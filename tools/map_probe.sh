@@ -10,7 +10,7 @@ BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_COLUMNLESS=1 run t64_columnless
 BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_SPECIES_PARALLEL=1 BIOIK_SOLVE_COLUMNLESS=2 run t64_sp_columnless_pairs
 BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_SPECIES_PARALLEL=1 BIOIK_SOLVE_COLUMNLESS=1 run t64_sp_columnless
 BIOIK_SOLVE_THREADS=128 BIOIK_SOLVE_COLUMNLESS=2 run t128_columnless_pairs
-real() { python bench.py --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 bench: %.0f solves/s %.2f ms success %.4f one-at-a-time %.0f' % (d['value'], d['ms_per_step'], d['success_rate'], d['one_batch_at_a_time']['value']))"; }
+real() { python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 bench: %.0f solves/s %.2f ms success %.4f one-at-a-time %.0f' % (d['value'], d['ms_per_step'], d['success_rate'], d['one_batch_at_a_time']['value']))"; }
 real default
 BIOIK_SOLVE_THREADS=64 real t64
 BIOIK_SOLVE_THREADS=64 BIOIK_SOLVE_SPECIES_PARALLEL=1 BIOIK_SOLVE_COLUMNLESS=2 real t64_sp_columnless_pairs
