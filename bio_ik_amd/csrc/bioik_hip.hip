@@ -32,6 +32,12 @@ using bioik::Error;
 
 static thread_local std::string g_err;
 
+// The kernels that may be launched with more than 64 KiB of dynamic LDS: above 64 KiB a launch needs an explicit allowance, which be_allow_lds(bytes)
+// gives every kernel of this list.  Both back ends take the list from here.
+#define BIOIK_WIDE_LDS_KERNELS(X)                                                                                                              \
+    X(k_solve) X(k_solve_lean) X(k_solve_lean_cl) X(k_solve_lean_cl4) X(k_solve_lean_cl64w4) X(k_solve_lean_lin) X(k_solve_lean_clj4) X(k_solve_lean_cl4h) \
+    X(k_eval_fk) X(k_eval_fitness) X(k_eval_approximator) X(k_eval_reproduce) X(k_eval_check) X(k_stream_fitness)
+
 // ------------------------------------------------------------------------------------------------------------
 // back end: memory + launch
 // ------------------------------------------------------------------------------------------------------------
@@ -287,16 +293,11 @@ __global__ void __launch_bounds__(256) k_stream_fitness(StreamArgs a) {
         hipLaunchKernelGGL(KERNEL, dim3((unsigned)(grid)), dim3(block), lds, stream, args);           \
         HIP_CHECK(hipGetLastError());                                                                 \
     } while (0)
-// more than 64 KiB of dynamic LDS per workgroup must be allowed explicitly
+// more than 64 KiB of dynamic LDS per workgroup must be allowed explicitly (every kernel of BIOIK_WIDE_LDS_KERNELS)
 static void be_allow_lds(size_t bytes) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_cl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_cl4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_cl64w4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_lin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_clj4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_solve_lean_cl4h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+#define BIOIK_ALLOW_(k) HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    BIOIK_WIDE_LDS_KERNELS(BIOIK_ALLOW_)
+#undef BIOIK_ALLOW_
 }
 #endif
 
@@ -569,6 +570,15 @@ static size_t lds_bytes(const bioik_problem* p, int nthreads, int lambda, int ch
     const DevProblem& d = p->host.dev;
     return (size_t)make_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, nthreads, lambda, d.n_secondary > 0 ? (exact ? 2 : 1) : 0, child_cols, groups, slot_sets, fit_park ? 1 : 0, lambda > 0 ? 1 : 0, helped ? 1 : 0).total * 8;  // (lambda > 0: a solve's layout; the function-level kernels keep their own)
 }
+// The dynamic LDS of a function-level launch (a kernel of BIOIK_WIDE_LDS_KERNELS): a problem whose need is beyond a CU's LDS is refused before anything is
+// allocated or launched, a need above 64 KiB is allowed for the kernel.  (Every problem bioik_problem_create accepts runs or is refused here: 64 tips x 64 ops
+// need about 290 KiB, tables of 7 T m doubles.)
+static size_t eval_lds(const bioik_problem* p, size_t bytes) {
+    if (bytes > p->model->dev.lds_cu)
+        throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs " + std::to_string(bytes) + " B of LDS per workgroup for this entry point, more than a CU has");
+    if (bytes > 64 * 1024) be_allow_lds(bytes);
+    return bytes;
+}
 
 // the timeout of a solve on the device clock (bioik_problem: clock_*)
 static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t stream, SolveArgs& a) {
@@ -744,6 +754,7 @@ struct SolveLauncher {
         result_arrays(pa, false);
         pa.phase_cycles = nullptr;
         set_deadline(p, sp, stream, pa);
+        if (sw.report) std::fprintf(stderr, "[bioik] launch: k_solve_point, 64 lanes, %zu B of LDS\n", lds_point);
         LAUNCH(k_solve_point, point_body(pa, b_, l_), units, 64, lds_point, stream, pa);
         select_islands(pa);
     }
@@ -1500,14 +1511,15 @@ int bioik_eval_fk(bioik_problem* p, size_t n, const double* seed, const double* 
     if (n == 0) return BIOIK_OK;
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
+    const int nth = 64;
+    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
     DevBuf dseed(V * 8), dgenes(n * D * 8), dout(n * T * 7 * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
     be_h2d(dgenes.p, genes, n * D * 8, 0);
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.genes = dgenes.as<double>(), a.out0 = dout.as<double>();
-    const int nth = 64;
-    LAUNCH(k_eval_fk, eval_fk_body(a, b_, l_), (n + nth - 1) / nth, nth, lds_bytes(p, nth, 0), 0, a);
+    LAUNCH(k_eval_fk, eval_fk_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
     be_d2h(tip_frames, dout.p, n * T * 7 * 8, 0);
     be_sync(0);
     API_END
@@ -1523,6 +1535,8 @@ int bioik_eval_fitness(bioik_problem* p, int fk_mode, size_t n, const double* se
     if (n == 0) return BIOIK_OK;
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
+    const int nth = 64;
+    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
     DevBuf dseed(V * 8), dpar(P * 8), dbase(D * 8), dgenes(n * D * 8), d0(n * 8), d1(n * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1532,8 +1546,7 @@ int bioik_eval_fitness(bioik_problem* p, int fk_mode, size_t n, const double* se
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.params = dpar.as<double>(), a.genes = dgenes.as<double>(), a.base = dbase.as<double>();
     a.out0 = d0.as<double>(), a.out1 = d1.as<double>(), a.fk_mode = fk_mode;
-    const int nth = 64;
-    LAUNCH(k_eval_fitness, eval_fitness_body(a, b_, l_), (n + nth - 1) / nth, nth, lds_bytes(p, nth, 0), 0, a);
+    LAUNCH(k_eval_fitness, eval_fitness_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
     be_d2h(primary, d0.p, n * 8, 0);
     be_d2h(secondary, d1.p, n * 8, 0);
     be_sync(0);
@@ -1545,14 +1558,15 @@ int bioik_eval_approximator(bioik_problem* p, const double* seed, const double* 
     if (!p || !seed || !base_genes || !tip_frames || !deltas) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
+    const int nth = 64;
+    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
     DevBuf dseed(V * 8), dbase(D * 8), d0(T * 7 * 8), d1(T * D * 7 * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
     be_h2d(dbase.p, base_genes, D * 8, 0);
     EvalArgs a = eval_args(p);
     a.n = 1, a.seed = dseed.as<double>(), a.base = dbase.as<double>(), a.out0 = d0.as<double>(), a.out1 = d1.as<double>();
-    const int nth = 64;
-    LAUNCH(k_eval_approximator, eval_approximator_body(a, l_), 1, nth, lds_bytes(p, nth, 0), 0, a);
+    LAUNCH(k_eval_approximator, eval_approximator_body(a, l_), 1, nth, lds, 0, a);
     be_d2h(tip_frames, d0.p, T * 7 * 8, 0);
     be_d2h(deltas, d1.p, T * D * 7 * 8, 0);
     be_sync(0);
@@ -1565,6 +1579,9 @@ int bioik_eval_reproduce(bioik_problem* p, int population, uint32_t rng_key, int
     if (!p || !parents || !children_genes || !children_gradients || population <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bad argument");
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
+    const int nth = 64;
+    const size_t M = p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1;
+    const size_t lds = eval_lds(p, (4 * M + 2 * M * nth) * 8);  // (eval_reproduce_body: the parents, then a genotype and a gradient column per lane)
     const size_t D = p->host.dev.D, n = (size_t)population;
     DevBuf dpar(4 * D * 8), d0(n * D * 8), d1(n * D * 8);
     be_h2d(dpar.p, parents, 4 * D * 8, 0);
@@ -1572,9 +1589,7 @@ int bioik_eval_reproduce(bioik_problem* p, int population, uint32_t rng_key, int
     a.n = n, a.genes = dpar.as<double>(), a.out0 = d0.as<double>(), a.out1 = d1.as<double>();
     a.rng_key = rng_key;
     a.rng_ctr1 = (generation << 4) | ((uint32_t)species << 3) | 0u;
-    const int nth = 64;
-    const size_t M = p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1;
-    LAUNCH(k_eval_reproduce, eval_reproduce_body(a, b_, l_), (n + nth - 1) / nth, nth, (4 * M + 2 * M * nth) * 8, 0, a);
+    LAUNCH(k_eval_reproduce, eval_reproduce_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
     be_d2h(children_genes, d0.p, n * D * 8, 0);
     be_d2h(children_gradients, d1.p, n * D * 8, 0);
     be_sync(0);
@@ -1590,6 +1605,8 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     DevSolveParams sp = bioik::normalize_params(*params, 0);
+    const int nth = 64;
+    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
     DevBuf dseed(V * 8), dpar(P * 8), dgenes(n * D * 8), dok(n * 4);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1598,8 +1615,7 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.params = dpar.as<double>(), a.genes = dgenes.as<double>(), a.outi = dok.as<int32_t>();
     a.dpos = sp.dpos, a.drot = sp.drot, a.dtwist = sp.dtwist;
-    const int nth = 64;
-    LAUNCH(k_eval_check, eval_check_body(a, b_, l_), (n + nth - 1) / nth, nth, lds_bytes(p, nth, 0), 0, a);
+    LAUNCH(k_eval_check, eval_check_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
     be_d2h(ok, dok.p, n * 4, 0);
     be_sync(0);
     API_END
@@ -1635,7 +1651,11 @@ int bioik_stream_fitness_device(bioik_problem* p, size_t n_units, int population
     if (n_units == 0) return BIOIK_OK;
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
-    const int nth = population >= 256 ? 256 : (population + 63) / 64 * 64;
+    int nth = population >= 256 ? 256 : (population + 63) / 64 * 64;
+    // (a lane per individual: the genotype columns and parked frames grow with the lanes -- fewer lanes per workgroup where a CU would not hold them; the
+    // lanes score their individuals independently, so the result does not change)
+    while (nth > 64 && lds_bytes(p, nth, 0) > p->model->dev.lds_cu) nth -= 64;
+    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
     StreamArgs a;
     a.pb = p->pb();
     a.n_units = n_units;
@@ -1644,7 +1664,7 @@ int bioik_stream_fitness_device(bioik_problem* p, size_t n_units, int population
     a.seeds = d_seeds, a.params = d_goal_params, a.genes = d_genes, a.fitness = d_fitness;
     uint64_t grid = (uint64_t)n_units * a.blocks_per_unit;
     if (grid > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many units for one launch");
-    LAUNCH(k_stream_fitness, stream_fitness_body(a, b_, l_), grid, nth, lds_bytes(p, nth, 0), (stream_t)hip_stream, a);
+    LAUNCH(k_stream_fitness, stream_fitness_body(a, b_, l_), grid, nth, lds, (stream_t)hip_stream, a);
     API_END
 }
 

@@ -256,7 +256,11 @@ void bioik_model_destroy(bioik_model* m);
 /* replaces Problem::initialize + IKBase::initialize(problem) -> RobotFK::initialize(tips)
  * (problem.cpp:72-228, ik_base.h:154-161, forward_kinematics.h:253-330, 566-599).
  * Size limits of one problem (BIOIK_ERR_UNSUPPORTED beyond them): 64 moving joints on the union of the goal chains (a short
- * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals. */
+ * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals.
+ * Tips and joints are further bounded TOGETHER by the 160 KiB of LDS of a CU: the function-level entry points hold 7 x tips x joints doubles
+ * of tables plus a genotype column per lane (64 tips on 12 joints: 71 KiB; 24 tips on 63 joints: about 137 KiB; 64 tips on 63 joints: about
+ * 290 KiB), the solvers hold more.  A problem beyond that is accepted here and refused with BIOIK_ERR_UNSUPPORTED by every entry point that
+ * cannot hold it, before any launch; gd / gd_r / gd_c / jac stop at 64 KiB. */
 int bioik_problem_create(bioik_model* model, const bioik_problem_desc* desc, bioik_problem** out);
 void bioik_problem_destroy(bioik_problem* p);
 

@@ -1,6 +1,7 @@
 // hostsim_backend.h — TEST INFRASTRUCTURE (tests/hostsim): substitute for the HIP back end of bio_ik_amd/csrc/bioik_hip.hip.
 // "Device memory" is host memory and a launch runs every workgroup as a gang of fibres (one per lane) of the calling thread that call the kernel body
 // directly.  Injected with -DBIOIK_BACKEND_HEADER; never part of the product library.
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <ucontext.h>
@@ -118,8 +119,33 @@ static void be_launch(uint64_t grid, int block, size_t lds_bytes, stream_t, Body
         sim::blk = nullptr;
     }
 }
-#define LAUNCH(KERNEL, BODYCALL, grid, block, lds, stream, args) be_launch(grid, block, lds, stream, [&](uint64_t b_, double* l_) { BODYCALL; })
-static void be_allow_lds(size_t) {}
+// The device's rules for dynamic LDS, enforced where the device enforces them: a launch that asks for more than 64 KiB fails unless its kernel is one of
+// BIOIK_WIDE_LDS_KERNELS and was allowed at least that much (be_allow_lds), an allowance or a launch beyond a CU's LDS fails.  Both fail as a failed
+// hipFuncSetAttribute / hipGetLastError() does on the device (BIOIK_ERR_HIP), so that the CPU suite sees what the device would.
+static std::atomic<size_t> g_allowed_lds{64 * 1024};
+static bool wide_lds_kernel(const char* name) {
+#define HOSTSIM_NAME_(k) #k,
+    static const char* const names[] = {BIOIK_WIDE_LDS_KERNELS(HOSTSIM_NAME_)};
+#undef HOSTSIM_NAME_
+    for (const char* n : names)
+        if (std::strcmp(n, name) == 0) return true;
+    return false;
+}
+static void be_check_lds(const char* kernel, size_t bytes) {
+    if (bytes > DeviceInfo{}.lds_cu) throw Error(BIOIK_ERR_HIP, std::string("hipGetLastError(): ") + kernel + " launched with " + std::to_string(bytes) + " B of LDS (more than a CU has)");
+    if (bytes <= 64 * 1024) return;
+    if (!wide_lds_kernel(kernel) || g_allowed_lds.load() < bytes)
+        throw Error(BIOIK_ERR_HIP, std::string("hipGetLastError(): ") + kernel + " launched with " + std::to_string(bytes) + " B of LDS, more than 64 KiB and more than it was allowed");
+}
+static void be_allow_lds(size_t bytes) {
+    if (bytes > DeviceInfo{}.lds_cu) throw Error(BIOIK_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): " + std::to_string(bytes) + " B is more than a CU has");
+    g_allowed_lds.store(bytes);
+}
+#define LAUNCH(KERNEL, BODYCALL, grid, block, lds, stream, args)                                        \
+    do {                                                                                                \
+        be_check_lds(#KERNEL, lds);                                                                     \
+        be_launch(grid, block, lds, stream, [&](uint64_t b_, double* l_) { BODYCALL; });               \
+    } while (0)
 // What the tests read of the simulator itself (tests/test_hostsim_parity.py): how often lanes met at DIFFERENT collectives so far -- on the device that
 // is a silent exchange of garbage --, and a launch that does it on purpose (odd lanes synchronise from another line than even ones)
 extern "C" unsigned long long hostsim_divergent_collectives() { return __atomic_load_n(&sim::n_site_mismatches, __ATOMIC_RELAXED); }
