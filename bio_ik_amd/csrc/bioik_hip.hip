@@ -364,7 +364,8 @@ struct bioik_problem {
         bool pinned = false;
         // purpose 0 (the islands' results): the control words of SolveArgs::island_done -- per query a count of the islands that have filed and the first_success word --
         // lie at the buffer's start, `ctl_n` of each, and are back in their resting state (0 / 0xffffffff) whenever no solve is running on them: the kernel that uses
-        // them puts them back.  ctl_base != base (or a call of more than ctl_n queries): they have to be set up (a new buffer, a call of the other kind in between)
+        // them puts them back.  ctl_base != base (or a call of more than ctl_n queries): they have to be set up (a new buffer, a call of the other kind in between).
+        // Eager calls only: a captured call sets its words up inside its graph, on every replay (graphs on one pinned buffer lay it out each their own way)
         void* ctl_base = nullptr;
         size_t ctl_n = 0;
     };
@@ -686,7 +687,7 @@ struct SolveLauncher {
                 // (stream-ordered on THIS stream, kept until it has to grow or the handle goes: no call here waits for the device -- hipMalloc / hipFree do, which
                 // cost the first solves of a pipeline over the handle's six streams a factor of three)
                 be_free_async(sc.base, stream);
-                sc.base = nullptr, sc.capacity = 0;
+                sc = bioik_problem::Scratch{};  // (the control words too: a new buffer holds none, even where the allocator hands the old address out again)
                 sc.base = be_alloc_async(bytes + bytes / 2, stream), sc.capacity = bytes + bytes / 2;
                 return sc.base;
             }
@@ -703,25 +704,34 @@ struct SolveLauncher {
         }
         const size_t per = (size_t)dp.V * 8 + 8 + 4 + 4;
         const size_t ctl_n = fused ? std::max<size_t>(n, 256) : 0;  // (the control words of the fused form: room for calls of up to this many queries)
-        const size_t ctl_bytes = (2 * ctl_n * 4 + 63) / 64 * 64;
-        char* w = (char*)scratch(0, ctl_bytes + units * per + 64 + n * 4, island_ws);
+        const auto ctl_bytes = [](size_t words) { return (2 * words * 4 + 63) / 64 * 64; };
+        // Eager: control words at rest from an earlier fused call with a larger ctl_n stay where they are, and this call's arrays go behind THEM -- the request
+        // counts that offset.  Captured: the graph sets up its own words on every replay (other graphs on the same pinned buffer lay it out their own way).
+        const bool capturing_now = be_stream_capturing(stream);
+        size_t prior = 0;
+        if (fused && !capturing_now) {
+            auto it = p->scratch.find(std::make_pair(stream, 0));
+            if (it != p->scratch.end() && !it->second.pinned && it->second.ctl_base == it->second.base) prior = it->second.ctl_n;
+        }
+        char* w = (char*)scratch(0, ctl_bytes(std::max(prior, ctl_n)) + units * per + 64 + n * 4, island_ws);
         bioik_problem::Scratch* sc = nullptr;
         {
             auto it = p->scratch.find(std::make_pair(stream, 0));
             if (it != p->scratch.end() && it->second.base == (void*)w) sc = &it->second;
         }
         if (fused) {
-            size_t have = sc && sc->ctl_base == (void*)w ? sc->ctl_n : 0;
-            if (have < n) {  // a new buffer, a larger call, or a call of the other kind in between: set the words up (the kernels keep them from then on)
+            size_t have = !capturing_now && sc && sc->ctl_base == (void*)w ? sc->ctl_n : 0;
+            if (have < n) {  // a new buffer, a larger call, a call of the other kind in between, or a capture: set the words up (the kernels keep them from then on)
                 be_fill_ff_async(w, ctl_n * 4, stream);
                 be_zero_async(w + ctl_n * 4, ctl_n * 4, stream);
                 have = ctl_n;
-                if (sc) sc->ctl_base = (void*)w, sc->ctl_n = ctl_n;
+                if (sc) sc->ctl_base = capturing_now ? nullptr : (void*)w, sc->ctl_n = capturing_now ? 0 : ctl_n;  // (a pinned buffer is never an eager call's again)
             }
+            if (sw.report) std::fprintf(stderr, "[bioik] islands: reduced by the last island in the launch (control words of %zu queries)\n", have);
             if (sp.island_sync) args.first_success = (unsigned int*)w;
             args.island_done = (unsigned int*)(w + have * 4);
             args.final_solutions = d_solutions, args.final_fitness = d_fitness, args.final_success = d_success, args.final_steps = d_steps;
-            w += (2 * have * 4 + 63) / 64 * 64;
+            w += ctl_bytes(have);
             fused_select = true;
         } else if (sc) {
             sc->ctl_base = nullptr, sc->ctl_n = 0;  // (this call lays the buffer out its own way)
@@ -742,7 +752,9 @@ struct SolveLauncher {
         s.sync = sp.island_sync, s.pad = 0;
         s.isl_solutions = args.solutions, s.isl_fitness = args.fitness, s.isl_success = args.success, s.isl_steps = args.steps;
         s.solutions = d_solutions, s.fitness = d_fitness, s.success = d_success, s.steps = d_steps;
-        if (sp.islands >= 8 && n <= 4096 && sw.fused_select >= 0) LAUNCH(k_select_wave, select_coop(s, b_, p_tid()), n, 64, 0, stream, s);
+        const bool wave = sp.islands >= 8 && n <= 4096 && sw.fused_select >= 0;
+        if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, islands %d\n", wave ? "k_select_wave" : "k_select", (int)sp.islands);
+        if (wave) LAUNCH(k_select_wave, select_coop(s, b_, p_tid()), n, 64, 0, stream, s);
         else LAUNCH(k_select, select_body(s, b_ * 256 + (uint64_t)p_tid()), (n + 255) / 256, 256, 0, stream, s);
     }
     // gd / gd_r / gd_c / jac: one wavefront per (query, island), its own (small) LDS layout

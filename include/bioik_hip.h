@@ -332,8 +332,13 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
  * hipMemsetAsync: on ROCm 7.2 a graph with a memset node in front of these kernels faults on its second replay (HISTORY.md).
  * Lifetime of the scratch under capture: a buffer a captured call has used is PINNED -- the graph holds its address -- and stays alive until
  * bioik_problem_destroy; the next eager call on that stream moves on to a buffer of its own, whatever its size.  Graphs captured from ONE
- * stream of one handle share that stream's pinned buffer: launch them on one stream (or capture from different streams).  Destroy the
- * graphs before the handle. */
+ * stream of one handle may share that stream's pinned buffer, whatever their kinds (one launch or several, islands reduced in the launch or by
+ * k_select, a hand-over, a timeout, any number of queries and islands): every captured call sets up the words it relies on itself on each replay
+ * (the islands' control words laid out for ITS query count), so one graph's replay leaves nothing another's depends on.  Replays of graphs that
+ * share a buffer must not overlap: launch them on one stream, or wait for one before launching the next (or capture from different streams).
+ * The one eager call before a capture must take the same plan as the captured call -- the same queries, islands, mode, population and steps,
+ * under the same BIOIK_SOLVE_* switches: a call in one launch sizes other scratch than one with hand-overs.  Destroy the graphs before the
+ * handle. */
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds,
                              const double* d_goal_params, double* d_solutions, double* d_fitness,
                              int32_t* d_success, int32_t* d_steps, void* hip_stream);

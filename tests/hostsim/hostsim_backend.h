@@ -4,6 +4,8 @@
 #include <atomic>
 #include <chrono>
 #include <functional>
+#include <map>
+#include <mutex>
 #include <ucontext.h>
 namespace sim {
 thread_local Block* blk = nullptr;
@@ -20,9 +22,151 @@ static double be_time_ms(void*, F&& enqueue) {
     enqueue();
     return 0.0;
 }
-static void be_zero_async(void* p, size_t bytes, void*) { std::memset(p, 0, bytes); }
-static void be_fill_ff_async(void* p, size_t bytes, void*) { std::memset(p, 0xff, bytes); }
 typedef void* stream_t;
+// ---- guarded "device" allocations: every block of be_alloc / be_alloc_async lies between two redzones of a fixed pattern (64 B before it, 16 KiB behind
+// it); be_free / be_free_async and hostsim_guard_violations() check them.  A damaged redzone is a write out of bounds on the device -- counted once per block,
+// the first few reported on stderr with the block's size and the offset of the first damaged byte; nothing aborts.
+namespace sim {
+constexpr size_t kRedBefore = 64, kRedAfter = 16 * 1024;
+constexpr unsigned char kRedByte = 0xa5;
+struct Guarded {
+    size_t bytes;
+    bool reported;
+};
+static std::mutex guard_mtx;
+static std::map<char*, Guarded> guarded;  // user pointer -> block
+static unsigned long long n_guard_violations = 0;
+static void check_block(char* p, Guarded& g, const char* when) {  // (guard_mtx held)
+    if (g.reported) return;
+    long first = 0;
+    bool bad = false;
+    for (size_t i = 0; i < kRedBefore && !bad; i++)
+        if ((unsigned char)p[-(long)kRedBefore + (long)i] != kRedByte) bad = true, first = -(long)kRedBefore + (long)i;
+    for (size_t i = 0; i < kRedAfter && !bad; i++)
+        if ((unsigned char)p[g.bytes + i] != kRedByte) bad = true, first = (long)(g.bytes + i);
+    if (!bad) return;
+    g.reported = true;
+    if (n_guard_violations++ < 8)
+        std::fprintf(stderr, "[hostsim] write out of bounds (%s): block of %zu B, first damaged byte at offset %ld\n", when, g.bytes, first);
+}
+static void* guarded_alloc(size_t bytes) {
+    const size_t total = (kRedBefore + bytes + kRedAfter + 63) / 64 * 64;
+    char* raw = (char*)std::aligned_alloc(64, total);
+    if (!raw) throw Error(BIOIK_ERR_HIP, "hipMalloc: out of host memory (hostsim)");
+    std::memset(raw, kRedByte, kRedBefore);
+    std::memset(raw + kRedBefore + bytes, kRedByte, kRedAfter);
+    char* p = raw + kRedBefore;
+    std::lock_guard<std::mutex> lock(guard_mtx);
+    guarded[p] = Guarded{bytes, false};
+    return p;
+}
+static void guarded_free(void* vp) {
+    if (!vp) return;
+    char* p = (char*)vp;
+    std::lock_guard<std::mutex> lock(guard_mtx);
+    auto it = guarded.find(p);
+    if (it == guarded.end()) {
+        n_guard_violations++;
+        std::fprintf(stderr, "[hostsim] free of a pointer that is no live device block\n");
+        return;
+    }
+    check_block(p, it->second, "at its release");
+    guarded.erase(it);
+    std::free(p - kRedBefore);
+}
+}  // namespace sim
+extern "C" unsigned long long hostsim_guard_violations() {
+    std::lock_guard<std::mutex> lock(sim::guard_mtx);
+    for (auto& kv : sim::guarded) sim::check_block(kv.first, kv.second, "live block");
+    return sim::n_guard_violations;
+}
+// ---- stream capture: tests pass small integers as streams (solve_batch_device); between hostsim_capture_begin(s) and hostsim_capture_end(s) the fills, the
+// copies to the device and the launches enqueued on `s` are recorded in order -- closures that hold their arguments by value -- instead of run, and
+// hostsim_graph_replay runs them again.  What HIP would refuse inside a capture (a stream-ordered allocation or release, a synchronisation, a copy to the
+// host) is counted (hostsim_capture_violations) and done at once.
+namespace sim {
+static std::mutex capture_mtx;
+static std::map<stream_t, std::vector<std::function<void()>>> capturing;
+static std::map<long long, std::vector<std::function<void()>>> graphs;
+static long long next_graph = 1;
+static unsigned long long n_capture_violations = 0;
+static bool is_capturing(stream_t s) {
+    std::lock_guard<std::mutex> lock(capture_mtx);
+    return capturing.count(s) != 0;
+}
+// `op` recorded when `s` is being captured (true), or not (false: the caller runs it)
+static bool record(stream_t s, std::function<void()> op) {
+    std::lock_guard<std::mutex> lock(capture_mtx);
+    auto it = capturing.find(s);
+    if (it == capturing.end()) return false;
+    it->second.push_back(std::move(op));
+    return true;
+}
+static void capture_violation(stream_t s, const char* what) {
+    if (!is_capturing(s)) return;
+    std::lock_guard<std::mutex> lock(capture_mtx);
+    if (n_capture_violations++ < 8) std::fprintf(stderr, "[hostsim] %s on a stream that is being captured (HIP invalidates the capture)\n", what);
+}
+}  // namespace sim
+extern "C" int hostsim_capture_begin(void* stream) {
+    std::lock_guard<std::mutex> lock(sim::capture_mtx);
+    return sim::capturing.emplace(stream, std::vector<std::function<void()>>{}).second ? 0 : -1;
+}
+extern "C" long long hostsim_capture_end(void* stream) {
+    std::lock_guard<std::mutex> lock(sim::capture_mtx);
+    auto it = sim::capturing.find(stream);
+    if (it == sim::capturing.end()) return -1;
+    const long long id = sim::next_graph++;
+    sim::graphs[id] = std::move(it->second);
+    sim::capturing.erase(it);
+    return id;
+}
+extern "C" int hostsim_graph_replay(long long graph) {
+    std::vector<std::function<void()>> ops;
+    {
+        std::lock_guard<std::mutex> lock(sim::capture_mtx);
+        auto it = sim::graphs.find(graph);
+        if (it == sim::graphs.end()) return -1;
+        ops = it->second;
+    }
+    for (auto& op : ops) op();
+    return 0;
+}
+extern "C" int hostsim_graph_destroy(long long graph) {
+    std::lock_guard<std::mutex> lock(sim::capture_mtx);
+    return sim::graphs.erase(graph) ? 0 : -1;
+}
+extern "C" unsigned long long hostsim_capture_violations() {
+    std::lock_guard<std::mutex> lock(sim::capture_mtx);
+    return sim::n_capture_violations;
+}
+static void be_zero_async(void* p, size_t bytes, stream_t s) {
+    if (!sim::record(s, [p, bytes]() { std::memset(p, 0, bytes); })) std::memset(p, 0, bytes);
+}
+static void be_fill_ff_async(void* p, size_t bytes, stream_t s) {
+    if (!sim::record(s, [p, bytes]() { std::memset(p, 0xff, bytes); })) std::memset(p, 0xff, bytes);
+}
+static void* be_alloc(size_t bytes) { return sim::guarded_alloc(bytes); }
+static void be_free(void* p) { sim::guarded_free(p); }
+static void* be_alloc_pinned(size_t bytes) { return std::malloc(bytes ? bytes : 1); }
+static void be_free_pinned(void* p) { std::free(p); }
+static void* be_alloc_async(size_t bytes, stream_t s) {
+    sim::capture_violation(s, "a stream-ordered allocation");
+    return sim::guarded_alloc(bytes);
+}
+static bool be_stream_capturing(stream_t s) { return sim::is_capturing(s); }
+static void be_free_async(void* p, stream_t s) {
+    if (p) sim::capture_violation(s, "a stream-ordered release");
+    sim::guarded_free(p);
+}
+static void be_h2d(void* d, const void* h, size_t bytes, stream_t s) {
+    if (!sim::record(s, [d, h, bytes]() { std::memcpy(d, h, bytes); })) std::memcpy(d, h, bytes);
+}
+static void be_d2h(void* h, const void* d, size_t bytes, stream_t s) {
+    sim::capture_violation(s, "a copy to the host");
+    std::memcpy(h, d, bytes);
+}
+static void be_sync(stream_t s) { sim::capture_violation(s, "a synchronisation"); }
 static int be_device_count() { return 1; }
 struct DeviceInfo {  // (the simulator stands for an MI355X)
     size_t lds_cu = 160 * 1024;
@@ -31,16 +175,6 @@ struct DeviceInfo {  // (the simulator stands for an MI355X)
 static DeviceInfo be_device_info(int) { return DeviceInfo{}; }
 static void be_set_device(int) {}
 static int be_get_device() { return 0; }
-static void* be_alloc(size_t bytes) { return std::malloc(bytes ? bytes : 1); }
-static void be_free(void* p) { std::free(p); }
-static void* be_alloc_pinned(size_t bytes) { return std::malloc(bytes ? bytes : 1); }
-static void be_free_pinned(void* p) { std::free(p); }
-static void* be_alloc_async(size_t bytes, stream_t) { return std::malloc(bytes ? bytes : 1); }
-static bool be_stream_capturing(stream_t) { return false; }
-static void be_free_async(void* p, stream_t) { std::free(p); }
-static void be_h2d(void* d, const void* h, size_t bytes, stream_t) { std::memcpy(d, h, bytes); }
-static void be_d2h(void* h, const void* d, size_t bytes, stream_t) { std::memcpy(h, d, bytes); }
-static void be_sync(stream_t) {}
 static stream_t be_stream_create() { return nullptr; }
 static void be_stream_destroy(stream_t) {}
 // One workgroup at a time; its lanes are fibres of the calling thread, scheduled round-robin: a lane runs until it waits at a rendezvous
@@ -144,7 +278,12 @@ static void be_allow_lds(size_t bytes) {
 #define LAUNCH(KERNEL, BODYCALL, grid, block, lds, stream, args)                                        \
     do {                                                                                                \
         be_check_lds(#KERNEL, lds);                                                                     \
-        be_launch(grid, block, lds, stream, [&](uint64_t b_, double* l_) { BODYCALL; });               \
+        auto body_ = [args](uint64_t b_, double* l_) { BODYCALL; }; /* (by value: nothing else may be named) */ \
+        const uint64_t grid_ = (grid);                                                                  \
+        const int block_ = (block);                                                                     \
+        const size_t lds_ = (lds);                                                                      \
+        if (!sim::record((stream_t)(stream), [=]() { be_launch(grid_, block_, lds_, nullptr, body_); })) \
+            be_launch(grid_, block_, lds_, stream, body_);                                               \
     } while (0)
 // What the tests read of the simulator itself (tests/test_hostsim_parity.py): how often lanes met at DIFFERENT collectives so far -- on the device that
 // is a silent exchange of garbage --, and a launch that does it on purpose (odd lanes synchronise from another line than even ones)
@@ -162,4 +301,18 @@ extern "C" void hostsim_selftest_divergence(int diverge) {
         const int sum = p_read_lane(lane, 63) + p_shfl_xor(lane, 1);  // (collectives from one line each: no report)
         if (lane == 0) l[0] = (double)sum;
     });
+}
+// ... and the two other detectors, on purpose (tests/test_hostsim_sequences.py): one byte written at offset `at` of a fresh block of `bytes` (at >= bytes: past
+// its end), and a 0xff fill of words[0] followed by a launch of two workgroups whose first lanes add one to words[1] each, enqueued on `stream`
+extern "C" void hostsim_selftest_write(unsigned long long bytes, unsigned long long at) {
+    char* p = (char*)be_alloc((size_t)bytes);
+    p[at] = 0x11;
+    be_free(p);
+}
+extern "C" void hostsim_selftest_enqueue(void* stream, unsigned int* words) {
+    struct {
+        unsigned int* w;
+    } a{words};
+    be_fill_ff_async(words, 4, (stream_t)stream);
+    LAUNCH(k_selftest, (void)(p_tid() == 0 && ++a.w[1]), 2, 64, 0, (stream_t)stream, a);
 }
