@@ -287,7 +287,8 @@ int bioik_resolve_islands(const bioik_problem* p, const bioik_solve_params* para
  *   seeds        [n][V]  Problem::initial_guess (kinematics_plugin.cpp:466-485, 507): full variable vectors
  *   goal_params  [n][P]  per-query goal parameters, goals in template order (P = bioik_problem_param_count)
  *   solutions    [n][V]  IKParallel::getSolution(): full variable vector (inactive variables = seed)
- *   fitness      [n]     IKParallel::getSolutionFitness(): primary fitness of the exact-FK pose
+ *   fitness      [n]     IKParallel::getSolutionFitness(): primary fitness of the exact-FK pose, plus its secondary fitness where the query succeeded and the
+ *                        problem has secondary goals (ik_parallel.h:222-246)
  *   success      [n]     IKParallel::getSuccess(): Problem::checkSolutionActiveVariables on the exact-FK pose
  *   steps        [n]     number of step() calls executed by the winning island (new: device counter)
  * Host-pointer variant: copies in, solves, copies out, synchronises.

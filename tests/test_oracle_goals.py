@@ -1,5 +1,5 @@
 """Goal costs of the oracle (reference include/bio_ik/goal_types.h, src/problem.cpp:244-341): closed-form known
-answers and an independent NumPy evaluation of every opcode."""
+answers and an independent long-double evaluation of every opcode (tests/np_goals.py)."""
 import numpy as np
 import pytest
 
@@ -7,7 +7,7 @@ from bio_ik_amd import (AvoidJointLimitsGoal, CenterJointsGoal, ConeGoal, Direct
                         LookAtGoal, MaxDistanceGoal, MinDistanceGoal, MinimalDisplacementGoal, OrientationGoal, PlaneGoal,
                         PoseGoal, PositionGoal, ProblemTemplate, RegularizationGoal, SideGoal, abi)
 from conftest import random_configuration
-from np_fk import quat_to_rot64
+from np_goals import np_goal_cost
 from oracle import orc
 
 TIP = "r_wrist_roll_link"
@@ -48,60 +48,6 @@ def test_pose_goal_known_answers(pr2):
     assert o5.fitness(abi.FK_EXACT, seed, g5.params(), genes)[0][0] == pytest.approx(9 * (d @ d), rel=1e-12)
 
 
-def np_goal_cost(goal, frame, genes, seed, o, model):
-    """independent evaluation with rotation matrices"""
-    p, R = frame[:3], quat_to_rot64(frame[3:])
-    q = frame[3:]
-    P = goal.params()
-    op = goal.opcode
-    lo = np.asarray(model.var_min)[o.active_variables]
-    hi = np.asarray(model.var_max)[o.active_variables]
-    info = o.robot_info()[o.active_variables]
-    bounded = info[:, 1] != np.finfo(float).max
-    w = o.velocity_weights()
-    if op == abi.GOAL_POSITION:
-        return np.sum((p - P[:3]) ** 2)
-    if op == abi.GOAL_ORIENTATION:
-        return min(np.sum((P - q) ** 2), np.sum((P + q) ** 2))
-    if op == abi.GOAL_POSE:
-        return np.sum((p - P[:3]) ** 2) + P[7] ** 2 * min(np.sum((P[3:7] - q) ** 2), np.sum((P[3:7] + q) ** 2))
-    if op == abi.GOAL_LOOK_AT:
-        a = R @ P[:3]
-        d = P[3:6] - p
-        return np.sum((d / np.linalg.norm(d) - a / np.linalg.norm(a)) ** 2)
-    if op == abi.GOAL_MAX_DISTANCE:
-        return max(0.0, np.linalg.norm(p - P[:3]) - P[3]) ** 2
-    if op == abi.GOAL_MIN_DISTANCE:
-        return max(0.0, P[3] - np.linalg.norm(p - P[:3])) ** 2
-    if op == abi.GOAL_LINE:
-        pos, d = P[:3], P[3:6]
-        return np.sum((pos - (p - d * np.dot(d, p - pos))) ** 2)
-    if op == abi.GOAL_PLANE:
-        return np.dot(p - P[:3], P[3:6]) ** 2
-    if op == abi.GOAL_AVOID_JOINT_LIMITS:
-        d = np.maximum(0.0, np.abs(genes - (lo + hi) * 0.5) * 2.0 - info[:, 2] * 0.5) * w
-        return np.sum((d * bounded) ** 2)
-    if op == abi.GOAL_CENTER_JOINTS:
-        d = (genes - (lo + hi) * 0.5) * w
-        return np.sum((d * bounded) ** 2)
-    if op == abi.GOAL_REGULARIZATION:
-        return np.sum((genes - seed[o.active_variables]) ** 2)
-    if op == abi.GOAL_MINIMAL_DISPLACEMENT:
-        return np.sum(((genes - seed[o.active_variables]) * w) ** 2)
-    if op == abi.GOAL_JOINT_VARIABLE:
-        vi = list(o.active_variables).index(model.variable_index(goal.variable_name()))
-        return (P[0] - genes[vi]) ** 2
-    if op == abi.GOAL_SIDE:
-        return max(0.0, np.dot(R @ P[:3], P[3:6])) ** 2
-    if op == abi.GOAL_DIRECTION:
-        return np.sum((R @ P[:3] - P[3:6]) ** 2)
-    if op == abi.GOAL_CONE:
-        v = R @ P[4:7]
-        ang = np.arccos(np.clip(np.dot(v, P[7:10]) / np.sqrt(np.dot(v, v) * np.dot(P[7:10], P[7:10])), -1, 1))
-        return max(0.0, ang - P[10]) ** 2 + P[3] ** 2 * np.sum((P[:3] - p) ** 2)
-    raise AssertionError(op)
-
-
 GOALS = [
     lambda: PositionGoal(TIP, (0.5, -0.2, 0.8)),
     lambda: OrientationGoal(TIP, (0.1, 0.2, 0.3, 0.9)),
@@ -138,7 +84,7 @@ def test_every_goal_opcode_against_numpy(pr2, mk):
             params[-1] = 0.0  # auxiliary pose goal with rotation_scale 0 ...
             params[-8:-5] = frame[:3]  # ... and zero position error: contributes exactly 0
         prim, sec = o.fitness(abi.FK_EXACT, seed, params, genes)
-        expect = 1.5 ** 2 * np_goal_cost(goal, frame, genes, seed, o, pr2)
+        expect = 1.5 ** 2 * float(np_goal_cost(goal, frame, genes, seed, o, pr2))
         got = sec[0] if goal.isSecondary() else prim[0]
         assert got == pytest.approx(expect, rel=1e-11, abs=1e-15)
 

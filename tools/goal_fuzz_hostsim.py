@@ -14,42 +14,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "hostsim"), "-s"], check=True)
 import parity_cases as pc  # noqa: E402
-from bio_ik_amd import (AvoidJointLimitsGoal, CenterJointsGoal, ConeGoal, DirectionGoal, JointVariableGoal, LineGoal, LookAtGoal, MaxDistanceGoal,  # noqa: E402
-                        MinDistanceGoal, MinimalDisplacementGoal, OrientationGoal, PlaneGoal, PoseGoal, PositionGoal, ProblemTemplate, RegularizationGoal, SideGoal,
+from robot_gen import link_goal  # noqa: E402
+from bio_ik_amd import (AvoidJointLimitsGoal, CenterJointsGoal, JointVariableGoal, MinimalDisplacementGoal, ProblemTemplate, RegularizationGoal,  # noqa: E402
                         abi, pr2_like, solver)
 from oracle import orc  # noqa: E402
-
-
-def unit(rng, n):
-    v = rng.normal(size=n)
-    return tuple(v / np.linalg.norm(v))
-
-
-def link_goal(rng, link):
-    w = float(rng.choice([0.2, 0.5, 1.0, 1.7]))
-    p = tuple(rng.normal(size=3) * 0.4)
-    k = int(rng.integers(11))
-    if k == 0:
-        return PositionGoal(link, p, weight=w)
-    if k == 1:
-        return OrientationGoal(link, unit(rng, 4), weight=w)
-    if k == 2:
-        return PoseGoal(link, p, unit(rng, 4), weight=w)
-    if k == 3:
-        return LookAtGoal(link, unit(rng, 3), p, weight=w)
-    if k == 4:
-        return MaxDistanceGoal(link, p, float(rng.uniform(0.1, 0.6)), weight=w)
-    if k == 5:
-        return MinDistanceGoal(link, p, float(rng.uniform(0.1, 0.6)), weight=w)
-    if k == 6:
-        return LineGoal(link, p, unit(rng, 3), weight=w)
-    if k == 7:
-        return PlaneGoal(link, p, unit(rng, 3), weight=w)
-    if k == 8:
-        return SideGoal(link, unit(rng, 3), unit(rng, 3), weight=w)
-    if k == 9:
-        return DirectionGoal(link, unit(rng, 3), unit(rng, 3), weight=w)
-    return ConeGoal(link, unit(rng, 3), unit(rng, 3), float(rng.uniform(0.1, 0.8)), weight=w, position=p if rng.random() < 0.5 else None, position_weight=0.5)
 
 
 def main():
