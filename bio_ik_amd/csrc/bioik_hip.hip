@@ -1246,8 +1246,19 @@ int bioik_problem_create(bioik_model* model, const bioik_problem_desc* desc, bio
     *out = p.release();
     API_END
 }
+static void io_finish(bioik_problem* p, bioik_problem::IoSlot& sl);
 void bioik_problem_destroy(bioik_problem* p) {
     if (!p) return;
+    {  // submitted solves nobody waited for are completed here, as include/bioik_hip.h promises: waited for and their results copied into their callers' arrays,
+       // before anything they use goes
+        std::lock_guard<std::mutex> lock(p->mtx);
+        for (auto& sl : p->io) {
+            try {
+                io_finish(p, sl);
+            } catch (...) {
+            }
+        }
+    }
     be_free(p->d_pb);
     be_free(p->d_clocks);
     be_free(p->d_resident);
@@ -1255,12 +1266,6 @@ void bioik_problem_destroy(bioik_problem* p) {
     for (auto& kv : p->scratch) be_free(kv.second.base);
     for (const auto& r : p->retired_scratch) be_free(r.base);
     for (auto& sl : p->io) {
-        if (sl.pending) {  // (a submitted solve nobody waited for: let it finish before its buffers go)
-            try {
-                be_sync(sl.stream);
-            } catch (...) {
-            }
-        }
         be_stream_destroy(sl.stream);
         be_free(sl.dev);
         be_free_pinned(sl.host);

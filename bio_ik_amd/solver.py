@@ -67,6 +67,7 @@ def _declare(L):
     if hasattr(L, "bioik_eval_arith"):
         L.bioik_eval_arith.argtypes = [C.c_int, C.c_int, C.c_size_t, _pd, _pd]
     L.bioik_stream_fitness_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bioik_resolve_islands.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, _pi, _pi]
     return L
 
 
@@ -213,6 +214,12 @@ class HipSolver:
                 raise ValueError("goal_params must have %d entries" % self.P)
             return g
         return _f64(goal_params).reshape(n, self.P) if self.P else np.zeros((n, 1))
+
+    def resolve_islands(self, params, n):
+        """bioik_resolve_islands: (islands, island_sync) a solve of `n` queries with `params` runs with (BIOIK_ISLANDS_AUTO resolved for this device)"""
+        isl, sync = C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.bioik_resolve_islands(self.problem, C.byref(params), int(n), C.byref(isl), C.byref(sync)))
+        return isl.value, sync.value
 
     def set_first_query(self, first_query):
         self._chk(self.L.bioik_problem_set_first_query(self.problem, int(first_query)))

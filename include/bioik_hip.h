@@ -297,6 +297,17 @@ int bioik_solve_batch(bioik_problem* p, const bioik_solve_params* params, size_t
                       const double* goal_params, double* solutions, double* fitness, int32_t* success,
                       int32_t* steps);
 
+/* CONCURRENCY.  Safe from any thread, at the same time, on ONE handle: bioik_solve_batch, bioik_solve_batch_submit / _wait, bioik_solve_batch_device (on different
+ * streams the solves then overlap on the device), bioik_solve_batch_multi, the function-level entries (bioik_eval_*, bioik_stream_fitness_device) -- each works on
+ * the handle's mutable state under the handle's lock, for the length of the CALL, not of the device work it enqueues (the wait of bioik_solve_batch_wait itself
+ * happens outside the lock: another thread may submit meanwhile) -- and bioik_resolve_islands and the bioik_problem_*_count / _variables / _links getters, which
+ * read what never changes after bioik_problem_create and take no lock.  A synchronous call holds the lock until its results are there: the synchronous calls of
+ * several threads on ONE handle run one after the other (use bioik_solve_batch_submit, or a handle per thread -- handles are independent of each other, also on one
+ * device, and may be created and destroyed while other handles are solving).  bioik_last_error() is per thread.
+ * NOT allowed while any call of that handle is running or any solve of it is in flight (no lock covers them): bioik_problem_set_first_query (bioik_solve_batch and
+ * bioik_solve_batch_multi read the offset before they take the lock), bioik_problem_destroy (wait for device-pointer solves on your own streams first; submitted
+ * tickets are completed by it) and, process-wide, bioik_debug_reload_switches (diagnostics).  (tests/concurrency_cases.py) */
+
 /* The same solve without waiting for it — for a caller with a STREAM of batches, the batched counterpart of calling
  * IKParallel::solve() from several threads (reference src/ik_parallel.h:193-218 keeps its own worker threads busy the same way).
  * `submit` copies the inputs into a page-locked arena of the handle, enqueues transfer in / solve / transfer out on one of the

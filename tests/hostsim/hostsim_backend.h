@@ -3,6 +3,7 @@
 // directly.  Injected with -DBIOIK_BACKEND_HEADER; never part of the product library.
 #include <atomic>
 #include <chrono>
+#include <deque>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -108,7 +109,9 @@ static void capture_violation(stream_t s, const char* what) {
     if (n_capture_violations++ < 8) std::fprintf(stderr, "[hostsim] %s on a stream that is being captured (HIP invalidates the capture)\n", what);
 }
 }  // namespace sim
+static bool hostsim_overlapping();
 extern "C" int hostsim_capture_begin(void* stream) {
+    if (hostsim_overlapping()) return -1;  // (no capture in overlap mode)
     std::lock_guard<std::mutex> lock(sim::capture_mtx);
     return sim::capturing.emplace(stream, std::vector<std::function<void()>>{}).second ? 0 : -1;
 }
@@ -122,6 +125,7 @@ extern "C" long long hostsim_capture_end(void* stream) {
     return id;
 }
 extern "C" int hostsim_graph_replay(long long graph) {
+    if (hostsim_overlapping()) return -1;
     std::vector<std::function<void()>> ops;
     {
         std::lock_guard<std::mutex> lock(sim::capture_mtx);
@@ -140,14 +144,101 @@ extern "C" unsigned long long hostsim_capture_violations() {
     std::lock_guard<std::mutex> lock(sim::capture_mtx);
     return sim::n_capture_violations;
 }
+// ---- overlap mode: between hostsim_overlap_begin(seed) and hostsim_overlap_end() the fills, the copies to the device, the stream-ordered releases and the launches
+// enqueued on ANY stream are queued per stream (held by value, as the capture recorder holds them) instead of run.  be_sync(s) and be_d2h(.., s) run the scheduler
+// until stream s is empty, be_free (hipFree waits for the device) and hostsim_overlap_end() until every stream is: it picks a non-empty stream with a counter
+// generator seeded by `seed` and runs the next WORKGROUP of that stream's head launch, or its head fill / copy / release.  Order within a stream is kept and a launch
+// is complete before its stream's next operation starts; workgroups of launches on different streams interleave.  Capturing and replaying are refused meanwhile.
+namespace sim {
+struct Op {
+    uint64_t grid = 0, next = 0;        // grid 0: a fill, a copy or a release (one step)
+    std::function<void(uint64_t)> run;  // workgroup b of a launch (its LDS buffer lives in the closure)
+};
+static std::mutex overlap_mtx;  // held while an operation is enqueued and for the whole of a scheduler run (kernel bodies never come back to the back end)
+static bool overlap_on = false;
+static uint64_t overlap_seed = 0, overlap_ctr = 0;
+static std::map<stream_t, std::deque<Op>> overlap_q;
+static unsigned long long n_interleaved = 0;  // workgroups run while a launch of ANOTHER stream was part-way through its grid
+static bool defer(stream_t s, Op op) {  // queued (true), or overlap mode is off (false: the caller runs it)
+    std::lock_guard<std::mutex> lock(overlap_mtx);
+    if (!overlap_on) return false;
+    overlap_q[s].push_back(std::move(op));
+    return true;
+}
+static uint64_t overlap_draw() {  // splitmix64 of seed + counter
+    uint64_t z = overlap_seed + 0x9e3779b97f4a7c15ull * ++overlap_ctr;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+static void drain_locked(const stream_t* only) {  // (overlap_mtx held) until stream *only is empty, or every stream
+    std::vector<std::deque<Op>*> ready;
+    for (;;) {
+        ready.clear();
+        int part_way = 0;
+        for (auto& kv : overlap_q)
+            if (!kv.second.empty()) ready.push_back(&kv.second), part_way += kv.second.front().next > 0 ? 1 : 0;
+        if (ready.empty()) return;
+        if (only) {
+            auto it = overlap_q.find(*only);
+            if (it == overlap_q.end() || it->second.empty()) return;
+        }
+        std::deque<Op>& q = *ready[overlap_draw() % ready.size()];
+        Op& op = q.front();
+        if (op.grid > 0 && part_way - (op.next > 0 ? 1 : 0) > 0) n_interleaved++;
+        op.run(op.next);
+        if (++op.next >= op.grid) q.pop_front();
+    }
+}
+static void drain(const stream_t* only) {
+    std::lock_guard<std::mutex> lock(overlap_mtx);
+    if (overlap_on) drain_locked(only);
+}
+}  // namespace sim
+extern "C" int hostsim_overlap_begin(unsigned long long seed) {
+    std::lock_guard<std::mutex> lock(sim::overlap_mtx);
+    {
+        std::lock_guard<std::mutex> cap(sim::capture_mtx);
+        if (!sim::capturing.empty()) return -1;
+    }
+    if (sim::overlap_on) return -1;
+    sim::overlap_on = true, sim::overlap_seed = seed, sim::overlap_ctr = 0;
+    return 0;
+}
+extern "C" int hostsim_overlap_end() {
+    std::lock_guard<std::mutex> lock(sim::overlap_mtx);
+    if (!sim::overlap_on) return -1;
+    sim::drain_locked(nullptr);
+    sim::overlap_on = false;
+    sim::overlap_q.clear();
+    return 0;
+}
+extern "C" unsigned long long hostsim_overlap_interleaved() {
+    std::lock_guard<std::mutex> lock(sim::overlap_mtx);
+    return sim::n_interleaved;
+}
+static bool hostsim_overlapping() {
+    std::lock_guard<std::mutex> lock(sim::overlap_mtx);
+    return sim::overlap_on;
+}
+// a fill, a copy or a release on stream s: recorded (capture), queued (overlap mode) or done at once
+template <class F>
+static void be_stream_op(stream_t s, F f) {
+    if (sim::record(s, f)) return;
+    if (sim::defer(s, sim::Op{0, 0, [f](uint64_t) { f(); }})) return;
+    f();
+}
 static void be_zero_async(void* p, size_t bytes, stream_t s) {
-    if (!sim::record(s, [p, bytes]() { std::memset(p, 0, bytes); })) std::memset(p, 0, bytes);
+    be_stream_op(s, [p, bytes]() { std::memset(p, 0, bytes); });
 }
 static void be_fill_ff_async(void* p, size_t bytes, stream_t s) {
-    if (!sim::record(s, [p, bytes]() { std::memset(p, 0xff, bytes); })) std::memset(p, 0xff, bytes);
+    be_stream_op(s, [p, bytes]() { std::memset(p, 0xff, bytes); });
 }
 static void* be_alloc(size_t bytes) { return sim::guarded_alloc(bytes); }
-static void be_free(void* p) { sim::guarded_free(p); }
+static void be_free(void* p) {
+    if (p) sim::drain(nullptr);  // (hipFree waits for the device)
+    sim::guarded_free(p);
+}
 static void* be_alloc_pinned(size_t bytes) { return std::malloc(bytes ? bytes : 1); }
 static void be_free_pinned(void* p) { std::free(p); }
 static void* be_alloc_async(size_t bytes, stream_t s) {
@@ -156,17 +247,22 @@ static void* be_alloc_async(size_t bytes, stream_t s) {
 }
 static bool be_stream_capturing(stream_t s) { return sim::is_capturing(s); }
 static void be_free_async(void* p, stream_t s) {
-    if (p) sim::capture_violation(s, "a stream-ordered release");
-    sim::guarded_free(p);
+    if (!p) return;
+    sim::capture_violation(s, "a stream-ordered release");
+    if (!sim::defer(s, sim::Op{0, 0, [p](uint64_t) { sim::guarded_free(p); }})) sim::guarded_free(p);  // (behind what the stream still holds)
 }
 static void be_h2d(void* d, const void* h, size_t bytes, stream_t s) {
-    if (!sim::record(s, [d, h, bytes]() { std::memcpy(d, h, bytes); })) std::memcpy(d, h, bytes);
+    be_stream_op(s, [d, h, bytes]() { std::memcpy(d, h, bytes); });
 }
 static void be_d2h(void* h, const void* d, size_t bytes, stream_t s) {
     sim::capture_violation(s, "a copy to the host");
+    sim::drain(&s);
     std::memcpy(h, d, bytes);
 }
-static void be_sync(stream_t s) { sim::capture_violation(s, "a synchronisation"); }
+static void be_sync(stream_t s) {
+    sim::capture_violation(s, "a synchronisation");
+    sim::drain(&s);
+}
 static int be_device_count() { return 1; }
 struct DeviceInfo {  // (the simulator stands for an MI355X)
     size_t lds_cu = 160 * 1024;
@@ -175,7 +271,11 @@ struct DeviceInfo {  // (the simulator stands for an MI355X)
 static DeviceInfo be_device_info(int) { return DeviceInfo{}; }
 static void be_set_device(int) {}
 static int be_get_device() { return 0; }
-static stream_t be_stream_create() { return nullptr; }
+// (distinct tokens, far from the small integers the tests pass as streams: the scratch of the host-pointer slots is keyed per slot, as on the device)
+static stream_t be_stream_create() {
+    static std::atomic<uintptr_t> next{0};
+    return (stream_t)(uintptr_t)(0x10000u + 16u * ++next);
+}
 static void be_stream_destroy(stream_t) {}
 // One workgroup at a time; its lanes are fibres of the calling thread, scheduled round-robin: a lane runs until it waits at a rendezvous
 // (or ends), then the next unfinished lane continues.  sim::tid is the running lane.
@@ -218,40 +318,54 @@ static void lane_main() {
     setcontext(&fib.ctx[tid]);
 }
 }  // namespace sim
+// "run block b" of a launch that has been set up (its lanes, its LDS buffer, its body): the whole workgroup, on the calling thread
 template <class Body>
-static void be_launch(uint64_t grid, int block, size_t lds_bytes, stream_t, Body body) {
-    std::vector<double> lds(lds_bytes / 8 + 2);
+static void be_run_block(uint64_t b, int block, double* lds, const Body& body) {
     sim::Fibres& f = sim::fib;
     while ((int)f.stacks.size() < block) f.stacks.emplace_back(new char[sim::Fibres::kStack]);
-    for (uint64_t b = 0; b < grid; b++) {
-        sim::Block blk;
-        blk.nthreads = block;
-        blk.block_id = (int)b;
-        blk.bar.n = block;
-        blk.bar.rounds.assign((size_t)block, 0ull);
-        {
-            sim::Rendezvous of_a_wave;
-            of_a_wave.n = 64;
-            of_a_wave.rounds.assign((size_t)block, 0ull);
-            blk.wave_bar.assign((size_t)(block / 64), of_a_wave);
-        }
-        blk.xchg.assign((size_t)block, 0);
-        f.n = f.alive = block;
-        f.ctx.assign((size_t)block, ucontext_t());
-        f.done.assign((size_t)block, 0);
-        f.run = [&]() { body(b, lds.data()); };
-        for (int t = 0; t < block; t++) {
-            getcontext(&f.ctx[t]);
-            f.ctx[t].uc_stack.ss_sp = f.stacks[t].get();
-            f.ctx[t].uc_stack.ss_size = sim::Fibres::kStack;
-            f.ctx[t].uc_link = nullptr;
-            makecontext(&f.ctx[t], sim::lane_main, 0);
-        }
-        sim::blk = &blk;
-        sim::tid = 0;
-        swapcontext(&f.main, &f.ctx[0]);  // returns when the last lane has ended
-        sim::blk = nullptr;
+    sim::Block blk;
+    blk.nthreads = block;
+    blk.block_id = (int)b;
+    blk.bar.n = block;
+    blk.bar.rounds.assign((size_t)block, 0ull);
+    {
+        sim::Rendezvous of_a_wave;
+        of_a_wave.n = 64;
+        of_a_wave.rounds.assign((size_t)block, 0ull);
+        blk.wave_bar.assign((size_t)(block / 64), of_a_wave);
     }
+    blk.xchg.assign((size_t)block, 0);
+    f.n = f.alive = block;
+    f.ctx.assign((size_t)block, ucontext_t());
+    f.done.assign((size_t)block, 0);
+    f.run = [&]() { body(b, lds); };
+    for (int t = 0; t < block; t++) {
+        getcontext(&f.ctx[t]);
+        f.ctx[t].uc_stack.ss_sp = f.stacks[t].get();
+        f.ctx[t].uc_stack.ss_size = sim::Fibres::kStack;
+        f.ctx[t].uc_link = nullptr;
+        makecontext(&f.ctx[t], sim::lane_main, 0);
+    }
+    sim::blk = &blk;
+    sim::tid = 0;
+    swapcontext(&f.main, &f.ctx[0]);  // returns when the last lane has ended
+    sim::blk = nullptr;
+}
+// every workgroup of a launch now, one after the other, sharing one LDS buffer
+template <class Body>
+static void be_launch_now(uint64_t grid, int block, size_t lds_bytes, const Body& body) {
+    std::vector<double> lds(lds_bytes / 8 + 2);
+    for (uint64_t b = 0; b < grid; b++) be_run_block(b, block, lds.data(), body);
+}
+// ... or, in overlap mode, queued on its stream with an LDS buffer of its own (`body` holds its arguments by value)
+template <class Body>
+static void be_launch(uint64_t grid, int block, size_t lds_bytes, stream_t s, Body body) {
+    if (grid == 0) return;
+    if (hostsim_overlapping()) {
+        auto lds = std::make_shared<std::vector<double>>(lds_bytes / 8 + 2);
+        if (sim::defer(s, sim::Op{grid, 0, [block, lds, body](uint64_t b) { be_run_block(b, block, lds->data(), body); }})) return;
+    }
+    be_launch_now(grid, block, lds_bytes, body);
 }
 // The device's rules for dynamic LDS, enforced where the device enforces them: a launch that asks for more than 64 KiB fails unless its kernel is one of
 // BIOIK_WIDE_LDS_KERNELS and was allowed at least that much (be_allow_lds), an allowance or a launch beyond a CU's LDS fails.  Both fail as a failed
@@ -282,14 +396,14 @@ static void be_allow_lds(size_t bytes) {
         const uint64_t grid_ = (grid);                                                                  \
         const int block_ = (block);                                                                     \
         const size_t lds_ = (lds);                                                                      \
-        if (!sim::record((stream_t)(stream), [=]() { be_launch(grid_, block_, lds_, nullptr, body_); })) \
-            be_launch(grid_, block_, lds_, stream, body_);                                               \
+        if (!sim::record((stream_t)(stream), [=]() { be_launch_now(grid_, block_, lds_, body_); })) \
+            be_launch(grid_, block_, lds_, (stream_t)(stream), body_);                                   \
     } while (0)
 // What the tests read of the simulator itself (tests/test_hostsim_parity.py): how often lanes met at DIFFERENT collectives so far -- on the device that
 // is a silent exchange of garbage --, and a launch that does it on purpose (odd lanes synchronise from another line than even ones)
 extern "C" unsigned long long hostsim_divergent_collectives() { return __atomic_load_n(&sim::n_site_mismatches, __ATOMIC_RELAXED); }
 extern "C" void hostsim_selftest_divergence(int diverge) {
-    be_launch(1, 64, 64, nullptr, [&](uint64_t, double* l) {
+    be_launch_now(1, 64, 64, [&](uint64_t, double* l) {
         const int lane = p_tid();
         l[0] = 0.0;
         p_wave_sync();
@@ -315,4 +429,12 @@ extern "C" void hostsim_selftest_enqueue(void* stream, unsigned int* words) {
     } a{words};
     be_fill_ff_async(words, 4, (stream_t)stream);
     LAUNCH(k_selftest, (void)(p_tid() == 0 && ++a.w[1]), 2, 64, 0, (stream_t)stream, a);
+}
+// ... and the scheduler of overlap mode: a launch of `blocks` workgroups on `stream` whose first lanes append (id, block) to log[1..] (log[0]: entries so far)
+extern "C" void hostsim_selftest_log(void* stream, int id, int blocks, int* log) {
+    struct {
+        int* log;
+        int id;
+    } a{log, id};
+    LAUNCH(k_selftest_log, (void)(p_tid() == 0 && (a.log[1 + 2 * a.log[0]] = a.id, a.log[2 + 2 * a.log[0]] = (int)b_, ++a.log[0])), (uint64_t)blocks, 64, 0, (stream_t)stream, a);
 }

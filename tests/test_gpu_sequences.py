@@ -1,5 +1,7 @@
 """The call sequences of tests/sequence_cases.py on a real MI355X: HipSolver(device=0), torch tensors, torch.cuda.Stream, and the captures of S4 through
 torch.cuda.graph (single-stream, linear graphs).  Graphs are destroyed before their handle."""
+import contextlib
+
 import pytest
 
 import limit_cases as lc
@@ -52,6 +54,21 @@ class TorchDevice:
     def sync(self):
         self.torch.cuda.synchronize()
 
+    overlap_seeds = (None,)  # tests/concurrency_cases.py: on the device the overlap is real, nothing to seed
+
+    def overlap(self, seed):
+        """nothing synchronises between the enqueues inside"""
+        return contextlib.nullcontext()
+
+    def heavy_rounds(self, cfg):
+        return None  # (every round)
+
+    def interleaved(self):
+        return None
+
+    def sync_stream(self, s):
+        s.synchronize()
+
     def capture(self, s, enqueue):
         g = self.torch.cuda.CUDAGraph()
         with self.torch.cuda.graph(g, stream=s):
@@ -60,6 +77,10 @@ class TorchDevice:
 
     def replay(self, g):
         g.replay()
+
+    def replay_on(self, g, s):
+        with self.torch.cuda.stream(s):
+            g.replay()
 
     def destroy(self, g):
         g.reset()

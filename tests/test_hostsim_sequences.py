@@ -42,6 +42,31 @@ class HostDevice:
         lib.hostsim_capture_end.restype = ctypes.c_longlong
         lib.hostsim_graph_replay.argtypes = [ctypes.c_longlong]
         lib.hostsim_graph_destroy.argtypes = [ctypes.c_longlong]
+        lib.hostsim_overlap_begin.argtypes = [ctypes.c_ulonglong]
+        lib.hostsim_overlap_interleaved.restype = ctypes.c_ulonglong
+
+    overlap_seeds = (11, 12, 13, 14)  # tests/concurrency_cases.py: the scheduler's seeds a case runs under
+
+    @contextlib.contextmanager
+    def overlap(self, seed):
+        """the simulator's overlap mode: what is enqueued inside is queued per stream and run, workgroups of different streams interleaved by the
+        scheduler seeded with `seed`, where the library waits for a stream and -- all that is left -- at the end"""
+        assert self.L.hostsim_overlap_begin(seed) == 0
+        try:
+            yield
+        finally:
+            assert self.L.hostsim_overlap_end() == 0
+
+    def heavy_rounds(self, cfg):
+        """the rounds of a window that S1's pair of calls takes part in: 800 units and more, half a minute per round in the simulator on c2 and more on c4"""
+        return (0, 1) if cfg == "c2" else (0,)
+
+    def interleaved(self):
+        """workgroups run so far while a launch of another stream was part-way through its grid"""
+        return self.L.hostsim_overlap_interleaved()
+
+    def sync_stream(self, s):
+        pass
 
     def buf(self, a):
         return HostBuf(a)
