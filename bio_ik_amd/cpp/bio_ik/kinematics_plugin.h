@@ -32,6 +32,8 @@ struct BioIKParams : bio_ik::core::Settings {  // the kinematics.yaml keys of th
     bool position_only_ik = false;
     double center_joints_weight = 0, avoid_joint_limits_weight = 0, minimal_displacement_weight = 0;
     int gpu_device = 0;
+    int gpu_solutions = 8;               // searchPositionIKRanked / the multi-solution getPositionIK: solutions per pose ...
+    double gpu_solution_distance = 0.1;  // ... and how far apart they are at least (max over the joints, rad / m)
     BioIKParams() { gpu_max_steps = 64; }
 };
 
@@ -42,6 +44,30 @@ class BioIKKinematicsPlugin {
     mutable bio_ik::core::Engine engine;
     mutable std::vector<std::unique_ptr<bio_ik::Goal>> default_goals;
     double base_default[7];
+    int gpu_solutions_ = 8;
+    double gpu_solution_distance_ = 0.1;
+    void buildRequest(bio_ik::core::Request& rq, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states,
+                      const bio_ik::KinematicsQueryOptions& options, const std::vector<double>* context_state, double timeout) const {
+        auto* bio = bio_ik::toBioIKKinematicsQueryOptions(&options);  // recognised by address, as the reference does (:75-101)
+        const bool replace = bio && bio->replace;
+        if (!replace)
+            for (auto& g : default_goals) rq.goals.push_back(g.get());  // :550-552
+        if (bio)
+            for (auto& g : bio->goals) rq.goals.push_back(g.get());
+        if (bio) rq.fixed_joints = bio->fixed_joints;
+        rq.n_pose_goals = replace ? 0 : tip_frames_.size();
+        rq.seed_states = &ik_seed_states;
+        rq.context = context_state ? *context_state : robot_model->defaultPositions();
+        if (context_state) robot_model->linkTransform(robot_model->linkIndex(base_frame), *context_state, rq.base_frame);
+        else
+            for (int c = 0; c < 7; c++) rq.base_frame[c] = base_default[c];
+        for (size_t k = 0; k < ik_seed_states.size() && rq.n_pose_goals; k++)
+            for (size_t t = 0; t < rq.n_pose_goals; t++) {
+                const geometry_msgs::Pose& p = ik_poses.at(k).at(t);
+                rq.tip_poses.insert(rq.tip_poses.end(), {p.position.x, p.position.y, p.position.z, p.orientation.x, p.orientation.y, p.orientation.z, p.orientation.w});
+            }
+        rq.timeout = timeout, rq.return_approximate_solution = options.return_approximate_solution, rq.bio = bio;
+    }
 
 public:
     // a batch that was submitted and not waited for yet (searchPositionIKBatchAsync)
@@ -89,6 +115,7 @@ public:
         bio_ik::core::Settings s = params;
         s.devices = {params.gpu_device};
         engine.initialize(rm.desc(), mv, s);
+        gpu_solutions_ = params.gpu_solutions, gpu_solution_distance_ = params.gpu_solution_distance;
         bio_ik::core::makeDefaultGoals(tip_frames, params.rotation_scale, params.position_only_ik, params.center_joints_weight, params.avoid_joint_limits_weight,
                                        params.minimal_displacement_weight, default_goals);  // :279-329
         rm.linkTransform(rm.linkIndex(base), rm.defaultPositions(), base_default);
@@ -109,26 +136,43 @@ public:
                                        const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions(),
                                        const std::vector<double>* context_state = nullptr, double timeout = 0.0) const {
         bio_ik::core::Request rq;
-        auto* bio = bio_ik::toBioIKKinematicsQueryOptions(&options);  // recognised by address, as the reference does (:75-101)
-        const bool replace = bio && bio->replace;
-        if (!replace)
-            for (auto& g : default_goals) rq.goals.push_back(g.get());  // :550-552
-        if (bio)
-            for (auto& g : bio->goals) rq.goals.push_back(g.get());
-        if (bio) rq.fixed_joints = bio->fixed_joints;
-        rq.n_pose_goals = replace ? 0 : tip_frames_.size();
-        rq.seed_states = &ik_seed_states;
-        rq.context = context_state ? *context_state : robot_model->defaultPositions();
-        if (context_state) robot_model->linkTransform(robot_model->linkIndex(base_frame), *context_state, rq.base_frame);
-        else
-            for (int c = 0; c < 7; c++) rq.base_frame[c] = base_default[c];
-        for (size_t k = 0; k < ik_seed_states.size() && rq.n_pose_goals; k++)
-            for (size_t t = 0; t < rq.n_pose_goals; t++) {
-                const geometry_msgs::Pose& p = ik_poses.at(k).at(t);
-                rq.tip_poses.insert(rq.tip_poses.end(), {p.position.x, p.position.y, p.position.z, p.orientation.x, p.orientation.y, p.orientation.z, p.orientation.w});
-            }
-        rq.timeout = timeout, rq.return_approximate_solution = options.return_approximate_solution, rq.bio = bio;
+        buildRequest(rq, ik_poses, ik_seed_states, options, context_state, timeout);
         return Pending{engine.submit(rq)};
+    }
+    // Up to k distinct solutions per pose, best first (core::Engine::solveRanked): solutions [n][<= k][group variables]; rows that did not pass only with
+    // options.return_approximate_solution; a goal list with callback goals throws.  Returns true iff every query has at least one row.
+    bool searchPositionIKRanked(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states, int k,
+                                double min_distance, std::vector<std::vector<std::vector<double>>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
+                                const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions(), const std::vector<double>* context_state = nullptr,
+                                double timeout = 0.0, std::vector<std::vector<uint8_t>>* passed = nullptr) const {
+        bio_ik::core::Request rq;
+        buildRequest(rq, ik_poses, ik_seed_states, options, context_state, timeout);
+        std::vector<std::vector<uint8_t>> ok;
+        bool all = engine.solveRanked(rq, k, min_distance, solutions, ok);
+        solutions.resize(ik_seed_states.size()), ok.resize(ik_seed_states.size());
+        error_codes.assign(ik_seed_states.size(), moveit_msgs::MoveItErrorCodes());
+        for (size_t q = 0; q < solutions.size(); q++) {
+            error_codes[q].val = solutions[q].empty() ? moveit_msgs::MoveItErrorCodes::NO_IK_SOLUTION : moveit_msgs::MoveItErrorCodes::SUCCESS;
+            all = all && !solutions[q].empty();
+        }
+        if (passed) *passed = ok;
+        return all;
+    }
+    // MoveIt's multi-solution getPositionIK for one pose: k and the distance are the keys gpu_solutions / gpu_solution_distance; solution_percentage =
+    // returned successes / gpu_solutions
+    bool getPositionIK(const std::vector<geometry_msgs::Pose>& ik_poses, const std::vector<double>& ik_seed_state, std::vector<std::vector<double>>& solutions,
+                       double& solution_percentage, const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions()) const {
+        std::vector<std::vector<std::vector<double>>> sols;
+        std::vector<moveit_msgs::MoveItErrorCodes> codes;
+        std::vector<std::vector<uint8_t>> ok;
+        solutions.clear(), solution_percentage = 0.0;
+        searchPositionIKRanked({ik_poses}, {ik_seed_state}, gpu_solutions_, gpu_solution_distance_, sols, codes, options, nullptr, 0.0, &ok);
+        if (sols.empty() || sols[0].empty()) return false;
+        solutions = sols[0];
+        size_t successes = 0;
+        for (uint8_t o : ok[0]) successes += o ? 1 : 0;
+        solution_percentage = (double)successes / (double)std::max(1, gpu_solutions_);
+        return true;
     }
     // Returns true iff every query produced an acceptable solution; per-query verdicts in error_codes.
     bool searchPositionIKBatchWait(Pending& pending, std::vector<std::vector<double>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes) const {

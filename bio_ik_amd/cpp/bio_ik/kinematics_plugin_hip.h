@@ -15,6 +15,13 @@ namespace bio_ik_kinematics_plugin {
 // (kinematics::KinematicsBase of class bio_ik/BioIKKinematicsPlugin); ik_poses[k] holds the tip poses of query k in the base frame
 // (ignored with BioIKKinematicsQueryOptions::replace), ik_seed_states[k] its group variables; `timeout` [s] bounds the whole call.
 // Returns true iff every query has an acceptable solution; the per-query verdicts are in error_codes.
+// Up to k distinct solutions per pose, best first; rows that did not pass only with options.return_approximate_solution.  solutions [n][<= k][group variables].
+// (One pose through MoveIt's own interface: KinematicsBase::getPositionIK(ik_poses, ik_seed_state, solutions, result, options), yaml keys gpu_solutions /
+// gpu_solution_distance.)  Goal lists with callback goals are refused (std::runtime_error).
+bool searchPositionIKRanked(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
+                            const std::vector<std::vector<double>>& ik_seed_states, int k, double min_distance, double timeout,
+                            std::vector<std::vector<std::vector<double>>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
+                            const kinematics::KinematicsQueryOptions& options = kinematics::KinematicsQueryOptions());
 bool searchPositionIKBatch(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                            const std::vector<std::vector<double>>& ik_seed_states, double timeout, std::vector<std::vector<double>>& solutions,
                            std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,

@@ -261,7 +261,10 @@ public:
         next_query_ = 0;
     }
 
-    std::shared_ptr<Ticket> submit(const Request& rq) {
+private:
+    // What a request needs before it is handed to the device: the goal list split and compiled, the seed states laid over the context, the per-query goal
+    // numbers, the solve parameters of the settings (the timeout less what the marshalling took).  `ranked`: a ranked request (solveRanked) -- host-callback goals refused.
+    std::shared_ptr<Ticket> prepare(const Request& rq, bioik_solve_params& sp, bool ranked) {
         const auto t_entry = std::chrono::steady_clock::now();
         if (models_.empty()) throw std::runtime_error("bio_ik (MI355X): plugin not initialised");
         auto tk = std::make_shared<Ticket>();
@@ -275,6 +278,9 @@ public:
         std::vector<const Goal*> device_goals;
         for (const Goal* g : rq.goals) (g->gpuOpcode() >= 0 ? device_goals : tk->host_goals).push_back(g);
         tk->device_goals = device_goals;
+        if (!tk->host_goals.empty() && ranked)
+            throw std::runtime_error("bio_ik (MI355X): a ranked request (several solutions per pose) cannot hold goals without a device implementation (JointFunctionGoal, "
+                                     "LinkFunctionGoal or a user-defined Goal): the hybrid path returns one solution per pose");
         if (!tk->host_goals.empty()) {
             if (device_goals.empty())
                 throw std::runtime_error("bio_ik (MI355X): every goal of this request is a host callback (JointFunctionGoal, LinkFunctionGoal or a user-defined Goal): the "
@@ -322,7 +328,6 @@ public:
             for (size_t j = 0; j < K; j++)
                 for (size_t i = 0; i < P; i++) tk->params[(k * K + j) * P + i] = row.at(i);
         }
-        bioik_solve_params sp;
         bioik_default_solve_params(&sp);
         const SolverMode sm = solverMode(settings_.mode);
         sp.mode = sm.mode;
@@ -341,6 +346,15 @@ public:
             const double used = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count();
             sp.timeout = std::max(rq.timeout - used, 1e-6);
         }
+        return tk;
+    }
+
+public:
+    std::shared_ptr<Ticket> submit(const Request& rq) {
+        bioik_solve_params sp;
+        std::shared_ptr<Ticket> tk = prepare(rq, sp, false);
+        const size_t V = mv_.n_variables, rows = tk->n * tk->replicas;
+        const size_t P = (size_t)bioik_problem_param_count(tk->handles.front());
         // contiguous shards over the devices, each submitted to its own handle (its own streams): no exchange between shards, and the
         // query-indexed random streams make the result independent of the split
         const size_t W = tk->handles.size();
@@ -362,6 +376,58 @@ public:
                 tk->failed = true;  // device errors never abort the caller: every query of the batch reports NO_IK_SOLUTION
         }
         return tk;
+    }
+
+    // A RANKED request: up to k distinct solutions per query, best first (MoveIt's multi-solution getPositionIK).  Seed mapping and goal marshalling as submit();
+    // solved through bioik_solve_batch_ranked with islands = max(k, what the settings resolve to) and island_sync off, on the first device; every returned row gets
+    // the post-processing of wait() (angle wrap towards the seed, bounds); a row that after wrapping coincides with an earlier kept row of its query (max over the
+    // active variables |a - b| <= min_distance) is dropped; rows that did not pass are returned only with return_approximate_solution.
+    // solutions [n][<= k][group variables], passed [n][<= k].  Returns false when the device refused or failed (every query then has no solution).
+    bool solveRanked(const Request& rq, int k, double min_distance, std::vector<std::vector<std::vector<double>>>& solutions, std::vector<std::vector<uint8_t>>& passed) {
+        bioik_solve_params sp;
+        std::shared_ptr<Ticket> tk = prepare(rq, sp, true);
+        tk->waited = true;  // (nothing is submitted through the ticket)
+        const size_t n = tk->n, V = mv_.n_variables;
+        solutions.assign(n, {}), passed.assign(n, {});
+        if (n == 0) return true;
+        bioik_problem* problem = tk->handles.front();
+        const size_t P = (size_t)bioik_problem_param_count(problem);
+        if (sp.islands <= 0) {
+            int32_t isl = 1, sync = 0;
+            if (bioik_resolve_islands(problem, &sp, n, &isl, &sync) != BIOIK_OK) return false;
+            sp.islands = isl;
+        }
+        sp.islands = std::max(sp.islands, k), sp.island_sync = 0;
+        const size_t K = (size_t)std::max(k, 0);
+        std::vector<double> sol(n * K * V), fit(n * K);
+        std::vector<int32_t> suc(n * K), steps(n * K), count(n);
+        const uint64_t first = settings_.gpu_reproducible_calls ? 0 : next_query_;
+        next_query_ += n;
+        bioik_problem_set_first_query(problem, first);
+        if (bioik_solve_batch_ranked(problem, &sp, n, k, min_distance, tk->seeds.data(), P ? tk->params.data() : nullptr, sol.data(), fit.data(), suc.data(), steps.data(),
+                                     count.data()) != BIOIK_OK)
+            return false;
+        for (size_t q = 0; q < n; q++) {
+            std::vector<const double*> kept;
+            for (int32_t r = 0; r < count[q]; r++) {
+                double* st = &sol[(q * K + r) * V];
+                if (!suc[q * K + r] && !tk->approximate) continue;
+                postprocess(st, &tk->seeds[q * V], tk->active);
+                bool coincides = false;
+                for (const double* o : kept) {
+                    double d = 0.0;
+                    for (int ivar : tk->active) d = std::max(d, std::fabs(st[ivar] - o[ivar]));
+                    coincides = coincides || (min_distance >= 0.0 && !(d > min_distance));
+                }
+                if (coincides) continue;
+                kept.push_back(st);
+                solutions[q].emplace_back();
+                for (int gv : mv_.group_vars) solutions[q].back().push_back(st[gv]);
+                passed[q].push_back(suc[q * K + r] ? 1 : 0);
+            }
+            if (tk->bio && q == n - 1 && count[q] > 0) tk->bio->solution_fitness = fit[q * K];
+        }
+        return true;
     }
 
     // Waits for the batch; solutions [n][group variables], ok[k] = accurate solution or an approximate one was asked for (:638-641).

@@ -213,6 +213,8 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
         lookupParam("gpu_fk", p.gpu_fk, std::string("exact"));  // "exact" | "linear" (the reference's linearised phenotypes)
         lookupParam("gpu_schedule", p.gpu_schedule, std::string("auto"));  // "auto" | "latency" | "throughput" (plugin_core.h: Settings)
         lookupParam("gpu_reproducible_calls", p.gpu_reproducible_calls, false);  // true: a repeated call replays the same random streams
+        lookupParam("gpu_solutions", gpu_solutions, 8);  // the multi-solution getPositionIK: solutions per pose ...
+        lookupParam("gpu_solution_distance", gpu_solution_distance, 0.1);  // ... and how far apart they are at least (max over the joints, rad / m)
         int gpu_device = 0;
         lookupParam("gpu_device", gpu_device, 0);
         std::string gpu_devices;  // kinematics.yaml `gpu_devices: "0,1,2,3"` (default: the single `gpu_device`): a batch is sharded over them
@@ -328,14 +330,63 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
 
     // The batched core: n queries of one goal structure, marshalled and enqueued here, finished by finishBatch.  poses[k] (tips of query k;
     // ignored with options.replace), seeds[k] (group variables); `timeout` bounds the whole call (ik_parallel.h:160, honoured on the device).
+    int gpu_solutions = 8;
+    double gpu_solution_distance = 0.1;
     std::shared_ptr<bio_ik::core::Engine::Ticket> submitBatch(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                                                               const std::vector<std::vector<double>>& ik_seed_states, double timeout,
                                                               const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state) const {
         std::lock_guard<std::mutex> lock(mutex);
+        bio_ik::core::Request rq;
+        buildRequest(rq, ik_poses, ik_seed_states, timeout, options, context_state);
+        return engine.submit(rq);
+    }
+    // Up to k distinct solutions per pose, best first (core::Engine::solveRanked): solutions [n][<= k][group variables]; a query without a row: NO_IK_SOLUTION
+    bool solveRanked(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states, int k, double min_distance,
+                     double timeout, std::vector<std::vector<std::vector<double>>>& solutions, std::vector<std::vector<uint8_t>>& passed,
+                     std::vector<moveit_msgs::MoveItErrorCodes>& error_codes, const kinematics::KinematicsQueryOptions& options,
+                     const moveit::core::RobotState* context_state) const {
+        std::lock_guard<std::mutex> lock(mutex);
+        bio_ik::core::Request rq;
+        buildRequest(rq, ik_poses, ik_seed_states, timeout, options, context_state);
+        const bool ran = engine.solveRanked(rq, k, min_distance, solutions, passed);
+        solutions.resize(ik_seed_states.size()), passed.resize(ik_seed_states.size());
+        error_codes.assign(ik_seed_states.size(), moveit_msgs::MoveItErrorCodes());
+        bool all = ran;
+        for (size_t q = 0; q < solutions.size(); q++) {
+            error_codes[q].val = !solutions[q].empty() ? moveit_msgs::MoveItErrorCodes::SUCCESS : moveit_msgs::MoveItErrorCodes::NO_IK_SOLUTION;
+            all = all && !solutions[q].empty();
+        }
+        return all;
+    }
+    // MoveIt's multi-solution overload: k and the distance from the yaml keys gpu_solutions / gpu_solution_distance
+    bool getPositionIK(const std::vector<geometry_msgs::Pose>& ik_poses, const std::vector<double>& ik_seed_state, std::vector<std::vector<double>>& solutions,
+                       kinematics::KinematicsResult& result, const kinematics::KinematicsQueryOptions& options) const override {
+        std::vector<std::vector<std::vector<double>>> sols;
+        std::vector<std::vector<uint8_t>> passed;
+        std::vector<moveit_msgs::MoveItErrorCodes> codes;
+        solutions.clear();
+        result.kinematic_error = kinematics::KinematicError::NO_SOLUTION, result.solution_percentage = 0.0;
+        try {
+            solveRanked({ik_poses}, {ik_seed_state}, gpu_solutions, gpu_solution_distance, 0.0, sols, passed, codes, options, nullptr);
+        } catch (const std::exception&) {
+            return false;
+        }
+        size_t successes = 0;
+        if (!sols.empty()) {
+            solutions = sols[0];
+            for (uint8_t ok : passed[0]) successes += ok ? 1 : 0;
+        }
+        result.solution_percentage = gpu_solutions > 0 ? (double)successes / (double)gpu_solutions : 0.0;
+        if (solutions.empty()) return false;
+        result.kinematic_error = kinematics::KinematicError::OK;
+        return true;
+    }
+    // what submitBatch and solveRanked hand to the engine (mutex held)
+    void buildRequest(bio_ik::core::Request& rq, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states,
+                      double timeout, const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state) const {
         if (!robot_model || !joint_model_group || !engine.ready()) throw std::runtime_error("bio_ik (MI355X): plugin not initialised");
         auto* bio_ik_options = bio_ik::toBioIKKinematicsQueryOptions(&options);
         const size_t V = robot_model->getVariableCount();
-        bio_ik::core::Request rq;
         // variable default positions / context state: what the seed states are laid over (:465-472)
         rq.context.resize(V);
         if (context_state)
@@ -367,7 +418,6 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
                     rq.tip_poses.insert(rq.tip_poses.end(), f.v, f.v + 7);
                 }
         rq.timeout = timeout, rq.return_approximate_solution = options.return_approximate_solution, rq.bio = bio_ik_options;
-        return engine.submit(rq);
     }
     bool finishBatch(bio_ik::core::Engine::Ticket& ticket, std::vector<std::vector<double>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes) const {
         std::vector<uint8_t> ok;
@@ -420,6 +470,15 @@ bool searchPositionIKBatch(const kinematics::KinematicsBase& solver, const std::
     return pluginOf(solver, "searchPositionIKBatch").solveBatch(ik_poses, ik_seed_states, timeout, solutions, error_codes, options, context_state);
 }
 
+
+// several solutions per pose for a batch: solutions [n][<= k][group variables], best first (bio_ik/plugin_core.h: Engine::solveRanked)
+bool searchPositionIKRanked(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
+                            const std::vector<std::vector<double>>& ik_seed_states, int k, double min_distance, double timeout,
+                            std::vector<std::vector<std::vector<double>>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
+                            const kinematics::KinematicsQueryOptions& options) {
+    std::vector<std::vector<uint8_t>> passed;
+    return pluginOf(solver, "searchPositionIKRanked").solveRanked(ik_poses, ik_seed_states, k, min_distance, timeout, solutions, passed, error_codes, options, nullptr);
+}
 
 struct BatchTicket::Impl {
     std::shared_ptr<bio_ik::core::Engine::Ticket> ticket;

@@ -59,6 +59,7 @@ typedef struct bioik_plugin_settings {  // kinematics.yaml keys (kinematics_plug
     const int32_t* devices;
     double dpos, drot, dtwist;  // negative dpos / drot: not set (DBL_MAX)
     double rotation_scale, center_joints_weight, avoid_joint_limits_weight, minimal_displacement_weight;
+    int32_t gpu_island_sync, reserved;  // gpu_island_sync: "any island succeeds => all stop" (core::Settings)
 } bioik_plugin_settings;
 
 typedef struct bioik_plugin_goal {
@@ -87,6 +88,7 @@ static bio_ik::core::Settings coreSettings(const bioik_plugin_settings& s) {
     c.dpos = s.dpos < 0 ? DBL_MAX : s.dpos, c.drot = s.drot < 0 ? DBL_MAX : s.drot, c.dtwist = s.dtwist;
     c.gpu_population = s.gpu_population, c.gpu_islands = s.gpu_islands, c.gpu_max_steps = s.gpu_max_steps;
     c.gpu_reproducible_calls = s.gpu_reproducible_calls != 0;
+    c.gpu_island_sync = s.gpu_island_sync != 0;
     c.devices.assign(s.devices, s.devices + s.n_devices);
     return c;
 }
@@ -155,6 +157,9 @@ void bioik_plugin_group_variables(const bioik_plugin* p, int32_t* out) {
     for (size_t i = 0; i < gv.size(); i++) out[i] = gv[i];
 }
 
+static void buildRequest(bioik_plugin* p, InFlight& f, bio_ik::core::Request& rq, uint64_t n, const double* seeds, const double* tip_poses, const double* base_frame,
+                         const double* context, uint32_t n_goals, const bioik_plugin_goal* goals, int32_t replace, uint32_t n_fixed, const char* const* fixed_joints,
+                         double timeout, int32_t return_approximate_solution);
 // kinematics_plugin.cpp:437-578 for n queries: seeds [n][group variables]; tip_poses [n][tips][7] in the frame `base_frame` [7] is the
 // global transform of (ignored with `replace`); context [n_variables]; goals: the CALLER's goals (the plugin's defaults are prepended
 // here unless `replace`, :550-556).  Nothing is waited for.
@@ -163,9 +168,50 @@ int bioik_plugin_submit(bioik_plugin* p, uint64_t n, const double* seeds, const 
                         int32_t return_approximate_solution, uint64_t* ticket) {
     return guarded([&] {
         std::lock_guard<std::mutex> lock(p->mutex);
-        const bio_ik::core::ModelView& mv = p->engine.modelView();
         InFlight f;
         bio_ik::core::Request rq;
+        buildRequest(p, f, rq, n, seeds, tip_poses, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints, timeout, return_approximate_solution);
+        f.ticket = p->engine.submit(rq);
+        *ticket = p->next_ticket++;
+        p->in_flight.emplace(*ticket, std::move(f));
+    });
+}
+
+// Up to k distinct solutions per query, best first (core::Engine::solveRanked; MoveIt's multi-solution getPositionIK): arrays as for bioik_plugin_submit;
+// solutions [n][k][group variables], passed [n][k], count [n] rows returned per query (the rows behind them are left as they were).  Waits for its solve.
+int bioik_plugin_search_ranked(bioik_plugin* p, uint64_t n, const double* seeds, const double* tip_poses, const double* base_frame, const double* context, uint32_t n_goals,
+                               const bioik_plugin_goal* goals, int32_t replace, uint32_t n_fixed, const char* const* fixed_joints, double timeout,
+                               int32_t return_approximate_solution, int32_t k, double min_distance, double* solutions, uint8_t* passed, int32_t* count) {
+    return guarded([&] {
+        if (!p) throw std::runtime_error("bio_ik (MI355X): null plugin handle");
+        if (n && (!seeds || !base_frame || !context || !solutions || !passed || !count)) throw std::runtime_error("bio_ik (MI355X): bioik_plugin_search_ranked: null array");
+        if (n && !replace && !p->tip_frames.empty() && !tip_poses) throw std::runtime_error("bio_ik (MI355X): bioik_plugin_search_ranked: tip_poses is null");
+        if ((n_goals && !goals) || (n_fixed && !fixed_joints)) throw std::runtime_error("bio_ik (MI355X): bioik_plugin_search_ranked: a count is non-zero but its array is null");
+        if (k < 1) throw std::runtime_error("bio_ik (MI355X): bioik_plugin_search_ranked: k must be at least 1");
+        std::lock_guard<std::mutex> lock(p->mutex);
+        InFlight f;
+        bio_ik::core::Request rq;
+        buildRequest(p, f, rq, n, seeds, tip_poses, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints, timeout, return_approximate_solution);
+        std::vector<std::vector<std::vector<double>>> sols;
+        std::vector<std::vector<uint8_t>> ok;
+        if (!p->engine.solveRanked(rq, k, min_distance, sols, ok)) throw std::runtime_error(std::string("bio_ik (MI355X): ") + bioik_last_error());
+        const size_t G = p->engine.modelView().group_vars.size();
+        for (uint64_t q = 0; q < n; q++) {
+            count[q] = (int32_t)sols[q].size();
+            for (size_t r = 0; r < sols[q].size(); r++) {
+                passed[q * k + r] = ok[q][r];
+                for (size_t i = 0; i < G; i++) solutions[(q * k + r) * G + i] = sols[q][r][i];
+            }
+        }
+    });
+}
+
+// (what bioik_plugin_submit and bioik_plugin_search_ranked hand to the engine: the goal list, the seed states, the poses; `f` keeps what `rq` points to)
+static void buildRequest(bioik_plugin* p, InFlight& f, bio_ik::core::Request& rq, uint64_t n, const double* seeds, const double* tip_poses, const double* base_frame,
+                         const double* context, uint32_t n_goals, const bioik_plugin_goal* goals, int32_t replace, uint32_t n_fixed, const char* const* fixed_joints,
+                         double timeout, int32_t return_approximate_solution) {
+    {
+        const bio_ik::core::ModelView& mv = p->engine.modelView();
         if (!replace)
             for (auto& g : p->default_goals) rq.goals.push_back(g.get());
         rq.n_pose_goals = replace ? 0 : p->tip_frames.size();
@@ -189,10 +235,7 @@ int bioik_plugin_submit(bioik_plugin* p, uint64_t n, const double* seeds, const 
         for (int c = 0; c < 7; c++) rq.base_frame[c] = base_frame[c];
         rq.context.assign(context, context + mv.n_variables);
         rq.timeout = timeout, rq.return_approximate_solution = return_approximate_solution != 0;
-        f.ticket = p->engine.submit(rq);
-        *ticket = p->next_ticket++;
-        p->in_flight.emplace(*ticket, std::move(f));
-    });
+    }
 }
 
 // kinematics_plugin.cpp:580-641: solutions [n][group variables], ok [n] (accurate, or approximate ones were asked for), fitness [n]

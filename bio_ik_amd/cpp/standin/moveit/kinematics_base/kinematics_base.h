@@ -14,6 +14,14 @@ struct KinematicsQueryOptions {  // (a plain struct in MoveIt: no virtual member
     bool lock_redundant_joints = false;
     bool return_approximate_solution = false;
 };
+namespace KinematicError {  // moveit/kinematics_base/kinematics_base.h
+enum KinematicErrors { OK = 1, UNSUPORTED_DISCRETIZATION_REQUESTED, DISCRETIZATION_NOT_INITIALIZED, MULTIPLE_TIPS_NOT_SUPPORTED, EMPTY_TIP_POSES, IK_SEED_OUTSIDE_LIMITS,
+                       SOLVER_NOT_ACTIVE, NO_SOLUTION };
+}
+struct KinematicsResult {
+    KinematicError::KinematicErrors kinematic_error = KinematicError::OK;
+    double solution_percentage = 0.0;  // the share of the requested solutions that was found
+};
 class KinematicsBase {
 public:
     typedef std::function<void(const geometry_msgs::Pose& ik_pose, const std::vector<double>& ik_solution, moveit_msgs::MoveItErrorCodes& error_code)>
@@ -21,6 +29,12 @@ public:
     virtual ~KinematicsBase() {}
     virtual bool getPositionIK(const geometry_msgs::Pose& ik_pose, const std::vector<double>& ik_seed_state, std::vector<double>& solution,
                                moveit_msgs::MoveItErrorCodes& error_code, const KinematicsQueryOptions& options = KinematicsQueryOptions()) const = 0;
+    // the multi-solution overload: MoveIt's default says "not supported"
+    virtual bool getPositionIK(const std::vector<geometry_msgs::Pose>& /*ik_poses*/, const std::vector<double>& /*ik_seed_state*/, std::vector<std::vector<double>>& /*solutions*/,
+                               KinematicsResult& result, const KinematicsQueryOptions& /*options*/) const {
+        result.kinematic_error = KinematicError::NO_SOLUTION, result.solution_percentage = 0.0;
+        return false;
+    }
     virtual bool searchPositionIK(const geometry_msgs::Pose& ik_pose, const std::vector<double>& ik_seed_state, double timeout, std::vector<double>& solution,
                                   moveit_msgs::MoveItErrorCodes& error_code, const KinematicsQueryOptions& options = KinematicsQueryOptions()) const = 0;
     virtual bool searchPositionIK(const geometry_msgs::Pose& ik_pose, const std::vector<double>& ik_seed_state, double timeout,

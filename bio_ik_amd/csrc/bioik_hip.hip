@@ -261,6 +261,11 @@ __global__ void __launch_bounds__(64) k_solve_point(SolveArgs a) {
 }
 __global__ void k_select(SelectArgs a) { select_body(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(64) k_select_wave(SelectArgs a) { select_coop(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }  // a wavefront per query: calls of few queries with many islands
+// the k best distinct islands of every query, ranked (bioik_solve_batch_ranked): a wavefront per query, lane = island
+__global__ void __launch_bounds__(64) k_select_ranked(RankedArgs a) {
+    extern __shared__ double lds[];
+    select_ranked(a, (uint64_t)blockIdx.x, (int)threadIdx.x, lds);
+}
 __global__ void __launch_bounds__(256) k_eval_fk(EvalArgs a) {
     extern __shared__ double lds[];
     eval_fk_body(a, blockIdx.x, lds);
@@ -329,9 +334,10 @@ struct bioik_problem {
         // the solve in flight on this slot, if any: where its results go when it completes
         bool pending = false;
         uint64_t ticket = 0;
-        size_t n = 0, o_sol = 0, o_fit = 0, o_suc = 0, o_steps = 0;
+        size_t n = 0, o_sol = 0, o_fit = 0, o_suc = 0, o_steps = 0, o_cnt = 0;
+        size_t rows = 1;  // result rows per query (a ranked solve: k)
         double *solutions = nullptr, *fitness = nullptr;
-        int32_t *success = nullptr, *steps = nullptr;
+        int32_t *success = nullptr, *steps = nullptr, *count = nullptr;  // (count: ranked solves only)
         // a solve of this slot that ended in a device error: remembered for ITS ticket's wait (the slot itself is free again)
         uint64_t failed_ticket = 0;
         int failed_code = 0;
@@ -638,6 +644,7 @@ struct SolveLauncher {
     uint64_t units = 0;
     void* island_ws = nullptr;  // (a stream-ordered fallback allocation of the per-island results, if any)
     bool fused_select = false;
+    const RankedArgs* ranked = nullptr;  // bioik_solve_batch_ranked: the per-island arrays are ranked by k_select_ranked (k, min_distance and the outputs: here), never reduced to one
     // the mapping (choose_mapping)
     int nth = 0, groups = 1;
     size_t lds = 0;
@@ -746,6 +753,15 @@ struct SolveLauncher {
         }
     }
     void select_islands(const SolveArgs& args) {  // ik_parallel.h:220-269: the best island of every query
+        if (ranked) {  // ... or its k best distinct ones, in that order (islands = 1: the solve wrote the row itself, the kernel adds the count)
+            RankedArgs r = *ranked;
+            r.pb = p->pb(), r.islands = sp.islands, r.V = dp.V, r.D = dp.D, r.n = n, r.seeds = d_seeds;
+            r.isl_solutions = args.solutions, r.isl_fitness = args.fitness, r.isl_success = args.success, r.isl_steps = args.steps;
+            const size_t lds_r = r.min_distance >= 0.0 && sp.islands > 1 ? (size_t)dp.D * 64 * 8 : 0;  // (at most 63 x 64 doubles: 31.5 KiB)
+            if (sw.report) std::fprintf(stderr, "[bioik] launch: k_select_ranked, islands %d, k %d, %zu B of LDS\n", (int)sp.islands, (int)r.k, lds_r);
+            LAUNCH(k_select_ranked, select_ranked(r, b_, p_tid(), l_), n, 64, lds_r, stream, r);
+            return;
+        }
         if (sp.islands == 1 || fused_select) return;
         SelectArgs s;
         s.islands = sp.islands, s.V = dp.V, s.n = n;
@@ -1064,9 +1080,11 @@ struct SolveLauncher {
 };
 
 static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, size_t n, const double* d_seeds, const double* d_params, double* d_solutions,
-                         double* d_fitness, int32_t* d_success, int32_t* d_steps, stream_t stream, const SolveSwitches& sw, unsigned int* error_word) {
+                         double* d_fitness, int32_t* d_success, int32_t* d_steps, stream_t stream, const SolveSwitches& sw, unsigned int* error_word,
+                         const RankedArgs* ranked = nullptr) {
     if (n == 0) return;
     SolveLauncher s(p, sp_in, n, d_seeds, d_params, d_solutions, d_fitness, d_success, d_steps, stream, sw, error_word);
+    s.ranked = ranked;
     if (s.sp.solver != 0) return s.solve_point();
     s.choose_mapping();
     if (sw.report) s.report_mapping();
@@ -1092,7 +1110,7 @@ static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, size_t n
     if (phase_path) s.handovers.clear();
 #endif
     // (a solve in ONE launch reduces its islands itself, SolveArgs::island_done; BIOIK_SOLVE_FUSED_SELECT=0: by k_select as before)
-    s.result_arrays(a, s.handovers.empty() && sw.fused_select > 0);
+    s.result_arrays(a, s.handovers.empty() && sw.fused_select > 0 && !ranked);  // (a ranked call keeps every island's result: never fused)
     s.run(a);
 #if defined(BIOIK_PHASE_TIMING)
     if (phase_path) {  // profiling build only: synchronous dump of the per-phase cycle counters
@@ -1318,6 +1336,35 @@ int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params,
     API_END
 }
 
+// ---- ranked solves: the k best distinct islands of every query (include/bioik_hip.h; select_ranked) ----
+// The solve parameters of a ranked call and its argument checks, all before anything is allocated or launched: an explicit island_sync = 1 is refused (islands that
+// stop each other leave at timing-dependent steps: their individual results are not defined), BIOIK_ISLANDS_AUTO gives max(k, what bioik_resolve_islands gives)
+// with island_sync off, and 1 <= k <= islands <= 64.
+static DevSolveParams ranked_params(bioik_problem* p, const bioik_solve_params& params, uint64_t first_query, size_t n, int32_t k, const int32_t* count) {
+    if (!count) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: count is null");
+    if (k < 1) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: k must be at least 1");
+    if (params.island_sync == 1) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: island_sync = 1 is refused (the results of islands that stop each other are not defined one by one)");
+    DevSolveParams sp = bioik::normalize_params(params, first_query, n, 8 * (size_t)p->model->dev.cus);
+    if (params.islands <= 0 && sp.islands < k) sp.islands = k;  // BIOIK_ISLANDS_AUTO
+    sp.island_sync = 0;
+    if (sp.islands > 64) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: at most 64 islands (a lane of one wavefront each)");
+    if (k > sp.islands) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: k = " + std::to_string(k) + " is more than the call's " + std::to_string(sp.islands) + " islands");
+    return sp;
+}
+static RankedArgs ranked_args(int32_t k, double min_distance, double* solutions, double* fitness, int32_t* success, int32_t* steps, int32_t* count) {
+    RankedArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.k = k, r.min_distance = min_distance;
+    r.solutions = solutions, r.fitness = fitness, r.success = success, r.steps = steps, r.count = count;
+    return r;
+}
+struct RankedCall {  // a ranked solve through the host-pointer path (io_begin): its checked parameters, k, the distance, where the counts go
+    DevSolveParams sp;
+    int32_t k;
+    double min_distance;
+    int32_t* count;
+};
+
 // host arrays in, host arrays out: staged through a slot's page-locked arena, one DMA each way, on the slot's own stream.
 // io_finish: the slot's solve is complete and its results are in the caller's arrays (no-op for an idle slot).  Called with p->mtx held.
 static void io_finish(bioik_problem* p, bioik_problem::IoSlot& sl) {
@@ -1344,22 +1391,27 @@ static void io_finish(bioik_problem* p, bioik_problem::IoSlot& sl) {
     }
     const size_t V = p->host.dev.V;
     const char* hd = (const char*)sl.host;
-    std::memcpy(sl.solutions, hd + sl.o_sol, sl.n * V * 8);
-    std::memcpy(sl.fitness, hd + sl.o_fit, sl.n * 8);
-    std::memcpy(sl.success, hd + sl.o_suc, sl.n * 4);
-    std::memcpy(sl.steps, hd + sl.o_steps, sl.n * 4);
+    const size_t rows = sl.n * sl.rows;
+    std::memcpy(sl.solutions, hd + sl.o_sol, rows * V * 8);
+    std::memcpy(sl.fitness, hd + sl.o_fit, rows * 8);
+    std::memcpy(sl.success, hd + sl.o_suc, rows * 4);
+    std::memcpy(sl.steps, hd + sl.o_steps, rows * 4);
+    if (sl.count) std::memcpy(sl.count, hd + sl.o_cnt, sl.n * 4);
 }
 // io_begin: copy in, enqueue the transfer in, the solve and the transfer out on the slot's stream; returns without waiting.
 // A solve still pending on the slot is completed first (its results reach its caller's arrays).  Called with p->mtx held.
 static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticket, const bioik_solve_params& params, uint64_t first_query, size_t n,
-                     const double* seeds, const double* goal_params, double* solutions, double* fitness, int32_t* success, int32_t* steps) {
+                     const double* seeds, const double* goal_params, double* solutions, double* fitness, int32_t* success, int32_t* steps,
+                     const RankedCall* ranked = nullptr) {
     io_finish(p, sl);
     DeviceGuard on_device(p->model->device);
     const size_t V = p->host.dev.V, P = p->host.dev.P;
     // arena layout: [seeds | goal_params] in, [solutions | fitness | success | steps] out, every block 64-byte aligned
     auto up = [](size_t b) { return (b + 63) / 64 * 64; };
     const size_t o_seeds = 0, o_par = o_seeds + up(n * V * 8), in_bytes = o_par + up(n * P * 8);
-    const size_t o_sol = in_bytes, o_fit = o_sol + up(n * V * 8), o_suc = o_fit + up(n * 8), o_steps = o_suc + up(n * 4), total = o_steps + up(n * 4);
+    const size_t K = ranked ? (size_t)ranked->k : 1;  // result rows per query; a ranked solve adds count [n]
+    const size_t o_sol = in_bytes, o_fit = o_sol + up(n * K * V * 8), o_suc = o_fit + up(n * K * 8), o_steps = o_suc + up(n * K * 4), o_cnt = o_steps + up(n * K * 4),
+                 total = o_cnt + (ranked ? up(n * 4) : 0);
     if (sl.bytes < total) {
         be_free(sl.dev);
         be_free_pinned(sl.host);
@@ -1380,19 +1432,24 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     const bool direct_inputs = n <= 16;
     if (!direct_inputs) be_h2d(dd, hd, in_bytes, st);
     const char* in_base = direct_inputs ? hd : dd;
-    DevSolveParams sp = bioik::normalize_params(params, first_query, n, 8 * (size_t)p->model->dev.cus);
+    DevSolveParams sp = ranked ? ranked->sp : bioik::normalize_params(params, first_query, n, 8 * (size_t)p->model->dev.cus);
     // The results go from the kernels straight into the page-locked arena (it is mapped into the device's address space; 1.5 MB per 4096 queries,
     // written once per query).  A transfer out enqueued behind the solve would sit at the head of a DMA queue until the solve is over -- 12 ms
     // for a one-launch solve -- with the transfers in of the handle's next solves behind it: nothing would overlap
     // (profiles/r03_inflight_and_schedule.log, host pipeline).
-    solve_dispatch(p, sp, n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
-                   (int32_t*)(hd + o_steps), st, true, p->h_error + (&sl - p->io));
-    sl.pending = true, sl.ticket = ticket, sl.n = n;
-    sl.o_sol = o_sol, sl.o_fit = o_fit, sl.o_suc = o_suc, sl.o_steps = o_steps;
-    sl.solutions = solutions, sl.fitness = fitness, sl.success = success, sl.steps = steps;
+    if (ranked) {  // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
+        const RankedArgs r = ranked_args(ranked->k, ranked->min_distance, (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc), (int32_t*)(hd + o_steps), (int32_t*)(hd + o_cnt));
+        launch_solve(p, sp, n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), r.solutions, r.fitness, r.success, r.steps, st, switches(), p->h_error + (&sl - p->io), &r);
+    } else {
+        solve_dispatch(p, sp, n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
+                       (int32_t*)(hd + o_steps), st, true, p->h_error + (&sl - p->io));
+    }
+    sl.pending = true, sl.ticket = ticket, sl.n = n, sl.rows = K;
+    sl.o_sol = o_sol, sl.o_fit = o_fit, sl.o_suc = o_suc, sl.o_steps = o_steps, sl.o_cnt = o_cnt;
+    sl.solutions = solutions, sl.fitness = fitness, sl.success = success, sl.steps = steps, sl.count = ranked ? ranked->count : nullptr;
 }
 static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint64_t first_query, size_t n, const double* seeds, const double* goal_params,
-                       double* solutions, double* fitness, int32_t* success, int32_t* steps) {
+                       double* solutions, double* fitness, int32_t* success, int32_t* steps, const RankedCall* ranked = nullptr) {
     if (n == 0) return;
     std::lock_guard<std::mutex> lock(p->mtx);
     const uint64_t ticket = p->next_ticket++;
@@ -1405,7 +1462,7 @@ static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint6
             break;
         }
     bioik_problem::IoSlot& sl = p->io[pick];
-    io_begin(p, sl, ticket, params, first_query, n, seeds, goal_params, solutions, fitness, success, steps);
+    io_begin(p, sl, ticket, params, first_query, n, seeds, goal_params, solutions, fitness, success, steps, ranked);
     io_finish(p, sl);
     if (sl.failed_ticket == ticket) throw Error(sl.failed_code, "the solve failed on the device: " + sl.failed_message);  // (the synchronous call is its own ticket's wait)
 }
@@ -1417,6 +1474,36 @@ int bioik_solve_batch(bioik_problem* p, const bioik_solve_params* params, size_t
     if (n && (!seeds || !solutions || !fitness || !success || !steps || (p->host.dev.P > 0 && !goal_params)))
         throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
     solve_host(p, *params, p->first_query, n, seeds, goal_params, solutions, fitness, success, steps);
+    API_END
+}
+
+int bioik_solve_batch_ranked_device(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* d_seeds,
+                                    const double* d_goal_params, double* d_solutions, double* d_fitness, int32_t* d_success, int32_t* d_steps, int32_t* d_count,
+                                    void* hip_stream) {
+    API_BEGIN
+    if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n && (!d_seeds || !d_solutions || !d_fitness || !d_success || !d_steps || (p->host.dev.P > 0 && !d_goal_params)))
+        throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    std::lock_guard<std::mutex> lock(p->mtx);
+    DeviceGuard on_device(p->model->device);
+    const DevSolveParams sp = ranked_params(p, *params, p->first_query, n, k, d_count);
+    if (p->h_error[bioik_problem::kIoSlots] != 0u) {
+        p->h_error[bioik_problem::kIoSlots] = 0u;
+        throw Error(BIOIK_ERR_HIP, "an earlier solve of this handle through a device-pointer entry timed out at a rendezvous between its wavefronts (k_solve_lean_cl4h): its results are not valid");
+    }
+    const RankedArgs r = ranked_args(k, min_distance, d_solutions, d_fitness, d_success, d_steps, d_count);
+    // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
+    launch_solve(p, sp, n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, (stream_t)hip_stream, switches(), p->h_error + bioik_problem::kIoSlots, &r);
+    API_END
+}
+int bioik_solve_batch_ranked(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* seeds,
+                             const double* goal_params, double* solutions, double* fitness, int32_t* success, int32_t* steps, int32_t* count) {
+    API_BEGIN
+    if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n && (!seeds || !solutions || !fitness || !success || !steps || (p->host.dev.P > 0 && !goal_params))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    const uint64_t first_query = p->first_query;
+    const RankedCall call{ranked_params(p, *params, first_query, n, k, count), k, min_distance, count};
+    solve_host(p, *params, first_query, n, seeds, goal_params, solutions, fitness, success, steps, &call);  // (the handle's arena, lock and slots, as bioik_solve_batch)
     API_END
 }
 

@@ -472,6 +472,90 @@ BIOIK_DEV void select_coop(const SelectArgs& a, uint64_t q, int lane) {
     }
 }
 
+// The k best DISTINCT islands of every query, ranked (bioik_solve_batch_ranked): ONE WAVEFRONT per query, lane = island (islands <= 64), over the per-island
+// arrays a solve without the fused reduction leaves behind.
+//   order     ik_parallel.h:220-269 read as a total order: the islands that passed by ascending isl_fitness (which holds the secondary term of a success, as
+//             select_body compares it), then the islands that did not by ascending isl_fitness, equal values by island index.  Rank 0 is the island select_body
+//             and select_coop pick with sync = 0.
+//   distinct  rows are taken greedily in rank order: a row is kept iff against every row kept before it max over the ACTIVE variables |a - b| > min_distance
+//             (plain IEEE subtraction, fabs, max: numpy gives the same bits); min_distance < 0 keeps everything.
+//   output    the first min(k, kept) kept rows in rank order, count[q] of them; the rows behind them hold the query's seed, fitness +inf, success 0, steps 0.
+// lds: D x 64 doubles, the active genes as [gene][island] (a column per lane: the candidate's gene is one broadcast read, a lane's own gene its own bank pair).
+struct RankedArgs {
+    ProbPtr pb;
+    int islands, V, D, k;
+    uint64_t n;
+    double min_distance;
+    const double* seeds;  // [n][V]
+    const double* isl_solutions;
+    const double* isl_fitness;
+    const int32_t* isl_success;
+    const int32_t* isl_steps;
+    double* solutions;  // [n][k][V]
+    double* fitness;    // [n][k]
+    int32_t* success;   // [n][k]
+    int32_t* steps;     // [n][k]
+    int32_t* count;     // [n]
+};
+BIOIK_DEV void select_ranked(const RankedArgs& a, uint64_t q, int lane, double* lds) {
+    if (a.islands == 1) {  // one island: the solve wrote the caller's row itself (SolveLauncher::result_arrays), k = 1
+        if (lane == 0) a.count[q] = 1;
+        return;
+    }
+    const uint64_t u0 = q * (uint64_t)a.islands;
+    const bool mine = lane < a.islands;
+    const double f = mine ? p_load_device(a.isl_fitness + u0 + lane) : P_INF;
+    const int suc = mine ? p_load_device(a.isl_success + u0 + lane) : 0;
+    const int st = mine ? p_load_device(a.isl_steps + u0 + lane) : 0;
+    const bool distinct = a.min_distance >= 0.0;  // (wavefront-uniform)
+    if (distinct) {
+        for (int g = 0; g < a.D; g++) {
+            const int var = a.pb->ops[a.pb->op_of_gene[g]].var;
+            if (mine) lds[g * 64 + lane] = p_load_device(a.isl_solutions + (u0 + lane) * a.V + var);
+        }
+        p_wave_sync();
+    }
+    // rank = the number of islands in front of this one.  (A fitness that is no number orders as +inf: the order stays total, every rank has one owner.)
+    const unsigned long long passed = p_ballot(mine && suc != 0);
+    const double fo = f == f ? f : P_INF;
+    int rank = 0;
+    for (int j = 0; j < a.islands; j++) {
+        const double fj = p_read_lane(fo, j);
+        const bool pj = (passed >> j) & 1ull, pm = suc != 0;
+        const bool before = pj != pm ? pj : (fj < fo || (fj == fo && j < lane));
+        rank += before ? 1 : 0;
+    }
+    // greedy pass in rank order: slot = the output row of this lane's island, -1: none
+    int slot = -1, n_out = 0;
+    for (int r = 0; r < a.islands && n_out < a.k; r++) {
+        const int c = __builtin_ctzll(p_ballot(mine && rank == r) | (1ull << 63));  // the island of rank r (wavefront-uniform)
+        bool close = false;
+        if (distinct) {
+            double d = 0.0;
+            if (slot >= 0)
+                for (int g = 0; g < a.D; g++) {
+                    const double t = fabs(lds[g * 64 + lane] - lds[g * 64 + c]);
+                    d = t > d ? t : d;
+                }
+            close = slot >= 0 && !(d > a.min_distance);
+        }
+        if (p_ballot(close) == 0ull) {
+            if (lane == c) slot = n_out;
+            n_out++;
+        }
+    }
+    // the rows: lanes stride over V
+    const uint64_t o0 = q * (uint64_t)a.k;
+    for (int s = 0; s < a.k; s++) {
+        const double* src = a.seeds + q * a.V;
+        if (s < n_out) src = a.isl_solutions + (u0 + (uint64_t)__builtin_ctzll(p_ballot(slot == s) | (1ull << 63))) * a.V;
+        for (int v = lane; v < a.V; v += 64) a.solutions[(o0 + s) * a.V + v] = p_load_device(src + v);
+    }
+    if (slot >= 0) a.fitness[o0 + slot] = f, a.success[o0 + slot] = suc, a.steps[o0 + slot] = st;
+    if (lane >= n_out && lane < a.k) a.fitness[o0 + lane] = P_INF, a.success[o0 + lane] = 0, a.steps[o0 + lane] = 0;
+    if (lane == 0) a.count[q] = n_out;
+}
+
 struct SolveArgs {
     ProbPtr pb;
     DevSolveParams sp;

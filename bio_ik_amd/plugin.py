@@ -30,7 +30,8 @@ class _Settings(C.Structure):  # bioik_plugin_settings (cpp/src/plugin_shim.cpp)
                 ("position_only_ik", C.c_int32), ("gpu_population", C.c_int32), ("gpu_islands", C.c_int32), ("gpu_max_steps", C.c_int32),
                 ("gpu_reproducible_calls", C.c_int32), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32)),
                 ("dpos", C.c_double), ("drot", C.c_double), ("dtwist", C.c_double), ("rotation_scale", C.c_double),
-                ("center_joints_weight", C.c_double), ("avoid_joint_limits_weight", C.c_double), ("minimal_displacement_weight", C.c_double)]
+                ("center_joints_weight", C.c_double), ("avoid_joint_limits_weight", C.c_double), ("minimal_displacement_weight", C.c_double),
+                ("gpu_island_sync", C.c_int32), ("reserved", C.c_int32)]
 
 
 class _WireGoal(C.Structure):  # bioik_plugin_goal
@@ -68,6 +69,8 @@ def load_shim(path=None):
     L.bioik_plugin_submit.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, C.POINTER(u64)]
     L.bioik_plugin_wait.argtypes = [vp, u64, dp, C.POINTER(C.c_uint8), dp]
     L.bioik_plugin_search_each.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, dp, C.POINTER(C.c_uint8), dp, dp]
+    L.bioik_plugin_search_ranked.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, i32, C.c_double, dp, C.POINTER(C.c_uint8),
+                                             C.POINTER(i32)]
     L.bioik_plugin_postprocess.argtypes = [vp, u64, dp, dp, u32, C.POINTER(i32)]
     _shims[path] = L
     return L
@@ -96,6 +99,8 @@ DEFAULT_PARAMS = {
     "minimal_displacement_weight": 0.0,
     # additive keys of the GPU build
     "gpu_population": 128, "gpu_fk": "exact", "gpu_islands": 0, "gpu_max_steps": 64, "gpu_devices": None, "gpu_reproducible_calls": False, "gpu_schedule": "auto",
+    "gpu_island_sync": True,  # islands stop each other (the reference's island loop); False: every island to its own end
+    "gpu_solutions": 8, "gpu_solution_distance": 0.1,  # searchPositionIKRanked: solutions per pose and how far apart (max over the joints, rad / m)
 }
 
 
@@ -131,7 +136,7 @@ class BioIKKinematicsPlugin:
                       gpu_reproducible_calls=int(bool(p["gpu_reproducible_calls"])), n_devices=len(devices), devices=abi.iptr(devices),
                       dpos=float(p["dpos"]), drot=float(p["drot"]), dtwist=float(p["dtwist"]), rotation_scale=float(p["rotation_scale"]),
                       center_joints_weight=float(p["center_joints_weight"]), avoid_joint_limits_weight=float(p["avoid_joint_limits_weight"]),
-                      minimal_displacement_weight=float(p["minimal_displacement_weight"]))
+                      minimal_displacement_weight=float(p["minimal_displacement_weight"]), gpu_island_sync=int(bool(p["gpu_island_sync"])))
         return s, devices
 
     def _push_params(self):
@@ -193,6 +198,28 @@ class BioIKKinematicsPlugin:
         searchPositionIKBatchWait.  ik_poses [n][tips][7] in the base frame (ignored when options.replace), ik_seed_states
         [n][group variables], context_state [variables] (None: the model's default positions, :465-472).  `timeout` [s] bounds the
         call on the device clock (ik_parallel.h:160; every query still runs one step), <= 0: only gpu_max_steps applies."""
+        a, n, bio, keep = self._marshal(ik_poses, ik_seed_states, options, context_state, timeout)
+        ticket = C.c_uint64()
+        self._chk(self._L.bioik_plugin_submit(self._h, *a, C.byref(ticket)))
+        return (ticket.value, n, bio)
+
+    def searchPositionIKRanked(self, ik_poses, ik_seed_states, k=None, min_distance=None, options=None, context_state=None, timeout=0.0):
+        """Up to k distinct solutions per pose, best first (MoveIt's multi-solution getPositionIK, batched): the islands of every query ranked on the device
+        (bioik_solve_batch_ranked with islands = max(k, gpu_islands resolved), island_sync off), every row wrapped towards the seed and bounded like
+        searchPositionIKBatch's, rows that coincide after wrapping dropped; rows that did not pass only with return_approximate_solution.  k / min_distance
+        default to the keys gpu_solutions / gpu_solution_distance.  Callback goals are refused.
+        -> (solutions: list of [count_q][group variables] arrays, passed: list of bool arrays)"""
+        k = int(self.params["gpu_solutions"] if k is None else k)
+        min_distance = float(self.params["gpu_solution_distance"] if min_distance is None else min_distance)
+        a, n, bio, keep = self._marshal(ik_poses, ik_seed_states, options, context_state, timeout)
+        G = len(self._group_vars)
+        kk = max(k, 1)
+        sol, ok, count = np.zeros((n, kk, G)), np.zeros((n, kk), dtype=np.uint8), np.zeros(n, dtype=np.int32)
+        self._chk(self._L.bioik_plugin_search_ranked(self._h, *a, k, min_distance, abi.dptr(sol), abi.u8ptr(ok), abi.iptr(count)))
+        return [sol[q, :count[q]].copy() for q in range(n)], [ok[q, :count[q]] != 0 for q in range(n)]
+
+    def _marshal(self, ik_poses, ik_seed_states, options, context_state, timeout):
+        """the arguments bioik_plugin_submit and bioik_plugin_search_ranked share (and what they point to)"""
         self._push_params()
         options = options or KinematicsQueryOptions()
         m = self.robot_model
@@ -223,11 +250,10 @@ class BioIKKinematicsPlugin:
             base = link_transform(m, self._base_link, context)  # :487-502
         base = np.ascontiguousarray(base, dtype=np.float64)
         poses = np.zeros(0) if replace else np.ascontiguousarray(np.asarray(ik_poses, dtype=np.float64).reshape(n, len(self.tip_frames), 7))
-        ticket = C.c_uint64()
-        self._chk(self._L.bioik_plugin_submit(self._h, n, abi.dptr(seeds), abi.dptr(poses) if poses.size else None, abi.dptr(base), abi.dptr(context),
-                                              len(caller), wire, int(replace), len(fixed), _strs(fixed), float(timeout) if timeout and timeout > 0.0 else 0.0,
-                                              int(bool(getattr(options, "return_approximate_solution", False))), C.byref(ticket)))
-        return (ticket.value, n, bio)
+        fx = _strs(fixed)
+        a = (n, abi.dptr(seeds), abi.dptr(poses) if poses.size else None, abi.dptr(base), abi.dptr(context), len(caller), wire, int(replace), len(fixed), fx,
+             float(timeout) if timeout and timeout > 0.0 else 0.0, int(bool(getattr(options, "return_approximate_solution", False))))
+        return a, n, bio, (keep, seeds, poses, base, context, wire, fx)
 
     def searchPositionIKBatchWait(self, pending):
         """-> (solutions [n][group variables], ok [n] bool, fitness [n], error codes [n])"""

@@ -28,7 +28,7 @@ EXPORTS = [
     "bioik_problem_param_count", "bioik_problem_variable_count", "bioik_problem_set_first_query", "bioik_solve_batch", "bioik_solve_batch_multi",
     "bioik_solve_batch_device", "bioik_eval_fk", "bioik_eval_fitness", "bioik_eval_approximator", "bioik_eval_reproduce",
     "bioik_eval_check", "bioik_stream_fitness_device", "bioik_solve_batch_submit", "bioik_solve_batch_wait", "bioik_debug_reload_switches", "bioik_eval_arith",
-    "bioik_resolve_islands",
+    "bioik_resolve_islands", "bioik_solve_batch_ranked", "bioik_solve_batch_ranked_device",
 ]
 
 
@@ -68,6 +68,9 @@ def _declare(L):
         L.bioik_eval_arith.argtypes = [C.c_int, C.c_int, C.c_size_t, _pd, _pd]
     L.bioik_stream_fitness_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bioik_resolve_islands.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, _pi, _pi]
+    L.bioik_solve_batch_ranked.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, _pd, _pd, _pd, _pd, _pi, _pi, _pi]
+    L.bioik_solve_batch_ranked_device.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -237,6 +240,29 @@ class HipSolver:
         steps = np.zeros(n, dtype=np.int32)
         self._chk(self.L.bioik_solve_batch(self.problem, C.byref(params), n, _d(s), _d(gp), _d(sol), _d(fit), _i(suc), _i(steps)))
         return sol, fit, suc, steps
+
+    def solve_batch_ranked(self, params, seeds, goal_params, k, min_distance=-1.0):
+        """bioik_solve_batch_ranked: the k best distinct islands of every query, ranked (include/bioik_hip.h: order, distance, fill) ->
+        (solutions [n][k][V], fitness [n][k], success [n][k], steps [n][k], count [n])."""
+        sync_debug_switches(self.L)
+        s = _f64(seeds).reshape(-1, self.V)
+        n, k = s.shape[0], int(k)
+        gp = self._gp(goal_params, n)
+        kk = max(k, 0)
+        sol = np.zeros((n, kk, self.V))
+        fit = np.zeros((n, kk))
+        suc = np.zeros((n, kk), dtype=np.int32)
+        steps = np.zeros((n, kk), dtype=np.int32)
+        count = np.zeros(n, dtype=np.int32)
+        self._chk(self.L.bioik_solve_batch_ranked(self.problem, C.byref(params), n, k, float(min_distance), _d(s), _d(gp), _d(sol), _d(fit), _i(suc), _i(steps),
+                                                  _i(count)))
+        return sol, fit, suc, steps, count
+
+    def solve_batch_ranked_device(self, params, n, k, min_distance, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, d_count, stream=0):
+        """The ranked solve on device pointers (ints): enqueues on `stream`, does not synchronise."""
+        sync_debug_switches(self.L)
+        self._chk(self.L.bioik_solve_batch_ranked_device(self.problem, C.byref(params), int(n), int(k), float(min_distance), d_seeds, d_goal_params, d_solutions,
+                                                         d_fitness, d_success, d_steps, d_count, stream))
 
     def submit_batch(self, params, seeds, goal_params):
         """bioik_solve_batch_submit: the same solve without waiting.  Returns a ticket object; `wait_batch(ticket)` returns what solve_batch

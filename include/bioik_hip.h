@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6 (round 6): bioik_resolve_islands (the island count BIOIK_ISLANDS_AUTO gives a call of n queries, for callers that shard a request themselves);
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_batch_ranked, bioik_solve_batch_ranked_device (the k best distinct islands of every query).
+                               6 (round 6): bioik_resolve_islands (the island count BIOIK_ISLANDS_AUTO gives a call of n queries, for callers that shard a request themselves);
                                a rendezvous time-out inside a workgroup is BIOIK_ERR_HIP for its call; a line-search candidate with a joint value of magnitude >= 1e300 is no candidate.
                                5 (round 5): bioik_solve_params::islands = 0 means BIOIK_ISLANDS_AUTO (versions up to 4 took 0 as 1); `timeout` counts from the call */
 
@@ -354,6 +355,30 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds,
                              const double* d_goal_params, double* d_solutions, double* d_fitness,
                              int32_t* d_success, int32_t* d_steps, void* hip_stream);
+
+/* RANKED SOLVES: the k best DISTINCT solutions of every query instead of the best one (MoveIt: the KinematicsBase::getPositionIK overload that fills a
+ * std::vector<std::vector<double>>).  A query's islands are independent searches; each ends with a complete result, and where bioik_solve_batch keeps the
+ * best island (reference src/ik_parallel.h:220-269) these entries rank all of them on the device and return the first k that differ:
+ *   order     ik_parallel.h:220-269 read as a total order: the islands that passed come first, by ascending fitness (for a success that figure holds the
+ *             secondary goals' term, exactly what the reference compares); then the islands that did not pass, by ascending fitness; ties go to the lower
+ *             island index.  Row 0 is therefore the island bioik_solve_batch returns with the same parameters and island_sync = 0, bit for bit.
+ *   distance  rows are taken greedily in that order: a row is kept iff, against EVERY row kept before it, the maximum over the problem's active variables of
+ *             |a - b| is greater than min_distance (a plain IEEE difference, fabs and max: no wrapping modulo 2 pi).  min_distance < 0 keeps every row,
+ *             min_distance = 0 drops only rows equal in every active variable.  Inactive variables are the seed's in every island and take no part.
+ *   fill      per query the first min(k, kept) kept rows go to solutions [n][k][V], fitness [n][k], success [n][k], steps [n][k], and count [n] is their
+ *             number; the rows from count to k - 1 hold the query's seed row, fitness +inf, success 0 and steps 0.  Every byte of the outputs is defined.
+ * `params` as for bioik_solve_batch, with 1 <= k <= islands <= 64 and count != NULL (else BIOIK_ERR_INVALID_ARGUMENT, nothing launched, outputs untouched);
+ * island_sync = 1 is refused the same way (islands that stop each other leave at timing-dependent steps: their individual results are not defined);
+ * BIOIK_ISLANDS_AUTO resolves to max(k, what bioik_resolve_islands gives) with island_sync off.  Every solver mode, a timeout, bioik_problem_set_first_query.
+ * The host form goes through the handle's page-locked arena under the handle's lock, as bioik_solve_batch.  The device form enqueues on `hip_stream` and
+ * returns; it may be captured into a hipGraph under the contract of bioik_solve_batch_device (one eager call of the same plan first; a linear chain of
+ * kernels, no memset node).  Neither takes nor changes the handle's measured mapping choice. */
+int bioik_solve_batch_ranked(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* seeds,
+                             const double* goal_params, double* solutions /*[n][k][V]*/, double* fitness /*[n][k]*/, int32_t* success /*[n][k]*/,
+                             int32_t* steps /*[n][k]*/, int32_t* count /*[n]*/);
+int bioik_solve_batch_ranked_device(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* d_seeds,
+                                    const double* d_goal_params, double* d_solutions, double* d_fitness, int32_t* d_success, int32_t* d_steps,
+                                    int32_t* d_count, void* hip_stream);
 
 /* ---- function-level entry points (device-resident math exposed one function at a time so that
  *      each kernel can be parity-checked against the matching reference function) -------------- */
