@@ -52,9 +52,15 @@ protected:
     std::vector<double> velocity_weights_;
     const RobotInfo* robot_info_ = nullptr;
     mutable std::vector<double> temp_vector_;
+    std::vector<const std::vector<double>*> goal_link_points_;  // per link of the goal: its collision points x y z r in the link frame (TouchGoal), or null
 
 public:
     GoalContext() {}
+    // the collision points of the goal's i-th link, rows x y z r in the link frame: what the reference's TouchGoal takes from getRobotModel() (goal_types.cpp:56-69)
+    const std::vector<double>& getLinkPoints(size_t i = 0) const {
+        static const std::vector<double> none;
+        return i < goal_link_points_.size() && goal_link_points_[i] ? *goal_link_points_[i] : none;
+    }
     const Frame& getLinkFrame(size_t i = 0) const { return tip_link_frames_[goal_link_indices_[i]]; }
     double getVariablePosition(size_t i = 0) const {
         const ssize_t j = goal_variable_indices_[i];

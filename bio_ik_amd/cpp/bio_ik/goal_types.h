@@ -376,7 +376,39 @@ public:
     }
 };
 
-// TouchGoal (:330-377) needs FCL collision shapes of the robot's links: not provided by this build.
+// TouchGoal (:330-377, goal_types.cpp:45-229): the collision shapes of the link touch the plane through `position` with `normal`.  No FCL: the shapes are the
+// link's collision points x y z r of the robot model (RobotModel::addCollisionBox / Sphere / Points, the URDF reader, or LinkModel::getShapes() in the
+// MoveIt plugin), and the cost is the squared support distance of that set along the normal (include/bioik_hip.h: BIOIK_GOAL_TOUCH)
+class TouchGoal : public LinkGoalBase {
+    Vector3 position, normal;
+
+public:
+    TouchGoal() : position(0, 0, 0), normal(0, 0, 0) {}
+    TouchGoal(const std::string& link_name, const Vector3& position_, const Vector3& normal_, double weight = 1.0)
+        : LinkGoalBase(link_name, weight), position(position_), normal(normal_.normalized()) {}
+    const Vector3& getPosition() const { return position; }
+    const Vector3& getNormal() const { return normal; }
+    // d = min_i (n_l . v_i - r_i) - normal . (position - p), n_l = the normal turned by the conjugate of the link's quaternion (tf2's inverse(), goal_types.cpp:170)
+    static double distance(const Frame& fb, const Vector3& position, const Vector3& normal, const std::vector<double>& points) {
+        const Quaternion q = fb.getOrientation();
+        // v + 2 (w t + u x t), t = u x v with u = -q.xyz: the quaternion as it is, unit or not (frame.h:108-149)
+        const Vector3 u(-q.x(), -q.y(), -q.z());
+        const Vector3 t = u.cross(normal);
+        const Vector3 nl = normal + (t * q.w() + u.cross(t)) * 2.0;
+        double dmin = DBL_MAX;  // (a link without shapes: the reference's DBL_MAX, goal_types.cpp:154)
+        for (size_t i = 0; i + 4 <= points.size(); i += 4) {
+            if (points[i + 3] < 0) continue;  // (the marker of a shape that is no point set: the device refuses such a link)
+            dmin = std::fmin(dmin, nl.x() * points[i] + nl.y() * points[i + 1] + nl.z() * points[i + 2] - points[i + 3]);
+        }
+        return dmin - normal.dot(position - fb.getPosition());
+    }
+    double evaluate(const GoalContext& context) const override {
+        const double d = distance(context.getLinkFrame(), position, normal, context.getLinkPoints());
+        return d * d;
+    }
+    int gpuOpcode() const override { return BIOIK_GOAL_TOUCH; }
+    void gpuParams(std::vector<double>& o) const override { o.insert(o.end(), {position.x(), position.y(), position.z(), normal.x(), normal.y(), normal.z()}); }
+};
 
 class BalanceGoal : public Goal {  // goal_types.h:540-566, goal_types.cpp:231-272
     Vector3 target_, axis_;

@@ -101,6 +101,7 @@ public:
         mv.link_frame = [&rm](const std::string& link, const double* positions, double* frame7) {
             rm.linkTransform(rm.linkIndex(link), std::vector<double>(positions, positions + rm.variable_names.size()), frame7);
         };
+        mv.link_points = [&rm](const std::string& link) { return rm.collisionPoints(link); };
         joint_names.clear();
         for (int j : jmg.active_joints) {
             joint_names.push_back(rm.joint_names[j]);

@@ -47,6 +47,7 @@ struct ModelView {
     std::vector<double> var_max_velocity;  // VariableBounds::max_velocity_ (RobotInfo, include/bio_ik/robot_info.h:70-106)
     std::vector<uint8_t> var_prismatic;
     std::function<void(const std::string& link, const double* positions, double* frame7)> link_frame;  // global frame of a link at a full variable vector
+    std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal on the host); may be empty
 };
 
 struct Settings {  // IKParams (src/utils.h:64-85) as far as the device path reads them, + the additive gpu_* keys
@@ -450,6 +451,7 @@ public:
                 hm.info.addVariable(mv_.var_min[v], mv_.var_max[v], mv_.var_bounded[v] != 0, mv_.var_max_velocity[v], mv_.var_revolute[v] != 0,
                                     v < mv_.var_prismatic.size() && mv_.var_prismatic[v] != 0);
             hm.variable_index = mv_.variable_index;
+            hm.link_points = mv_.link_points;
             const ModelView* mv = &mv_;
             hm.link_frame = [mv](const std::string& name, const std::vector<double>& p) {
                 double f[7];

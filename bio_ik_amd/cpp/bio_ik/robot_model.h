@@ -26,6 +26,74 @@ public:
     std::vector<double> link_mass, link_center;  // urdf <inertial> mass / origin xyz per link (BalanceGoal); empty = none
     std::vector<uint8_t> var_bounded;
     std::map<std::string, JointModelGroup> groups;
+    // collision shapes as points (TouchGoal): per link rows x y z r in the link frame; r < 0 marks a shape that is no point set (a cylinder)
+    std::map<int, std::vector<double>> link_points;
+    struct MeshRef {  // a <mesh> collision a URDF names: its file is not loaded, the caller supplies the vertices (addCollisionPoints)
+        std::string filename;
+        double scale[3], origin[7];
+        bool resolved = false;  // set once vertices were added for the link
+    };
+    std::map<int, std::vector<MeshRef>> link_meshes;
+    mutable std::vector<int32_t> point_first_;  // flattened by desc()
+    mutable std::vector<double> points_flat_;
+
+    // points (x y z triples) with radii (empty: all 0), moved by the shape's collision origin (px py pz qx qy qz qw; null or the identity: untouched)
+    void addCollisionPoints(const std::string& link, const std::vector<double>& xyz, const std::vector<double>& radii = {}, const double* origin = nullptr) {
+        std::vector<double>& t = link_points[linkIndex(link)];
+        const bool ident = !origin || (origin[0] == 0 && origin[1] == 0 && origin[2] == 0 && origin[3] == 0 && origin[4] == 0 && origin[5] == 0 && origin[6] == 1);
+        for (size_t i = 0; i + 3 <= xyz.size(); i += 3) {
+            double v[3] = {xyz[i], xyz[i + 1], xyz[i + 2]};
+            if (!ident) {
+                double r[3];
+                rotate(origin + 3, v, r);
+                for (int c = 0; c < 3; c++) v[c] = r[c] + origin[c];
+            }
+            const double rad = radii.empty() ? 0.0 : radii[i / 3];
+            if (!(rad >= 0)) throw std::runtime_error("collision radii must be >= 0");
+            t.insert(t.end(), {v[0], v[1], v[2], rad});
+        }
+        auto mr = link_meshes.find(linkIndex(link));
+        if (mr != link_meshes.end())
+            for (MeshRef& r : mr->second) r.resolved = true;
+    }
+    void addCollisionBox(const std::string& link, const double (&size)[3], const double* origin = nullptr) {  // its 8 corners (exact)
+        std::vector<double> c;
+        for (int sx = -1; sx <= 1; sx += 2)
+            for (int sy = -1; sy <= 1; sy += 2)
+                for (int sz = -1; sz <= 1; sz += 2) c.insert(c.end(), {sx * 0.5 * size[0], sy * 0.5 * size[1], sz * 0.5 * size[2]});
+        const bool keep = meshesResolved(link);
+        addCollisionPoints(link, c, {}, origin);
+        if (!keep) unresolveMeshes(link);
+    }
+    void addCollisionSphere(const std::string& link, double radius, const double* origin = nullptr) {  // one point with a radius (exact)
+        const bool keep = meshesResolved(link);
+        addCollisionPoints(link, {0.0, 0.0, 0.0}, {radius}, origin);
+        if (!keep) unresolveMeshes(link);
+    }
+    void addCollisionUnsupported(const std::string& link) {  // a cylinder or a cone: a TouchGoal on this link is refused, never approximated
+        link_points[linkIndex(link)].insert(link_points[linkIndex(link)].end(), {0.0, 0.0, 0.0, -1.0});
+    }
+    void addCollisionMeshRef(const std::string& link, const std::string& filename, const double (&scale)[3], const double (&origin)[7]) {
+        MeshRef r;
+        r.filename = filename;
+        for (int c = 0; c < 3; c++) r.scale[c] = scale[c];
+        for (int c = 0; c < 7; c++) r.origin[c] = origin[c];
+        link_meshes[linkIndex(link)].push_back(r);
+    }
+    bool meshesResolved(const std::string& link) const {
+        auto mr = link_meshes.find(linkIndex(link));
+        if (mr == link_meshes.end()) return true;
+        for (const MeshRef& r : mr->second)
+            if (!r.resolved) return false;
+        return true;
+    }
+    void unresolveMeshes(const std::string& link) {
+        for (MeshRef& r : link_meshes[linkIndex(link)]) r.resolved = false;
+    }
+    const std::vector<double>* collisionPoints(const std::string& link) const {
+        auto it = link_points.find(linkIndex(link));
+        return it == link_points.end() ? nullptr : &it->second;
+    }
 
     static void quatFromRpy(double r, double p, double y, double* q) {
         double cr = std::cos(r / 2), sr = std::sin(r / 2), cp = std::cos(p / 2), sp = std::sin(p / 2), cy = std::cos(y / 2), sy = std::sin(y / 2);
@@ -152,6 +220,21 @@ public:
         d.joint_mimic_factor = joint_mimic_factor.data(), d.joint_mimic_offset = joint_mimic_offset.data();
         d.var_min = var_min.data(), d.var_max = var_max.data(), d.var_bounded = var_bounded.data(), d.var_max_velocity = var_max_velocity.data();
         if (link_mass.size() == link_names.size() && link_center.size() == 3 * link_names.size()) d.link_mass = link_mass.data(), d.link_center = link_center.data();
+        point_first_.assign(1, 0), points_flat_.clear();
+        for (size_t l = 0; l < link_names.size(); l++) {
+            auto it = link_points.find((int)l);
+            if (it != link_points.end()) points_flat_.insert(points_flat_.end(), it->second.begin(), it->second.end());
+            // a <mesh> whose vertices nobody supplied: the link is marked like a shape without a point form, so a TouchGoal on it is refused and not scored on the rest
+            auto mr = link_meshes.find((int)l);
+            if (mr != link_meshes.end())
+                for (const MeshRef& r : mr->second)
+                    if (!r.resolved) {
+                        points_flat_.insert(points_flat_.end(), {0.0, 0.0, 0.0, -1.0});
+                        break;
+                    }
+            point_first_.push_back((int32_t)(points_flat_.size() / 4));
+        }
+        if (!points_flat_.empty()) d.link_point_first = point_first_.data(), d.link_points = points_flat_.data();
         return d;
     }
     // frame algebra for the plugin boundary (goal poses into the model frame, kinematics_plugin.cpp:487-502)

@@ -12,7 +12,8 @@
 //   * SRDF <group>: <chain base_link tip_link>, <joint name>, <link name> (= its parent joint), nested <group name>; <end_effector
 //     parent_link parent_group> names the tips of a group without a chain; <virtual_joint type = fixed | floating | planar> puts
 //     `parent_frame` in front of the root (the mobile or free-flying base of MoveIt).
-// Not read: collision / visual geometry, transmissions, xacro.
+// <collision> <origin> with <box> / <sphere>: the link's collision points (TouchGoal); <mesh filename scale>: recorded, not loaded (the caller supplies the
+// vertices; until then a TouchGoal on the link is refused); <cylinder>: recorded as a shape without a point form.  Not read: visual geometry, transmissions, xacro.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -342,6 +343,31 @@ inline std::shared_ptr<RobotModel> loadURDF(const std::string& urdf_xml, const s
         const std::vector<double> c = numbers(o ? o->find("xyz") : nullptr, 3, {0, 0, 0});
         m->setInertial(l->get("name"), number(ine->child("mass"), "value", 0.0), c[0], c[1], c[2]);
     }
+    for (const XmlNode* l : root.all("link"))  // <collision>: LinkModel::getShapes() / getCollisionOriginTransforms() in the order of the file (TouchGoal)
+        for (const XmlNode* c : l->all("collision")) {
+            const XmlNode* o = c->child("origin");
+            const XmlNode* geo = c->child("geometry");
+            if (!geo) continue;
+            const std::vector<double> xyz = numbers(o ? o->find("xyz") : nullptr, 3, {0, 0, 0}), rpy = numbers(o ? o->find("rpy") : nullptr, 3, {0, 0, 0});
+            double origin[7] = {xyz[0], xyz[1], xyz[2], 0, 0, 0, 1};
+            RobotModel::quatFromRpy(rpy[0], rpy[1], rpy[2], origin + 3);
+            const bool ident = xyz[0] == 0 && xyz[1] == 0 && xyz[2] == 0 && rpy[0] == 0 && rpy[1] == 0 && rpy[2] == 0;
+            const std::string name = l->get("name");
+            if (const XmlNode* b = geo->child("box")) {
+                const std::vector<double> s = numbers(b->find("size"), 3, {0, 0, 0});
+                const double size[3] = {s[0], s[1], s[2]};
+                m->addCollisionBox(name, size, ident ? nullptr : origin);
+            } else if (const XmlNode* s = geo->child("sphere")) {
+                m->addCollisionSphere(name, number(s, "radius", 0.0), ident ? nullptr : origin);
+            } else if (const XmlNode* me = geo->child("mesh")) {
+                const std::vector<double> sc = numbers(me->find("scale"), 3, {1, 1, 1});
+                const double scale[3] = {sc[0], sc[1], sc[2]};
+                if (ident) origin[3] = origin[4] = origin[5] = 0, origin[6] = 1;
+                m->addCollisionMeshRef(name, me->get("filename"), scale, origin);
+            } else if (geo->child("cylinder")) {
+                m->addCollisionUnsupported(name);
+            }
+        }
     if (!srdf_xml.empty()) addSRDFGroups(*m, srdf_xml);
     return m;
 }

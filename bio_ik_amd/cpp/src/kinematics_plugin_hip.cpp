@@ -68,6 +68,37 @@ struct FlatModel {
     std::vector<int32_t> link_parent, joint_type, joint_first_variable, joint_mimic;
     std::vector<double> link_origin, joint_axis, joint_mimic_factor, joint_mimic_offset, var_min, var_max, var_max_velocity, link_mass, link_center;
     std::vector<uint8_t> var_bounded;
+    // TouchGoal: the links' collision shapes as points x y z r in the link frame (bioik_model_desc::link_point_first / link_points), from what the
+    // reference's TouchGoal::describe reads (goal_types.cpp:56-69): a mesh's vertices, a box's corners, a sphere's centre with its radius; a shape that is
+    // no point set (cylinder, cone) leaves the marker row that makes a TouchGoal on the link a refusal
+    std::vector<int32_t> link_point_first{0};
+    std::vector<double> link_points;
+    std::vector<std::vector<double>> points_of_link;  // the same rows per link, for goals evaluated on the host
+    void addShapes(const moveit::core::LinkModel* l) {
+        std::vector<double> rows;
+        for (size_t s = 0; s < l->getShapes().size(); s++) {
+            const Eigen::Isometry3d& o = l->getCollisionOriginTransforms()[s];
+            auto put = [&](double x, double y, double z, double r) {
+                const Eigen::Vector3d v = o.linear() * Eigen::Vector3d(x, y, z) + o.translation();
+                rows.insert(rows.end(), {v.x(), v.y(), v.z(), r});
+            };
+            const shapes::Shape* sh = l->getShapes()[s].get();
+            if (auto* m = dynamic_cast<const shapes::Mesh*>(sh)) {
+                for (unsigned i = 0; i < m->vertex_count; i++) put(m->vertices[3 * i], m->vertices[3 * i + 1], m->vertices[3 * i + 2], 0.0);
+            } else if (auto* b = dynamic_cast<const shapes::Box*>(sh)) {
+                for (int sx = -1; sx <= 1; sx += 2)
+                    for (int sy = -1; sy <= 1; sy += 2)
+                        for (int sz = -1; sz <= 1; sz += 2) put(sx * 0.5 * b->size[0], sy * 0.5 * b->size[1], sz * 0.5 * b->size[2], 0.0);
+            } else if (auto* sp = dynamic_cast<const shapes::Sphere*>(sh)) {
+                put(0.0, 0.0, 0.0, sp->radius);
+            } else if (sh) {
+                rows.insert(rows.end(), {0.0, 0.0, 0.0, -1.0});
+            }
+        }
+        link_points.insert(link_points.end(), rows.begin(), rows.end());
+        link_point_first.push_back((int32_t)(link_points.size() / 4));
+        points_of_link.push_back(rows);
+    }
     explicit FlatModel(const moveit::core::RobotModel& rm) {
         const auto& links = rm.getLinkModels();
         for (const moveit::core::LinkModel* l : links) {
@@ -111,6 +142,7 @@ struct FlatModel {
             }
             link_mass.push_back(mass);
             link_center.insert(link_center.end(), c, c + 3);
+            addShapes(l);
         }
         for (const std::string& name : rm.getVariableNames()) {
             const moveit::core::VariableBounds& b = rm.getVariableBounds(name);
@@ -128,6 +160,7 @@ struct FlatModel {
         d.joint_mimic_factor = joint_mimic_factor.data(), d.joint_mimic_offset = joint_mimic_offset.data();
         d.var_min = var_min.data(), d.var_max = var_max.data(), d.var_bounded = var_bounded.data(), d.var_max_velocity = var_max_velocity.data();
         d.link_mass = link_mass.data(), d.link_center = link_center.data();
+        if (!link_points.empty()) d.link_point_first = link_point_first.data(), d.link_points = link_points.data();
         return d;
     }
 };
@@ -253,6 +286,11 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
             hs->update();
             const Frame7 f = toFrame(hs->getGlobalLinkTransform(link));
             for (int c = 0; c < 7; c++) frame7[c] = f.v[c];
+        };
+        const FlatModel* fm = flat.get();
+        mv.link_points = [rm, fm](const std::string& link) -> const std::vector<double>* {  // TouchGoal on the host (the hybrid path)
+            auto* l = rm->getLinkModel(link);
+            return l ? &fm->points_of_link[(size_t)l->getLinkIndex()] : nullptr;
         };
         mv.has_mimic = !rm->getMimicJointModels().empty();
         for (auto& joint_name : joint_names) {  // seed / solution vectors: the variables of the group's joints in this order (:473-484, :619-629)

@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
@@ -60,6 +61,7 @@ int goal_param_count(int type) {
         case BIOIK_GOAL_DIRECTION: return 6;
         case BIOIK_GOAL_CONE: return 11;
         case BIOIK_GOAL_BALANCE: return 6;
+        case BIOIK_GOAL_TOUCH: return 6;
     }
     return -1;
 }
@@ -76,7 +78,9 @@ static int joint_var_count(int type) {
 }
 
 HostModel::HostModel(const bioik_model_desc& d) {
-    if (d.struct_size != sizeof(bioik_model_desc)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: struct_size mismatch");
+    // (the descriptor grew by link_point_first / link_points without a new ABI version: a caller built against the header without them passes the shorter size)
+    const bool has_points = d.struct_size == sizeof(bioik_model_desc);
+    if (!has_points && d.struct_size != offsetof(bioik_model_desc, link_point_first)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: struct_size mismatch");
     if (d.n_links == 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "model has no links");
     if (!d.link_parent || !d.link_origin || !d.joint_type || !d.joint_axis || !d.joint_first_variable)
         throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: null link array");
@@ -104,6 +108,21 @@ HostModel::HostModel(const bioik_model_desc& d) {
         if (l.var_count > 0) {
             if (l.first_var < 0 || l.first_var + l.var_count > (int)d.n_variables) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "joint variable index out of range");
             for (int v = 0; v < l.var_count; v++) var_joint[l.first_var + v] = (int)i;
+        }
+    }
+    point_first.assign(d.n_links + 1, 0);
+    if (has_points && (d.link_point_first || d.link_points)) {
+        if (!d.link_point_first || !d.link_points) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_point_first and link_points go together");
+        if (d.link_point_first[0] != 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_point_first[0] must be 0");
+        for (uint32_t i = 0; i < d.n_links; i++)
+            if (d.link_point_first[i + 1] < d.link_point_first[i]) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_point_first must be ascending");
+        point_first.assign(d.link_point_first, d.link_point_first + d.n_links + 1);
+        points.assign(d.link_points, d.link_points + (size_t)point_first[d.n_links] * 4);
+        for (size_t i = 0; i < points.size(); i += 4) {
+            if (!(std::isfinite(points[i]) && std::isfinite(points[i + 1]) && std::isfinite(points[i + 2])))
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: a collision point is not finite");
+            if (!(std::isfinite(points[i + 3]) && (points[i + 3] >= 0.0 || points[i + 3] == -1.0)))
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the radius of a collision point must be finite and >= 0 (or exactly -1, the marker row)");
         }
     }
     // A joint that mimics a joint that itself mimics another: resolved to the joint at the end of the chain with the composed factor and offset, as MoveIt's
@@ -185,6 +204,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         long var;
         double weight;
         int secondary, param_off;
+        int point_first, point_count;  // TouchGoal: its link's points in touch_points
     };
     std::vector<G> goals;
     double balance_total = 0.0;
@@ -193,7 +213,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         const bioik_goal_desc& g = d.goals[gi];
         int np = goal_param_count(g.type);
         if (np < 0) throw Error(BIOIK_ERR_UNSUPPORTED, "goal type has no device implementation");
-        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count};
+        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0};
         if (g.link >= 0) {
             if (g.link >= nl) throw Error(BIOIK_ERR_NOT_FOUND, "link not found");
             info.tip = add_tip_link(g.link);
@@ -201,6 +221,21 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         if (g.variable >= 0) {
             if (g.variable >= nv) throw Error(BIOIK_ERR_NOT_FOUND, "joint variable not found");
             info.var = add_active_variable(g.variable);
+        }
+        if (g.type == BIOIK_GOAL_TOUCH) {  // TouchGoal::describe (goal_types.cpp:46-150): the shapes of the link, here as the points the model was given
+            if (g.link < 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "TouchGoal names no link");
+            const int first = m->point_first[g.link], count = m->point_first[g.link + 1] - first;
+            for (int i = 0; i < count; i++)
+                if (m->points[(size_t)(first + i) * 4 + 3] < 0.0)
+                    throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: a row of the link in bioik_model_desc::link_points has the radius -1, the marker of a shape that is no "
+                                                       "set of points (a cylinder, a cone, a mesh without its vertices): no device implementation, not approximated");
+            if (count <= 0)
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "TouchGoal: the link has no collision points (bioik_model_desc::link_points); the reference's cost would be DBL_MAX squared");
+            if (count > BIOIK_MAX_TOUCH_POINTS)
+                throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) +
+                                                       ") collision points: pass the mesh as its convex hull or decimated");
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = count;
+            touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
         }
         if (g.type == BIOIK_GOAL_BALANCE) {  // BalanceGoal::describe (goal_types.cpp:231-255): every link with mass becomes a tip, in link order
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, "BalanceGoal cannot be a secondary goal (the reference's has no such constructor)");
@@ -511,6 +546,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             if (g.var >= 0) o.var_op = dev.op_of_gene[g.var];
             else o.var_seed = (int)(-1 - g.var);
         }
+        if (g.type == BIOIK_GOAL_TOUCH) o.var_op = g.point_first, o.var_seed = g.point_count;
         o.param_off = g.param_off;
         return o;
     };

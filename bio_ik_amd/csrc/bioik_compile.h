@@ -35,6 +35,8 @@ struct HostModel {
     };
     std::vector<Link> links;
     std::vector<Var> vars;
+    std::vector<int> point_first;  // [links + 1] rows of `points` (bioik_model_desc::link_point_first); all zero: no link has shapes
+    std::vector<double> points;    // x y z r per collision point, link frame (TouchGoal)
     explicit HostModel(const bioik_model_desc& d);
 };
 
@@ -45,6 +47,7 @@ struct HostProblem {
     std::vector<int> active_variables;  // robot variable per gene
     std::vector<int> tip_links;         // link per public tip
     int param_count = 0;
+    std::vector<double> touch_points;   // the points of the links the TouchGoals name, goal after goal (DevGoal::var_op / var_seed index it): uploaded once by bioik_problem_create
     DevProblem dev;
     HostProblem(const HostModel* m, const bioik_problem_desc& d);
 };

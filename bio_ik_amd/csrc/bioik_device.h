@@ -21,7 +21,7 @@
 enum {
     G_POSITION = 0, G_ORIENTATION = 1, G_POSE = 2, G_LOOK_AT = 3, G_MAX_DISTANCE = 4, G_MIN_DISTANCE = 5, G_LINE = 6,
     G_PLANE = 7, G_AVOID_JOINT_LIMITS = 8, G_CENTER_JOINTS = 9, G_REGULARIZATION = 10, G_MINIMAL_DISPLACEMENT = 11,
-    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15
+    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15, G_TOUCH = 17
 };
 enum { FK_LINEAR = 0, FK_EXACT = 1 };
 
@@ -243,6 +243,42 @@ struct XV {
 // ---------------------------------------------------------------------------------------------------------
 // goal costs (goal_types.h); joint-set goals walk the active ops.
 // ---------------------------------------------------------------------------------------------------------
+// TouchGoal (goal_types.h:330-377, goal_types.cpp:152-228): the collision shapes of the link touch the plane (position P[0..2], unit normal P[3..5]).  The
+// shapes are points with a radius in the link frame (include/bioik_hip.h: BIOIK_GOAL_TOUCH), so the distance is the support function of a point set along the
+// normal turned into the link frame -- the brute-force minimum the reference keeps as a comment (goal_types.cpp:172-182) and its hill climb over the hull's
+// edges returns:   d = min_i (n_l . v_i - r_i) - normal . (position - p).
+// first / count: the goal's `count` >= 1 points x y z r in DevProblem::touch_points (global memory), the same for every lane -- the problem pointer and the
+// table address are made wavefront-uniform here (arguments of a real call arrive in vector registers), so the table is read with scalar loads
+// (s_load_dwordx16 per trip) and its numbers are SGPR operands of the FMAs: no vector memory, no LDS, no divergence.
+// Two points per trip into two independent minima, so the loop is not one dependency chain -- and no more than two: eight doubles of table per trip keep
+// the function inside the scalar registers a callee may use without saving any; a point left over joins the first.  min is exact: any order gives the
+// same number.  What the compiler makes of a point (gfx950, ROCm 7.2): three v_fma_f64, one v_min_f64, one v_max_f64 that canonicalises the loop-carried
+// minimum, and two v_mov_b32 that bring -r into a vector register (a VOP3 instruction of gfx9 reads one scalar operand): about five FP64 issue slots and two
+// moves.  A trip waits for its own scalar load (no load of the next trip in flight): with few wavefronts resident that latency shows.
+// One out-of-line copy, reached only from the general kernel flavour: the lean kernels are compiled without it.
+typedef decltype(&((ProbPtr)0)->pose_weight_sq) UniformF64;  // read-only doubles in the address space of the problem block
+BIOIK_CALL double goal_eval_touch(ProbPtr pb_, int first, int count, const lds_f64* P, F7 fb) {
+    const unsigned long long pba = (unsigned long long)pb_;
+    const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
+    const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * p_uniform(first));
+    const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
+    const int n = p_uniform(count);
+    const V3 normal = v3(P[3], P[4], P[5]);
+    const V3 nl = qrot(qinv(fb.q), normal);  // tf2's inverse(): the conjugate, no normalisation (goal_types.cpp:170)
+    double m0 = P_INF, m1 = P_INF;
+    int i = 0;
+    for (; i + 2 <= n; i += 2) {
+        const UniformF64 a = v + 4 * i;
+        m0 = fmin(m0, BK_FMA(nl.x, a[0], BK_FMA(nl.y, a[1], BK_FMA(nl.z, a[2], -a[3]))));
+        m1 = fmin(m1, BK_FMA(nl.x, a[4], BK_FMA(nl.y, a[5], BK_FMA(nl.z, a[6], -a[7]))));
+    }
+    if (i < n) {
+        const UniformF64 a = v + 4 * i;
+        m0 = fmin(m0, BK_FMA(nl.x, a[0], BK_FMA(nl.y, a[1], BK_FMA(nl.z, a[2], -a[3]))));
+    }
+    const double d = fmin(m0, m1) - dot3(normal, v3(P[0], P[1], P[2]) - fb.p);
+    return d * d;
+}
 // The link goals beyond position / orientation / pose: one out-of-line copy (sqrt, divisions, acos) instead of one per
 // evaluation site.  P: the goal's numbers (at most 11, goal_types.h) where they lie in LDS -- the pointer crosses the call with its
 // address space spelled out, and the 16 argument registers stay inside the 32 the calling convention passes without stack traffic.
@@ -488,8 +524,8 @@ BIOIK_DEV double pose_goal_cost(const double* P, const F7& fb) {
     return e;
 }
 // JS_INLINE: the goals over the joint values are inlined (the one hot site: secondary fitness of every child in the pre-selection)
-template <bool JS_INLINE = false, class XA = XV>
-BIOIK_DEV double goal_eval(ProbPtr pb, int type, int var_op, int var_seed, const double* P, const F7& fb, const XA& x, const QueryCtx& qc) {
+template <bool JS_INLINE = false, class XA = XV, class PB = ProbPtr>
+BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const double* P, const F7& fb, const XA& x, const QueryCtx& qc) {
     const int n_ops = pb->n_ops;
     switch (type) {
         case G_POSITION:  // goal_types.h:96
@@ -514,6 +550,10 @@ BIOIK_DEV double goal_eval(ProbPtr pb, int type, int var_op, int var_seed, const
                 return goal_eval_joint_set(pb, type, var_op, var_seed, type == G_JOINT_VARIABLE ? P[0] : 0.0, (const lds_f64*)x.p, x.s, (const lds_f64*)qc.seed);
             }
         default:  // the remaining link goals
+            // TouchGoal: only in the general flavour (the launcher hands a problem with one to k_solve, never to a lean kernel: those stay as they were).  A link
+            // goal has no variable: var_op / var_seed carry its first point and its number of points (DevGoal)
+            if constexpr (pb_flavour<PB>::general)
+                if (type == G_TOUCH) return goal_eval_touch(pb, var_op, var_seed, (const lds_f64*)P, fb);
             return goal_eval_link_rare(type, (const lds_f64*)P, fb);
     }
     return 0.0;
@@ -523,8 +563,8 @@ BIOIK_DEV double goal_eval(ProbPtr pb, int type, int var_op, int var_seed, const
 // (sum: the fitness so far.  The reference adds goal after goal to ONE running sum (problem.cpp:244-257); a tip's goals continue the caller's sum instead of
 // forming one of their own, so that (s + a) + b is what is computed, not s + (a + b) -- the same for every evaluation path of the device, and the reference's
 // bits wherever the goals are listed in the order the walk completes their tips, gene-only goals behind them)
-template <class XA>
-BIOIK_DEV double tip_goals(ProbPtr pb, int t, const F7& f, const XA& x, const QueryCtx& qc, double sum) {
+template <class XA, class PB>
+BIOIK_DEV double tip_goals(PB pb, int t, const F7& f, const XA& x, const QueryCtx& qc, double sum) {
 #if !defined(BIOIK_NO_POSE_ONLY)
     // the usual tip: one PoseGoal (DevTip::pose_off): the sum below without the goal table's dependent scalar loads
     if (pb->tips[t].pose_off >= 0) return sum + pose_goal_cost(qc.par + pb->tips[t].pose_off, f) * pb->tips[t].pose_weight_sq;
@@ -536,8 +576,8 @@ BIOIK_DEV double tip_goals(ProbPtr pb, int t, const F7& f, const XA& x, const Qu
     return sum;
 }
 // primary goals that read no link
-template <class XA>
-BIOIK_DEV double nonlink_primary(ProbPtr pb, const XA& x, const QueryCtx& qc, double sum) {
+template <class XA, class PB>
+BIOIK_DEV double nonlink_primary(PB pb, const XA& x, const QueryCtx& qc, double sum) {
     const F7 zero = F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
     for (int g = pb->n_link_primary; g < pb->n_primary; g++)
         sum += goal_eval<false, XA>(pb, pb->primary[g].type, pb->primary[g].var_op, pb->primary[g].var_seed, qc.par + pb->primary[g].param_off, zero, x, qc) *
@@ -575,8 +615,8 @@ BIOIK_DEV double balance_cost(PB pb, const V3& acc, const QueryCtx& qc) {
     return sum;
 }
 // secondary goals see genes only; link goals marked secondary read null frames (ik_base.h:163)
-template <bool JS_INLINE = false, class XA = XV>
-BIOIK_DEV double secondary_fitness(ProbPtr pb, const XA& x, const QueryCtx& qc) {
+template <bool JS_INLINE = false, class XA = XV, class PB = ProbPtr>
+BIOIK_DEV double secondary_fitness(PB pb, const XA& x, const QueryCtx& qc) {
     double sum = 0.0;
     const F7 zero = F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
     for (int g = 0; g < pb->n_secondary; g++)
@@ -595,8 +635,8 @@ BIOIK_DEV bool avoid_limits_surely_free(double parent_gene, double pg_even, doub
     const double reach = 0.0173 * span + 2.0 * fmax(fabs(pg_even), fabs(pg_odd));
     return fabs(parent_gene - mid) + reach < 0.25 * span * (1.0 - 1e-9);
 }
-template <int N, class XA>
-BIOIK_DEV void secondary_fitness_n(ProbPtr pb, const XA (&x)[N], const QueryCtx& qc, double (&out)[N], uint64_t inside_mask = 0ull) {
+template <int N, class XA, class PB>
+BIOIK_DEV void secondary_fitness_n(PB pb, const XA (&x)[N], const QueryCtx& qc, double (&out)[N], uint64_t inside_mask = 0ull) {
     const F7 zero = F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
 #pragma unroll
     for (int j = 0; j < N; j++) out[j] = 0.0;
@@ -1540,7 +1580,8 @@ BIOIK_CALL int check_frame_goal(int type, const lds_f64* P, F7 fb, double dpos, 
     return ok ? 1 : 0;
 }
 
-BIOIK_DEV bool check_goal(ProbPtr pb, int g, const F7& fb, const XV& x, const QueryCtx& qc, double dpos, double drot, double dtwist) {
+template <class PB>
+BIOIK_DEV bool check_goal(PB pb, int g, const F7& fb, const XV& x, const QueryCtx& qc, double dpos, double drot, double dtwist) {
     const int type = pb->primary[g].type;
     const double* P = qc.par + pb->primary[g].param_off;
     bool ok = true;

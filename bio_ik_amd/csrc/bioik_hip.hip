@@ -24,7 +24,7 @@
 
 static_assert((int)G_POSITION == (int)BIOIK_GOAL_POSITION && (int)G_POSE == (int)BIOIK_GOAL_POSE && (int)G_CONE == (int)BIOIK_GOAL_CONE &&
                   (int)G_JOINT_VARIABLE == (int)BIOIK_GOAL_JOINT_VARIABLE && (int)G_MINIMAL_DISPLACEMENT == (int)BIOIK_GOAL_MINIMAL_DISPLACEMENT &&
-                  (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS,
+                  (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS && (int)G_TOUCH == (int)BIOIK_GOAL_TOUCH,
               "goal opcodes out of sync with include/bioik_hip.h");
 static_assert((int)FK_LINEAR == (int)BIOIK_FK_LINEAR && (int)FK_EXACT == (int)BIOIK_FK_EXACT, "fk modes out of sync");
 
@@ -319,6 +319,7 @@ struct bioik_problem {
     bioik_model* model;
     bioik::HostProblem host;
     DevProblem* d_pb = nullptr;
+    double* d_touch = nullptr;  // DevProblem::touch_points: the collision points the problem's TouchGoals read (null without one)
     // Host-pointer solves (bioik_solve_batch, bioik_solve_batch_submit / _wait) go through one of kIoSlots slots, each with a grow-only
     // device arena, its page-locked host mirror (one DMA in, one DMA out per solve) and its own stream: up to kIoSlots batches of one
     // handle are in flight together, the tail of one solve behind the bulk of the next.  Streams are created at a
@@ -798,7 +799,7 @@ struct SolveLauncher {
         quat = dp.n_quat > 0;  // winners re-derived: their momentum is taken before the quaternion genes are renormalised
         manual = sw.manual();
         // children computed where they are read (no genotype columns in LDS): the lean flavour can, whenever it is chosen below
-        can_columnless = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && !sw.general_set;
+        can_columnless = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr && !sw.general_set;
         sp.columnless = 0;
         // k_solve_lean_cl4's mapping first -- 128 lanes, a wavefront per species, children computed where they are read and walked in pairs, the kernel compiled
         // for exactly that under the budget of four wavefronts per SIMD (no register spills since round 4): for problems without a secondary goal whose
@@ -896,7 +897,7 @@ struct SolveLauncher {
         // step is a third shorter (SolveArgs::resident).  An isolated 4096-query call: 9.2 -> 8.5 ms (profiles/r04_drain_handover.log).  Streams of solves keep the
         // chip full, never see the hand-over and pay for its bookkeeping: the throughput schedule does without (BIOIK_SOLVE_DRAIN_THROUGHPUT=1: with).
         dense_ok = !manual && can_columnless && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 && dp.n_secondary == 0 && !sw.three_waves && dp.multi_op < 0 &&
-                              dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.serial_chain != 0;
+                              dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr && dp.serial_chain != 0;
         // (BIOIK_SOLVE_CAPTURE_ONE_LAUNCH=1: round 4's rule -- a call on a stream that is being captured gets a one-launch mapping.  The replay defect it worked around
         // was the runtime's memset NODE in front of the kernels, not the hand-over; the library fills its words with a kernel of its own now
         // and captured calls take the same mapping as eager ones)
@@ -911,7 +912,7 @@ struct SolveLauncher {
         groups = sp.species_parallel ? 2 : 1;
         lds = lds_bytes(p, nth, sp.lambda, sp.columnless ? 0 : sp.child_cols, groups, sp.child_pairs ? 2 : 1, exact, sp.columnless && exact);
         if (lds > kLds) throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs more LDS per workgroup than a CU has");
-        lean = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0;
+        lean = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr;
         if (sw.general_set && sw.general) lean = false;
         halves_ok = lean && can_columnless && exact && sp.lambda >= 128 && dp.D < 32;  // the first launch's mapping exists for this problem
     }
@@ -1259,6 +1260,11 @@ int bioik_problem_create(bioik_model* model, const bioik_problem_desc* desc, bio
     be_zero_async(p->d_resident, 16 * 128, 0);
     p->h_error = (unsigned int*)be_alloc_pinned(64);
     std::memset(p->h_error, 0, 64);
+    if (!p->host.touch_points.empty()) {
+        p->d_touch = (double*)be_alloc(p->host.touch_points.size() * sizeof(double));
+        be_h2d(p->d_touch, p->host.touch_points.data(), p->host.touch_points.size() * sizeof(double), 0);
+        p->host.dev.touch_points = p->d_touch;
+    }
     be_h2d(p->d_pb, &p->host.dev, sizeof(DevProblem), 0);
     be_sync(0);
     *out = p.release();
@@ -1278,6 +1284,7 @@ void bioik_problem_destroy(bioik_problem* p) {
         }
     }
     be_free(p->d_pb);
+    if (p->d_touch) be_free(p->d_touch);
     be_free(p->d_clocks);
     be_free(p->d_resident);
     be_free_pinned(p->h_error);

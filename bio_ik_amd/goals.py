@@ -3,7 +3,7 @@
 Same class names, constructor arguments, setters and normalisation behaviour as the reference; instead of a
 virtual `evaluate` every built-in goal serialises itself into (opcode, link/variable, weight, secondary) for the
 problem template and a flat parameter vector per query (`params()`), which is what the device evaluates.
-Goals that need host callbacks or FCL (JointFunctionGoal, LinkFunctionGoal, TouchGoal) have no
+Goals that need host callbacks (JointFunctionGoal, LinkFunctionGoal) have no
 device opcode; constructing a problem with them raises NotImplementedError.
 """
 import math
@@ -234,6 +234,37 @@ class PlaneGoal(LinkGoalBase):
 
     def params(self):
         return np.concatenate([self.position, self.normal])
+
+
+class TouchGoal(LinkGoalBase):
+    """goal_types.h:330-377, goal_types.cpp:152-228: the collision shapes of the link touch the plane through `position` with `normal`.  The shapes are the
+    link's collision points of the robot model (RobotModel.add_collision_box / _sphere / _points, or the URDF reader): no FCL."""
+    opcode = abi.GOAL_TOUCH
+
+    def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0):
+        super().__init__(link_name, weight)
+        self.position = _vec3(position)
+        self.normal = _normalized(normal)  # goal_types.h:371
+
+    def getPosition(self):
+        return self.position
+
+    def getNormal(self):
+        return self.normal
+
+    def params(self):
+        return np.concatenate([self.position, self.normal])
+
+    def evaluate(self, frame, points):
+        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link).  The device's formula in numpy."""
+        f = np.asarray(frame, dtype=np.float64)
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        x, y, z, w = f[3:7]
+        u = np.array([-x, -y, -z])  # tf2's inverse(): the conjugate
+        t = 2.0 * np.cross(u, self.normal)
+        n_l = self.normal + w * t + np.cross(u, t)
+        d = float(np.min(pts[:, :3] @ n_l - pts[:, 3])) - float(np.dot(self.normal, self.position - f[:3]))
+        return d * d
 
 
 class _JointSetGoal(Goal):

@@ -54,6 +54,10 @@ class RobotModel:
         self.var_max = []
         self.var_bounded = []
         self.var_max_velocity = []
+        self.link_points = {}   # link index -> list of (x, y, z, r): collision points in the link frame (TouchGoal); r < 0 marks a shape without a point form
+        self.link_meshes = {}   # link index -> list of (filename, scale xyz, origin px py pz qx qy qz qw): <mesh> collisions a URDF names; the caller supplies their vertices
+        self.link_unsupported = {}  # link index -> kinds of shapes without a point form (add_collision_unsupported)
+        self.meshes_resolved = set()  # links of link_meshes whose vertices the caller has supplied (add_collision_points)
         self.groups = {}
         self._keep = None
 
@@ -126,6 +130,47 @@ class RobotModel:
                 self.var_max_velocity.append(float(velocity))
         self._keep = None
         return idx
+
+    # ---- collision shapes as points (TouchGoal, goal_types.cpp:46-228: what the reference takes from LinkModel::getShapes / getCollisionOriginTransforms) ----
+    def add_collision_points(self, link, points, radii=None, origin=None, _shape=False):
+        """Points of `link` (name or index) with a radius each (default 0): the vertices of a mesh -- best its convex hull, only hull vertices can touch a
+        plane first -- or spheres.  origin: the shape's collision origin px py pz qx qy qz qw (quat_from_rpy turns a URDF rpy into the quaternion); the points are
+        moved by it into the link frame, and an identity origin (or None) passes them through untouched."""
+        i = link if isinstance(link, int) else self.link_index(link)
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        rad = np.zeros(len(pts)) if radii is None else np.broadcast_to(np.asarray(radii, dtype=np.float64), (len(pts),))
+        if np.any(rad < 0) or not (np.all(np.isfinite(pts)) and np.all(np.isfinite(rad))):
+            raise ValueError("collision points must be finite and their radii >= 0")
+        if origin is not None and tuple(float(v) for v in origin) != (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0):
+            o = np.asarray(origin, dtype=np.float64).reshape(7)
+            pts = np.array([quat_rotate(o[3:], v) + o[:3] for v in pts]).reshape(-1, 3)
+        self.link_points.setdefault(i, []).extend((float(v[0]), float(v[1]), float(v[2]), float(r)) for v, r in zip(pts, rad))
+        if not _shape:
+            self.meshes_resolved.add(i)  # vertices supplied by the caller: the link's <mesh> collisions (link_meshes) count as given
+        self._keep = None
+
+    def add_collision_box(self, link, size, origin=None):
+        """URDF <box size="x y z">: its 8 corners (exact: a box's support function is attained at a corner)."""
+        hx, hy, hz = (0.5 * float(s) for s in size)
+        corners = [(sx * hx, sy * hy, sz * hz) for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]
+        self.add_collision_points(link, corners, None, origin, _shape=True)
+
+    def add_collision_sphere(self, link, radius, origin=None):
+        """URDF <sphere radius="r">: one point with that radius (exact)."""
+        self.add_collision_points(link, [(0.0, 0.0, 0.0)], [float(radius)], origin, _shape=True)
+
+    def add_collision_unsupported(self, link, kind="cylinder"):
+        """A shape that is no set of points (cylinder, cone): recorded (link_unsupported: its kind), and a TouchGoal on this link is refused
+        (BIOIK_ERR_UNSUPPORTED); never approximated."""
+        i = link if isinstance(link, int) else self.link_index(link)
+        self.link_unsupported.setdefault(i, []).append(str(kind))
+        self.link_points.setdefault(i, []).append((0.0, 0.0, 0.0, -1.0))
+        self._keep = None
+
+    def collision_points(self, link):
+        """[n][4] x y z r of `link` as the device will read them"""
+        i = link if isinstance(link, int) else self.link_index(link)
+        return np.asarray(self.link_points.get(i, []), dtype=np.float64).reshape(-1, 4)
 
     def add_group(self, name, joints=None, chain=None, tips=None):
         """Group from an explicit joint-name list or a (base_link, tip_link) chain, like an SRDF <group>."""
@@ -221,6 +266,12 @@ class RobotModel:
             k["var_max_velocity"] = np.asarray(self.var_max_velocity, dtype=np.float64)
             k["link_mass"] = np.asarray(self.link_mass, dtype=np.float64)
             k["link_center"] = np.asarray(self.link_center, dtype=np.float64).reshape(-1, 3)
+            # a <mesh> collision whose vertices nobody supplied: the link gets the marker row of a shape without a point form, so a TouchGoal on it is
+            # refused instead of being scored on the link's other shapes alone
+            rows = [list(self.link_points.get(i, ())) + ([(0.0, 0.0, 0.0, -1.0)] if (i in self.link_meshes and i not in self.meshes_resolved) else [])
+                    for i in range(self.n_links)]
+            k["link_point_first"] = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+            k["link_points"] = np.asarray([p for r in rows for p in r], dtype=np.float64).reshape(-1, 4)
             self._keep = k
         return self._keep
 
@@ -246,6 +297,9 @@ class RobotModel:
         if np.any(k["link_mass"] > 0.0):
             d.link_mass = abi.dptr(k["link_mass"])
             d.link_center = abi.dptr(k["link_center"])
+        if len(k["link_points"]):
+            d.link_point_first = abi.iptr(k["link_point_first"])
+            d.link_points = abi.dptr(k["link_points"])
         return d
 
 

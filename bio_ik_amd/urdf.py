@@ -11,10 +11,13 @@ src/kinematics_plugin.cpp:167-189) is built here from the robot description itse
     <end_effector parent_link parent_group> supplies the tips of a group without a chain;
     <virtual_joint name type parent_frame child_link> (fixed | floating | planar) puts a new root link `parent_frame` in front of
     the URDF's root, as MoveIt does for a mobile or free-flying base.
-Read as well: <inertial> mass and origin of every link (BalanceGoal, goal_types.cpp:236-247).  Not read: collision / visual geometry, transmissions, <safety_controller>, xacro macros."""
+Read as well: <inertial> mass and origin of every link (BalanceGoal, goal_types.cpp:236-247); <collision> <origin> with <box> / <sphere> as the link's
+collision points (TouchGoal: RobotModel.add_collision_box / _sphere), <mesh filename scale> recorded in RobotModel.link_meshes without loading the file (the
+caller adds its vertices with add_collision_points), <cylinder> recorded as a shape without a point form (a TouchGoal on that link is refused).
+Not read: visual geometry, transmissions, <safety_controller>, xacro macros."""
 import xml.etree.ElementTree as ET
 
-from .robot import RobotModel
+from .robot import RobotModel, quat_from_rpy
 
 
 def _floats(text, n, default):
@@ -112,6 +115,27 @@ def load_urdf(urdf_xml, srdf_xml=None):
         i = m.link_names.index(name)
         m.link_mass[i] = mass
         m.link_center[i] = [float(com[0]), float(com[1]), float(com[2])]
+    for l in root.findall("link"):  # <collision>: LinkModel::getShapes() / getCollisionOriginTransforms() in the order of the file
+        i = m.link_names.index(l.get("name"))
+        for c in l.findall("collision"):
+            o, geo = c.find("origin"), c.find("geometry")
+            if geo is None or len(geo) == 0:
+                continue
+            xyz = _floats(o.get("xyz") if o is not None else None, 3, (0, 0, 0))
+            rpy = _floats(o.get("rpy") if o is not None else None, 3, (0, 0, 0))
+            origin = None if (xyz == (0, 0, 0) and rpy == (0, 0, 0)) else tuple(xyz) + tuple(quat_from_rpy(*rpy))
+            shape = geo[0]
+            if shape.tag == "box":
+                m.add_collision_box(i, _floats(shape.get("size"), 3, (0, 0, 0)), origin)
+            elif shape.tag == "sphere":
+                m.add_collision_sphere(i, float(shape.get("radius")), origin)
+            elif shape.tag == "mesh":
+                m.link_meshes.setdefault(i, []).append((shape.get("filename"), _floats(shape.get("scale"), 3, (1, 1, 1)),
+                                                        origin if origin is not None else (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)))
+            elif shape.tag == "cylinder":
+                m.add_collision_unsupported(i, "cylinder")
+            else:
+                raise ValueError("link %r: unsupported collision geometry <%s>" % (l.get("name"), shape.tag))
     m._keep = None
     if srdf_xml is not None:
         add_srdf_groups(m, srdf_xml)

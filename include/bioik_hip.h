@@ -83,9 +83,21 @@ enum {
     BIOIK_GOAL_BALANCE = 16,             /* goal_types.h:540-566, goal_types.cpp:231-272  params: target[3] axis[3].  Reads the frames of
                                             EVERY link of the model with a positive mass (bioik_model_desc::link_mass), each of which
                                             becomes a tip of the problem, as BalanceGoal::describe does                              */
-    BIOIK_GOAL_TYPE_COUNT = 17
-    /* TouchGoal (FCL), JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
+    BIOIK_GOAL_TOUCH = 17,               /* goal_types.h:330-377, goal_types.cpp:152-228  params: position[3] normal[3].  The collision shapes of the
+                                            link touch the plane through `position` with unit `normal`: with the link's frame (p, q) and its
+                                            points (v_i, r_i) of bioik_model_desc::link_points,
+                                                n_l = rotate(conjugate(q), normal)      d = min_i (n_l . v_i - r_i) - normal . (position - p)
+                                            and the cost is d * d.  No FCL: a box is its 8 corners, a sphere one point with a radius, a mesh its
+                                            vertices (the support function along the normal, what the reference's hill climb returns).  A link
+                                            without points: BIOIK_ERR_INVALID_ARGUMENT; more than BIOIK_MAX_TOUCH_POINTS: BIOIK_ERR_UNSUPPORTED   */
+    BIOIK_GOAL_TYPE_COUNT = 18
+    /* JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
 };
+/* Points one BIOIK_GOAL_TOUCH may read (the table of its link).  The minimum is a loop every evaluation of every individual runs in full: about five
+ * FP64 issue slots per point (three fused multiply-adds, a minimum and its canonicalisation; counted in the compiled loop, not timed), so by that count a few
+ * hundred points cost as much as the whole chain walk of a 7-joint arm (profiles/touch_goal_metadata_and_bench.log has measured solves per second at 8, 64 and 1024 points).
+ * Hand meshes over as their convex hull or decimated: only hull vertices can be the minimum. */
+#define BIOIK_MAX_TOUCH_POINTS 1024
 
 /* number of per-query parameter doubles of a goal opcode, or -1 for an unknown opcode */
 int bioik_goal_param_count(int goal_type);
@@ -163,6 +175,12 @@ typedef struct bioik_model_desc {
     const double* link_mass;             /* [n_links] urdf::Link::inertial->mass, 0 where the link has no <inertial>; NULL: no link
                                             has one (only BIOIK_GOAL_BALANCE reads it, goal_types.cpp:236-247)                  */
     const double* link_center;           /* [n_links*3] urdf::Link::inertial->origin.position (link frame); NULL with link_mass   */
+    /* Collision points of the links (only BIOIK_GOAL_TOUCH reads them), in compressed rows: link l owns the points link_point_first[l] ... link_point_first[l + 1]
+       - 1.  A point is x y z r IN THE LINK FRAME (the shape's collision origin already applied by the caller), r >= 0 the radius of a sphere around it.  A row with
+       r == -1 exactly is no point but a MARKER (any other negative radius is BIOIK_ERR_INVALID_ARGUMENT): the link carries a shape that is no set of points (a cylinder, a cone, a mesh whose vertices are not there) -- the model is accepted, a BIOIK_GOAL_TOUCH that names
+       the link is refused with BIOIK_ERR_UNSUPPORTED (such a shape is never approximated silently).  Both NULL: no link has shapes.  A caller whose struct_size ends in front of these two fields (a build against the header without them) gets none.                    */
+    const int32_t* link_point_first;     /* [n_links + 1] ascending, [0] = 0                                                       */
+    const double* link_points;           /* [link_point_first[n_links] * 4]                                                        */
 } bioik_model_desc;
 
 /* ---- one goal of the problem template (structure shared by every query of a batch; the numeric
@@ -257,7 +275,8 @@ void bioik_model_destroy(bioik_model* m);
 /* replaces Problem::initialize + IKBase::initialize(problem) -> RobotFK::initialize(tips)
  * (problem.cpp:72-228, ik_base.h:154-161, forward_kinematics.h:253-330, 566-599).
  * Size limits of one problem (BIOIK_ERR_UNSUPPORTED beyond them): 64 moving joints on the union of the goal chains (a short
- * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals.
+ * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals,
+ * BIOIK_MAX_TOUCH_POINTS collision points per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS).
  * Tips and joints are further bounded TOGETHER by the 160 KiB of LDS of a CU: the function-level entry points hold 7 x tips x joints doubles
  * of tables plus a genotype column per lane (64 tips on 12 joints: 71 KiB; 24 tips on 63 joints: about 137 KiB; 64 tips on 63 joints: about
  * 290 KiB), the solvers hold more.  A problem beyond that is accepted here and refused with BIOIK_ERR_UNSUPPORTED by every entry point that
