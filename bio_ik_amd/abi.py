@@ -46,7 +46,8 @@ class ModelDesc(C.Structure):
                 ("joint_first_variable", _pi), ("joint_mimic", _pi), ("joint_mimic_factor", _pd),
                 ("joint_mimic_offset", _pd), ("var_min", _pd), ("var_max", _pd), ("var_bounded", _pu8),
                 ("var_max_velocity", _pd), ("link_mass", _pd), ("link_center", _pd),
-                ("link_point_first", _pi), ("link_points", _pd)]  # (the last two: collision points for TouchGoal; a struct_size that ends in front of them is accepted)
+                ("link_point_first", _pi), ("link_points", _pd),  # (collision points for TouchGoal; a struct_size that ends in front of them is accepted)
+                ("link_disk_first", _pi), ("link_disks", _pd)]  # (collision disks for TouchGoal: the ends of cylinders, the bases of cones; likewise)
 
 
 class GoalDesc(C.Structure):

@@ -53,6 +53,7 @@ protected:
     const RobotInfo* robot_info_ = nullptr;
     mutable std::vector<double> temp_vector_;
     std::vector<const std::vector<double>*> goal_link_points_;  // per link of the goal: its collision points x y z r in the link frame (TouchGoal), or null
+    std::vector<const std::vector<double>*> goal_link_disks_;   // per link of the goal: its collision disks cx cy cz r ax ay az 0 in the link frame (TouchGoal), or null
 
 public:
     GoalContext() {}
@@ -60,6 +61,11 @@ public:
     const std::vector<double>& getLinkPoints(size_t i = 0) const {
         static const std::vector<double> none;
         return i < goal_link_points_.size() && goal_link_points_[i] ? *goal_link_points_[i] : none;
+    }
+    // the collision disks of the goal's i-th link (the ends of cylinders, the bases of cones), rows cx cy cz r ax ay az 0 in the link frame
+    const std::vector<double>& getLinkDisks(size_t i = 0) const {
+        static const std::vector<double> none;
+        return i < goal_link_disks_.size() && goal_link_disks_[i] ? *goal_link_disks_[i] : none;
     }
     const Frame& getLinkFrame(size_t i = 0) const { return tip_link_frames_[goal_link_indices_[i]]; }
     double getVariablePosition(size_t i = 0) const {

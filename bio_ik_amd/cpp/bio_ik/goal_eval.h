@@ -21,6 +21,7 @@ public:
         std::function<int(const std::string&)> variable_index;                           // robot variable by name, -1: unknown
         std::function<Frame(const std::string&, const std::vector<double>&)> link_frame;  // global frame of a link at a full variable vector
         std::function<const std::vector<double>*(const std::string&)> link_points;       // collision points x y z r of a link (TouchGoal); may be empty
+        std::function<const std::vector<double>*(const std::string&)> link_disks;        // collision disks cx cy cz r ax ay az 0 of a link (TouchGoal); may be empty
     };
 
 private:
@@ -58,6 +59,7 @@ public:
                 if (t == tip_names_.size()) tip_names_.push_back(name);
                 c.goal_link_indices_.push_back(t);
                 c.goal_link_points_.push_back(model_.link_points ? model_.link_points(name) : nullptr);
+                c.goal_link_disks_.push_back(model_.link_disks ? model_.link_disks(name) : nullptr);
             }
             for (auto& name : c.goal_variable_names_) {
                 const int ivar = model_.variable_index(name);

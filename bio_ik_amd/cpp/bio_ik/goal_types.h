@@ -377,8 +377,9 @@ public:
 };
 
 // TouchGoal (:330-377, goal_types.cpp:45-229): the collision shapes of the link touch the plane through `position` with `normal`.  No FCL: the shapes are the
-// link's collision points x y z r of the robot model (RobotModel::addCollisionBox / Sphere / Points, the URDF reader, or LinkModel::getShapes() in the
-// MoveIt plugin), and the cost is the squared support distance of that set along the normal (include/bioik_hip.h: BIOIK_GOAL_TOUCH)
+// link's collision points x y z r and disks cx cy cz r ax ay az 0 of the robot model (RobotModel::addCollisionBox / Sphere / Points / Cylinder / Cone, the
+// URDF reader, or LinkModel::getShapes() in the MoveIt plugin), and the cost is the squared support distance of their hull along the normal
+// (include/bioik_hip.h: BIOIK_GOAL_TOUCH)
 class TouchGoal : public LinkGoalBase {
     Vector3 position, normal;
 
@@ -388,8 +389,9 @@ public:
         : LinkGoalBase(link_name, weight), position(position_), normal(normal_.normalized()) {}
     const Vector3& getPosition() const { return position; }
     const Vector3& getNormal() const { return normal; }
-    // d = min_i (n_l . v_i - r_i) - normal . (position - p), n_l = the normal turned by the conjugate of the link's quaternion (tf2's inverse(), goal_types.cpp:170)
-    static double distance(const Frame& fb, const Vector3& position, const Vector3& normal, const std::vector<double>& points) {
+    // d = min(min_i (n_l . v_i - r_i), min_j (n_l . c_j - r_j |n_l x a_j|)) - normal . (position - p), n_l = the normal turned by the conjugate of the link's quaternion (tf2's inverse(), goal_types.cpp:170)
+    static double distance(const Frame& fb, const Vector3& position, const Vector3& normal, const std::vector<double>& points,
+                           const std::vector<double>& disks = std::vector<double>()) {
         const Quaternion q = fb.getOrientation();
         // v + 2 (w t + u x t), t = u x v with u = -q.xyz: the quaternion as it is, unit or not (frame.h:108-149)
         const Vector3 u(-q.x(), -q.y(), -q.z());
@@ -400,10 +402,14 @@ public:
             if (points[i + 3] < 0) continue;  // (the marker of a shape that is no point set: the device refuses such a link)
             dmin = std::fmin(dmin, nl.x() * points[i] + nl.y() * points[i + 1] + nl.z() * points[i + 2] - points[i + 3]);
         }
+        for (size_t i = 0; i + 8 <= disks.size(); i += 8) {  // a disk's support: the cross product, which keeps its digits where the normal is parallel to the axis
+            const Vector3 rim = nl.cross(Vector3(disks[i + 4], disks[i + 5], disks[i + 6]));
+            dmin = std::fmin(dmin, nl.x() * disks[i] + nl.y() * disks[i + 1] + nl.z() * disks[i + 2] - disks[i + 3] * std::sqrt(rim.dot(rim)));
+        }
         return dmin - normal.dot(position - fb.getPosition());
     }
     double evaluate(const GoalContext& context) const override {
-        const double d = distance(context.getLinkFrame(), position, normal, context.getLinkPoints());
+        const double d = distance(context.getLinkFrame(), position, normal, context.getLinkPoints(), context.getLinkDisks());
         return d * d;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_TOUCH; }

@@ -102,6 +102,7 @@ public:
             rm.linkTransform(rm.linkIndex(link), std::vector<double>(positions, positions + rm.variable_names.size()), frame7);
         };
         mv.link_points = [&rm](const std::string& link) { return rm.collisionPoints(link); };
+        mv.link_disks = [&rm](const std::string& link) { return rm.collisionDisks(link); };
         joint_names.clear();
         for (int j : jmg.active_joints) {
             joint_names.push_back(rm.joint_names[j]);

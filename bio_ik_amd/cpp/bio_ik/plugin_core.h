@@ -48,6 +48,7 @@ struct ModelView {
     std::vector<uint8_t> var_prismatic;
     std::function<void(const std::string& link, const double* positions, double* frame7)> link_frame;  // global frame of a link at a full variable vector
     std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal on the host); may be empty
+    std::function<const std::vector<double>*(const std::string& link)> link_disks;   // collision disks cx cy cz r ax ay az 0 of a link (likewise)
 };
 
 struct Settings {  // IKParams (src/utils.h:64-85) as far as the device path reads them, + the additive gpu_* keys
@@ -452,6 +453,7 @@ public:
                                     v < mv_.var_prismatic.size() && mv_.var_prismatic[v] != 0);
             hm.variable_index = mv_.variable_index;
             hm.link_points = mv_.link_points;
+            hm.link_disks = mv_.link_disks;
             const ModelView* mv = &mv_;
             hm.link_frame = [mv](const std::string& name, const std::vector<double>& p) {
                 double f[7];

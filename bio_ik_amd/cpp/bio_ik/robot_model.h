@@ -34,8 +34,15 @@ public:
         bool resolved = false;  // set once vertices were added for the link
     };
     std::map<int, std::vector<MeshRef>> link_meshes;
-    mutable std::vector<int32_t> point_first_;  // flattened by desc()
-    mutable std::vector<double> points_flat_;
+    // cylinders and cones: the convex hull of disks and points -- per link rows cx cy cz r ax ay az 0 in the link frame (the ends of cylinders, the bases of cones)
+    std::map<int, std::vector<double>> link_disks;
+    struct SolidRef {  // a <cylinder> collision a URDF names: left as a marker row until resolveCollisionSolids() turns it into its disks
+        std::string kind;
+        double radius, length, origin[7];
+    };
+    std::map<int, std::vector<SolidRef>> link_solids;
+    mutable std::vector<int32_t> point_first_, disk_first_;  // flattened by desc()
+    mutable std::vector<double> points_flat_, disks_flat_;
 
     // points (x y z triples) with radii (empty: all 0), moved by the shape's collision origin (px py pz qx qy qz qw; null or the identity: untouched)
     void addCollisionPoints(const std::string& link, const std::vector<double>& xyz, const std::vector<double>& radii = {}, const double* origin = nullptr) {
@@ -70,7 +77,64 @@ public:
         addCollisionPoints(link, {0.0, 0.0, 0.0}, {radius}, origin);
         if (!keep) unresolveMeshes(link);
     }
-    void addCollisionUnsupported(const std::string& link) {  // a cylinder or a cone: a TouchGoal on this link is refused, never approximated
+    // raw disks: rows cx cy cz r ax ay az 0 (radius >= 0, axis of unit length within 1e-9), centres moved and axes turned by the shape's collision origin
+    void addCollisionDisks(const std::string& link, const std::vector<double>& rows, const double* origin = nullptr) {
+        std::vector<double>& t = link_disks[linkIndex(link)];
+        const bool ident = !origin || (origin[0] == 0 && origin[1] == 0 && origin[2] == 0 && origin[3] == 0 && origin[4] == 0 && origin[5] == 0 && origin[6] == 1);
+        for (size_t i = 0; i + 8 <= rows.size(); i += 8) {
+            double c[3] = {rows[i], rows[i + 1], rows[i + 2]}, a[3] = {rows[i + 4], rows[i + 5], rows[i + 6]};
+            const double len = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            if (!(rows[i + 3] >= 0) || !(std::fabs(len - 1.0) <= 1e-9) || rows[i + 7] != 0) throw std::runtime_error("collision disks: radius >= 0, a unit axis, an eighth number 0");
+            if (!ident) {
+                double r[3];
+                rotate(origin + 3, c, r);
+                for (int k = 0; k < 3; k++) c[k] = r[k] + origin[k];
+                rotate(origin + 3, a, r);
+                for (int k = 0; k < 3; k++) a[k] = r[k];
+            }
+            t.insert(t.end(), {c[0], c[1], c[2], rows[i + 3], a[0], a[1], a[2], 0.0});
+        }
+    }
+    // URDF <cylinder> / shapes::Cylinder: centred on its origin, axis z -- its two end disks (exact: a cylinder is their convex hull)
+    void addCollisionCylinder(const std::string& link, double radius, double length, const double* origin = nullptr) {
+        addCollisionDisks(link, {0.0, 0.0, -0.5 * length, radius, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.5 * length, radius, 0.0, 0.0, 1.0, 0.0}, origin);
+    }
+    // shapes::Cone of MoveIt: the origin halfway up, the tip on +z -- its base disk and its apex as a point with r = 0 (exact)
+    void addCollisionCone(const std::string& link, double radius, double length, const double* origin = nullptr) {
+        addCollisionDisks(link, {0.0, 0.0, -0.5 * length, radius, 0.0, 0.0, 1.0, 0.0}, origin);
+        const bool keep = meshesResolved(link);
+        addCollisionPoints(link, {0.0, 0.0, 0.5 * length}, {}, origin);
+        if (!keep) unresolveMeshes(link);
+    }
+    void addCollisionSolidRef(const std::string& link, const std::string& kind, double radius, double length, const double (&origin)[7]) {
+        SolidRef r;
+        r.kind = kind, r.radius = radius, r.length = length;
+        for (int c = 0; c < 7; c++) r.origin[c] = origin[c];
+        link_solids[linkIndex(link)].push_back(r);
+    }
+    // every solid the URDF reader recorded (of `link`, or of all links) becomes its disks, and exactly the marker row the reader left for it goes
+    void resolveCollisionSolids(const std::string& link = "") {
+        for (auto& ls : link_solids) {
+            if (!link.empty() && ls.first != linkIndex(link)) continue;
+            const std::string& name = link_names[ls.first];
+            for (const SolidRef& r : ls.second) {
+                if (r.kind == "cylinder") addCollisionCylinder(name, r.radius, r.length, r.origin);
+                else addCollisionCone(name, r.radius, r.length, r.origin);
+                std::vector<double>& t = link_points[ls.first];
+                for (size_t i = 0; i + 4 <= t.size(); i += 4)
+                    if (t[i + 3] < 0) {
+                        t.erase(t.begin() + i, t.begin() + i + 4);
+                        break;
+                    }
+            }
+            ls.second.clear();
+        }
+    }
+    const std::vector<double>* collisionDisks(const std::string& link) const {
+        auto it = link_disks.find(linkIndex(link));
+        return it == link_disks.end() ? nullptr : &it->second;
+    }
+    void addCollisionUnsupported(const std::string& link) {  // a shape nobody converted (a cylinder or a cone left as it was): a TouchGoal on this link is refused, never approximated
         link_points[linkIndex(link)].insert(link_points[linkIndex(link)].end(), {0.0, 0.0, 0.0, -1.0});
     }
     void addCollisionMeshRef(const std::string& link, const std::string& filename, const double (&scale)[3], const double (&origin)[7]) {
@@ -235,6 +299,13 @@ public:
             point_first_.push_back((int32_t)(points_flat_.size() / 4));
         }
         if (!points_flat_.empty()) d.link_point_first = point_first_.data(), d.link_points = points_flat_.data();
+        disk_first_.assign(1, 0), disks_flat_.clear();
+        for (size_t l = 0; l < link_names.size(); l++) {
+            auto it = link_disks.find((int)l);
+            if (it != link_disks.end()) disks_flat_.insert(disks_flat_.end(), it->second.begin(), it->second.end());
+            disk_first_.push_back((int32_t)(disks_flat_.size() / 8));
+        }
+        if (!disks_flat_.empty()) d.link_disk_first = disk_first_.data(), d.link_disks = disks_flat_.data();
         return d;
     }
     // frame algebra for the plugin boundary (goal poses into the model frame, kinematics_plugin.cpp:487-502)

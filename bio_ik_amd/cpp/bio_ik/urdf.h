@@ -13,7 +13,8 @@
 //     parent_link parent_group> names the tips of a group without a chain; <virtual_joint type = fixed | floating | planar> puts
 //     `parent_frame` in front of the root (the mobile or free-flying base of MoveIt).
 // <collision> <origin> with <box> / <sphere>: the link's collision points (TouchGoal); <mesh filename scale>: recorded, not loaded (the caller supplies the
-// vertices; until then a TouchGoal on the link is refused); <cylinder>: recorded as a shape without a point form.  Not read: visual geometry, transmissions, xacro.
+// vertices; until then a TouchGoal on the link is refused); <cylinder radius length>: recorded (RobotModel::link_solids) and left as a shape without a point form until RobotModel::resolveCollisionSolids() turns it into
+// its two end disks.  Not read: visual geometry, transmissions, xacro.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -364,8 +365,10 @@ inline std::shared_ptr<RobotModel> loadURDF(const std::string& urdf_xml, const s
                 const double scale[3] = {sc[0], sc[1], sc[2]};
                 if (ident) origin[3] = origin[4] = origin[5] = 0, origin[6] = 1;
                 m->addCollisionMeshRef(name, me->get("filename"), scale, origin);
-            } else if (geo->child("cylinder")) {
+            } else if (const XmlNode* cy = geo->child("cylinder")) {  // a marker until the caller asks for its disks (RobotModel::resolveCollisionSolids)
                 m->addCollisionUnsupported(name);
+                if (ident) origin[3] = origin[4] = origin[5] = 0, origin[6] = 1;
+                m->addCollisionSolidRef(name, "cylinder", number(cy, "radius", 0.0), number(cy, "length", 0.0), origin);
             }
         }
     if (!srdf_xml.empty()) addSRDFGroups(*m, srdf_xml);

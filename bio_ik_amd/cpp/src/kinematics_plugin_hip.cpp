@@ -69,18 +69,23 @@ struct FlatModel {
     std::vector<double> link_origin, joint_axis, joint_mimic_factor, joint_mimic_offset, var_min, var_max, var_max_velocity, link_mass, link_center;
     std::vector<uint8_t> var_bounded;
     // TouchGoal: the links' collision shapes as points x y z r in the link frame (bioik_model_desc::link_point_first / link_points), from what the
-    // reference's TouchGoal::describe reads (goal_types.cpp:56-69): a mesh's vertices, a box's corners, a sphere's centre with its radius; a shape that is
-    // no point set (cylinder, cone) leaves the marker row that makes a TouchGoal on the link a refusal
-    std::vector<int32_t> link_point_first{0};
-    std::vector<double> link_points;
-    std::vector<std::vector<double>> points_of_link;  // the same rows per link, for goals evaluated on the host
+    // reference's TouchGoal::describe reads (goal_types.cpp:56-69): a mesh's vertices, a box's corners, a sphere's centre with its radius; a cylinder's two
+    // end disks and a cone's base disk (rows cx cy cz r ax ay az 0: link_disk_first / link_disks) with its apex as a point; any other shape leaves the marker
+    // row that makes a TouchGoal on the link a refusal
+    std::vector<int32_t> link_point_first{0}, link_disk_first{0};
+    std::vector<double> link_points, link_disks;
+    std::vector<std::vector<double>> points_of_link, disks_of_link;  // the same rows per link, for goals evaluated on the host
     void addShapes(const moveit::core::LinkModel* l) {
-        std::vector<double> rows;
+        std::vector<double> rows, drows;
         for (size_t s = 0; s < l->getShapes().size(); s++) {
             const Eigen::Isometry3d& o = l->getCollisionOriginTransforms()[s];
             auto put = [&](double x, double y, double z, double r) {
                 const Eigen::Vector3d v = o.linear() * Eigen::Vector3d(x, y, z) + o.translation();
                 rows.insert(rows.end(), {v.x(), v.y(), v.z(), r});
+            };
+            auto disk = [&](double z, double r) {  // a disk about the shape's z axis
+                const Eigen::Vector3d c = o.linear() * Eigen::Vector3d(0.0, 0.0, z) + o.translation(), a = o.linear() * Eigen::Vector3d(0.0, 0.0, 1.0);
+                drows.insert(drows.end(), {c.x(), c.y(), c.z(), r, a.x(), a.y(), a.z(), 0.0});
             };
             const shapes::Shape* sh = l->getShapes()[s].get();
             if (auto* m = dynamic_cast<const shapes::Mesh*>(sh)) {
@@ -91,6 +96,10 @@ struct FlatModel {
                         for (int sz = -1; sz <= 1; sz += 2) put(sx * 0.5 * b->size[0], sy * 0.5 * b->size[1], sz * 0.5 * b->size[2], 0.0);
             } else if (auto* sp = dynamic_cast<const shapes::Sphere*>(sh)) {
                 put(0.0, 0.0, 0.0, sp->radius);
+            } else if (auto* cy = dynamic_cast<const shapes::Cylinder*>(sh)) {
+                disk(-0.5 * cy->length, cy->radius), disk(0.5 * cy->length, cy->radius);
+            } else if (auto* co = dynamic_cast<const shapes::Cone*>(sh)) {  // the origin halfway up, the tip on +z
+                disk(-0.5 * co->length, co->radius), put(0.0, 0.0, 0.5 * co->length, 0.0);
             } else if (sh) {
                 rows.insert(rows.end(), {0.0, 0.0, 0.0, -1.0});
             }
@@ -98,6 +107,9 @@ struct FlatModel {
         link_points.insert(link_points.end(), rows.begin(), rows.end());
         link_point_first.push_back((int32_t)(link_points.size() / 4));
         points_of_link.push_back(rows);
+        link_disks.insert(link_disks.end(), drows.begin(), drows.end());
+        link_disk_first.push_back((int32_t)(link_disks.size() / 8));
+        disks_of_link.push_back(drows);
     }
     explicit FlatModel(const moveit::core::RobotModel& rm) {
         const auto& links = rm.getLinkModels();
@@ -161,6 +173,7 @@ struct FlatModel {
         d.var_min = var_min.data(), d.var_max = var_max.data(), d.var_bounded = var_bounded.data(), d.var_max_velocity = var_max_velocity.data();
         d.link_mass = link_mass.data(), d.link_center = link_center.data();
         if (!link_points.empty()) d.link_point_first = link_point_first.data(), d.link_points = link_points.data();
+        if (!link_disks.empty()) d.link_disk_first = link_disk_first.data(), d.link_disks = link_disks.data();
         return d;
     }
 };
@@ -291,6 +304,10 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
         mv.link_points = [rm, fm](const std::string& link) -> const std::vector<double>* {  // TouchGoal on the host (the hybrid path)
             auto* l = rm->getLinkModel(link);
             return l ? &fm->points_of_link[(size_t)l->getLinkIndex()] : nullptr;
+        };
+        mv.link_disks = [rm, fm](const std::string& link) -> const std::vector<double>* {
+            auto* l = rm->getLinkModel(link);
+            return l ? &fm->disks_of_link[(size_t)l->getLinkIndex()] : nullptr;
         };
         mv.has_mimic = !rm->getMimicJointModels().empty();
         for (auto& joint_name : joint_names) {  // seed / solution vectors: the variables of the group's joints in this order (:473-484, :619-629)

@@ -29,6 +29,10 @@ struct Cylinder : Shape {
     double length, radius;
     Cylinder(double r = 0, double l = 0) : length(l), radius(r) { type = CYLINDER; }
 };
+struct Cone : Shape {  // the origin halfway up, the tip on +z
+    double length, radius;
+    Cone(double r = 0, double l = 0) : length(l), radius(r) { type = CONE; }
+};
 struct Mesh : Shape {
     unsigned int vertex_count = 0;
     double* vertices = nullptr;  // x y z per vertex

@@ -79,7 +79,9 @@ static int joint_var_count(int type) {
 
 HostModel::HostModel(const bioik_model_desc& d) {
     // (the descriptor grew by link_point_first / link_points without a new ABI version: a caller built against the header without them passes the shorter size)
-    const bool has_points = d.struct_size == sizeof(bioik_model_desc);
+    // and then by link_disk_first / link_disks in the same way: the three sizes are accepted, one between two of them is not
+    const bool has_disks = d.struct_size == sizeof(bioik_model_desc);
+    const bool has_points = has_disks || d.struct_size == offsetof(bioik_model_desc, link_disk_first);
     if (!has_points && d.struct_size != offsetof(bioik_model_desc, link_point_first)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: struct_size mismatch");
     if (d.n_links == 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "model has no links");
     if (!d.link_parent || !d.link_origin || !d.joint_type || !d.joint_axis || !d.joint_first_variable)
@@ -123,6 +125,23 @@ HostModel::HostModel(const bioik_model_desc& d) {
                 throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: a collision point is not finite");
             if (!(std::isfinite(points[i + 3]) && (points[i + 3] >= 0.0 || points[i + 3] == -1.0)))
                 throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the radius of a collision point must be finite and >= 0 (or exactly -1, the marker row)");
+        }
+    }
+    disk_first.assign(d.n_links + 1, 0);
+    if (has_disks && (d.link_disk_first || d.link_disks)) {
+        if (!d.link_disk_first || !d.link_disks) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_disk_first and link_disks go together");
+        if (d.link_disk_first[0] != 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_disk_first[0] must be 0");
+        for (uint32_t i = 0; i < d.n_links; i++)
+            if (d.link_disk_first[i + 1] < d.link_disk_first[i]) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_disk_first must be ascending");
+        disk_first.assign(d.link_disk_first, d.link_disk_first + d.n_links + 1);
+        disks.assign(d.link_disks, d.link_disks + (size_t)disk_first[d.n_links] * 8);
+        for (size_t i = 0; i < disks.size(); i += 8) {
+            for (int c = 0; c < 8; c++)
+                if (!std::isfinite(disks[i + c])) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: a collision disk is not finite");
+            if (!(disks[i + 3] >= 0.0)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the radius of a collision disk must be >= 0");
+            const double len = std::sqrt(disks[i + 4] * disks[i + 4] + disks[i + 5] * disks[i + 5] + disks[i + 6] * disks[i + 6]);
+            if (!(std::fabs(len - 1.0) <= 1e-9)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the axis of a collision disk must be of unit length (within 1e-9)");
+            if (disks[i + 7] != 0.0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the eighth number of a collision disk must be 0");
         }
     }
     // A joint that mimics a joint that itself mimics another: resolved to the joint at the end of the chain with the composed factor and offset, as MoveIt's
@@ -204,7 +223,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         long var;
         double weight;
         int secondary, param_off;
-        int point_first, point_count;  // TouchGoal: its link's points in touch_points
+        int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them
     };
     std::vector<G> goals;
     double balance_total = 0.0;
@@ -213,7 +232,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         const bioik_goal_desc& g = d.goals[gi];
         int np = goal_param_count(g.type);
         if (np < 0) throw Error(BIOIK_ERR_UNSUPPORTED, "goal type has no device implementation");
-        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0};
+        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0, 0};
         if (g.link >= 0) {
             if (g.link >= nl) throw Error(BIOIK_ERR_NOT_FOUND, "link not found");
             info.tip = add_tip_link(g.link);
@@ -228,14 +247,17 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             for (int i = 0; i < count; i++)
                 if (m->points[(size_t)(first + i) * 4 + 3] < 0.0)
                     throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: a row of the link in bioik_model_desc::link_points has the radius -1, the marker of a shape that is no "
-                                                       "set of points (a cylinder, a cone, a mesh without its vertices): no device implementation, not approximated");
-            if (count <= 0)
-                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "TouchGoal: the link has no collision points (bioik_model_desc::link_points); the reference's cost would be DBL_MAX squared");
-            if (count > BIOIK_MAX_TOUCH_POINTS)
+                                                       "set of points or disks (a mesh without its vertices, a shape the caller did not convert -- a cylinder or a cone left as it was): no device implementation, not approximated");
+            const int dfirst = m->disk_first[g.link], dcount = m->disk_first[g.link + 1] - dfirst;
+            if (count <= 0 && dcount <= 0)
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "TouchGoal: the link has no collision points (bioik_model_desc::link_points) and no disks (link_disks); the reference's cost would be DBL_MAX squared");
+            if ((long)count + (long)dcount > BIOIK_MAX_TOUCH_POINTS)
                 throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) +
-                                                       ") collision points: pass the mesh as its convex hull or decimated");
-            info.point_first = (int)(touch_points.size() / 4), info.point_count = count;
+                                                       ") collision points and disks together: pass the mesh as its convex hull or decimated");
+            // (a disk is two rows of four doubles: the next goal's first row stays a whole number)
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = count, info.disk_count = dcount;
             touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
+            touch_points.insert(touch_points.end(), m->disks.begin() + (size_t)dfirst * 8, m->disks.begin() + (size_t)(dfirst + dcount) * 8);
         }
         if (g.type == BIOIK_GOAL_BALANCE) {  // BalanceGoal::describe (goal_types.cpp:231-255): every link with mass becomes a tip, in link order
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, "BalanceGoal cannot be a secondary goal (the reference's has no such constructor)");
@@ -546,7 +568,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             if (g.var >= 0) o.var_op = dev.op_of_gene[g.var];
             else o.var_seed = (int)(-1 - g.var);
         }
-        if (g.type == BIOIK_GOAL_TOUCH) o.var_op = g.point_first, o.var_seed = g.point_count;
+        if (g.type == BIOIK_GOAL_TOUCH) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
         o.param_off = g.param_off;
         return o;
     };

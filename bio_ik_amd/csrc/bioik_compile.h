@@ -37,6 +37,8 @@ struct HostModel {
     std::vector<Var> vars;
     std::vector<int> point_first;  // [links + 1] rows of `points` (bioik_model_desc::link_point_first); all zero: no link has shapes
     std::vector<double> points;    // x y z r per collision point, link frame (TouchGoal)
+    std::vector<int> disk_first;   // [links + 1] rows of `disks` (bioik_model_desc::link_disk_first); all zero: no link has disks
+    std::vector<double> disks;     // cx cy cz r ax ay az 0 per disk, link frame (TouchGoal: the ends of a cylinder, the base of a cone)
     explicit HostModel(const bioik_model_desc& d);
 };
 
@@ -47,7 +49,7 @@ struct HostProblem {
     std::vector<int> active_variables;  // robot variable per gene
     std::vector<int> tip_links;         // link per public tip
     int param_count = 0;
-    std::vector<double> touch_points;   // the points of the links the TouchGoals name, goal after goal (DevGoal::var_op / var_seed index it): uploaded once by bioik_problem_create
+    std::vector<double> touch_points;   // the points of the links the TouchGoals name and behind each goal's points its disks, goal after goal (DevGoal::var_op / var_seed / pad index it): uploaded once by bioik_problem_create
     DevProblem dev;
     HostProblem(const HostModel* m, const bioik_problem_desc& d);
 };

@@ -247,22 +247,33 @@ struct XV {
 // shapes are points with a radius in the link frame (include/bioik_hip.h: BIOIK_GOAL_TOUCH), so the distance is the support function of a point set along the
 // normal turned into the link frame -- the brute-force minimum the reference keeps as a comment (goal_types.cpp:172-182) and its hill climb over the hull's
 // edges returns:   d = min_i (n_l . v_i - r_i) - normal . (position - p).
-// first / count: the goal's `count` >= 1 points x y z r in DevProblem::touch_points (global memory), the same for every lane -- the problem pointer and the
+// Cylinders and cones join the same minimum in closed form: both are the convex hull of DISKS and points (a cylinder: two coaxial disks; a cone: a disk and
+// its apex), the support function of a hull is the minimum of its parts', and a disk (centre c, unit axis a, radius r) has   n_l . c - r |n_l x a|.   The
+// cross product, not sqrt(n.n - (n.a)^2): that form loses half the digits where the normal is parallel to the axis, the pose "cylinder standing on the plane".
+// first / count / disks: the goal's `count` >= 0 points x y z r and, directly behind them, its `disks` >= 0 rows cx cy cz r ax ay az 0 in
+// DevProblem::touch_points (global memory; count + disks >= 1), the same for every lane -- the problem pointer and the
 // table address are made wavefront-uniform here (arguments of a real call arrive in vector registers), so the table is read with scalar loads
 // (s_load_dwordx16 per trip) and its numbers are SGPR operands of the FMAs: no vector memory, no LDS, no divergence.
 // Two points per trip into two independent minima, so the loop is not one dependency chain -- and no more than two: eight doubles of table per trip keep
-// the function inside the scalar registers a callee may use without saving any; a point left over joins the first.  min is exact: any order gives the
+// the function inside the scalar registers a callee may use without saving any; a point left over joins the first.  The loop runs zero trips for a link with
+// disks only (both minima stay +inf, which min passes over).  min is exact: any order gives the
 // same number.  What the compiler makes of a point (gfx950, ROCm 7.2): three v_fma_f64, one v_min_f64, one v_max_f64 that canonicalises the loop-carried
 // minimum, and two v_mov_b32 that bring -r into a vector register (a VOP3 instruction of gfx9 reads one scalar operand): about five FP64 issue slots and two
 // moves.  A trip waits for its own scalar load (no load of the next trip in flight): with few wavefronts resident that latency shows.
+// What the compiler makes of a disk: three scalar loads of together seven doubles (the eighth, the zero, is never read), 29 FP64 instructions -- six for the
+// cross product, three for its squared norm, fourteen for the correctly rounded square root (v_rsq_f64, its refinement, the scaling around it), three for
+// n . c, then v_fma_f64, v_min_f64 and the canonicalising v_max_f64 -- and seven 32-bit moves and selects: about six points' worth.
+// One disk per trip into ONE minimum (the first): a disk is eight doubles, the width of a trip of the point loop, so a second disk per trip would double the
+// scalar registers the callee holds; and a second minimum would buy nothing, since what is long in a disk -- cross product, squared norm, the square root's
+// refinement -- does not depend on the trip before: only the closing v_min_f64 is carried around the loop.
 // One out-of-line copy, reached only from the general kernel flavour: the lean kernels are compiled without it.
 typedef decltype(&((ProbPtr)0)->pose_weight_sq) UniformF64;  // read-only doubles in the address space of the problem block
-BIOIK_CALL double goal_eval_touch(ProbPtr pb_, int first, int count, const lds_f64* P, F7 fb) {
+BIOIK_CALL double goal_eval_touch(ProbPtr pb_, int first, int count, int disks, const lds_f64* P, F7 fb) {
     const unsigned long long pba = (unsigned long long)pb_;
     const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
     const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * p_uniform(first));
     const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
-    const int n = p_uniform(count);
+    const int n = p_uniform(count), nd = p_uniform(disks);
     const V3 normal = v3(P[3], P[4], P[5]);
     const V3 nl = qrot(qinv(fb.q), normal);  // tf2's inverse(): the conjugate, no normalisation (goal_types.cpp:170)
     double m0 = P_INF, m1 = P_INF;
@@ -275,6 +286,13 @@ BIOIK_CALL double goal_eval_touch(ProbPtr pb_, int first, int count, const lds_f
     if (i < n) {
         const UniformF64 a = v + 4 * i;
         m0 = fmin(m0, BK_FMA(nl.x, a[0], BK_FMA(nl.y, a[1], BK_FMA(nl.z, a[2], -a[3]))));
+    }
+    const UniformF64 vd = v + 4 * n;
+    for (int j = 0; j < nd; j++) {
+        const UniformF64 a = vd + 8 * j;
+        const double cx = BK_FMA(nl.y, a[6], -(nl.z * a[5])), cy = BK_FMA(nl.z, a[4], -(nl.x * a[6])), cz = BK_FMA(nl.x, a[5], -(nl.y * a[4]));  // n_l x a
+        const double rim = sqrt(BK_FMA(cx, cx, BK_FMA(cy, cy, cz * cz)));
+        m0 = fmin(m0, BK_FMA(-a[3], rim, BK_FMA(nl.x, a[0], BK_FMA(nl.y, a[1], nl.z * a[2]))));
     }
     const double d = fmin(m0, m1) - dot3(normal, v3(P[0], P[1], P[2]) - fb.p);
     return d * d;
@@ -525,7 +543,7 @@ BIOIK_DEV double pose_goal_cost(const double* P, const F7& fb) {
 }
 // JS_INLINE: the goals over the joint values are inlined (the one hot site: secondary fitness of every child in the pre-selection)
 template <bool JS_INLINE = false, class XA = XV, class PB = ProbPtr>
-BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const double* P, const F7& fb, const XA& x, const QueryCtx& qc) {
+BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const double* P, const F7& fb, const XA& x, const QueryCtx& qc, int aux = 0) {
     const int n_ops = pb->n_ops;
     switch (type) {
         case G_POSITION:  // goal_types.h:96
@@ -551,9 +569,9 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
             }
         default:  // the remaining link goals
             // TouchGoal: only in the general flavour (the launcher hands a problem with one to k_solve, never to a lean kernel: those stay as they were).  A link
-            // goal has no variable: var_op / var_seed carry its first point and its number of points (DevGoal)
+            // goal has no variable: var_op / var_seed carry its first point and its number of points, aux (DevGoal::pad) its number of disks
             if constexpr (pb_flavour<PB>::general)
-                if (type == G_TOUCH) return goal_eval_touch(pb, var_op, var_seed, (const lds_f64*)P, fb);
+                if (type == G_TOUCH) return goal_eval_touch(pb, var_op, var_seed, aux, (const lds_f64*)P, fb);
             return goal_eval_link_rare(type, (const lds_f64*)P, fb);
     }
     return 0.0;
@@ -571,7 +589,7 @@ BIOIK_DEV double tip_goals(PB pb, int t, const F7& f, const XA& x, const QueryCt
 #endif
     const int g0 = pb->tips[t].goal_first, g1 = g0 + pb->tips[t].goal_count;
     for (int g = g0; g < g1; g++)
-        sum += goal_eval<false, XA>(pb, pb->primary[g].type, pb->primary[g].var_op, pb->primary[g].var_seed, qc.par + pb->primary[g].param_off, f, x, qc) *
+        sum += goal_eval<false, XA>(pb, pb->primary[g].type, pb->primary[g].var_op, pb->primary[g].var_seed, qc.par + pb->primary[g].param_off, f, x, qc, pb->primary[g].pad) *
                pb->primary[g].weight_sq;
     return sum;
 }
@@ -620,7 +638,7 @@ BIOIK_DEV double secondary_fitness(PB pb, const XA& x, const QueryCtx& qc) {
     double sum = 0.0;
     const F7 zero = F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
     for (int g = 0; g < pb->n_secondary; g++)
-        sum += goal_eval<JS_INLINE, XA>(pb, pb->secondary[g].type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, x, qc) *
+        sum += goal_eval<JS_INLINE, XA>(pb, pb->secondary[g].type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, x, qc, pb->secondary[g].pad) *
                pb->secondary[g].weight_sq;
     return sum;
 }
@@ -650,7 +668,7 @@ BIOIK_DEV void secondary_fitness_n(PB pb, const XA (&x)[N], const QueryCtx& qc, 
         } else {
 #pragma unroll
             for (int j = 0; j < N; j++)
-                e[j] = goal_eval<true, XA>(pb, type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, x[j], qc);
+                e[j] = goal_eval<true, XA>(pb, type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, x[j], qc, pb->secondary[g].pad);
         }
 #pragma unroll
         for (int j = 0; j < N; j++) out[j] += e[j] * w;
@@ -1008,7 +1026,7 @@ BIOIK_DEV void eval_exact_primary_n(PB pb, const XA (&x)[N], const QueryCtx& qc,
             const double w = pb->primary[g].weight_sq;
             const double* P = qc.par + po;
 #pragma unroll
-            for (int j = 0; j < N; j++) out[j] += goal_eval<false, XA>(pb, type, var_op, var_seed, P, f[j], x[j], qc) * w;
+            for (int j = 0; j < N; j++) out[j] += goal_eval<false, XA>(pb, type, var_op, var_seed, P, f[j], x[j], qc, pb->primary[g].pad) * w;
         }
     }, prefix);
     if constexpr (!LINKS_ONLY) {
@@ -1589,7 +1607,7 @@ BIOIK_DEV bool check_goal(PB pb, int g, const F7& fb, const XV& x, const QueryCt
         ok = check_frame_goal(type, (const lds_f64*)P, fb, dpos, drot, dtwist) != 0;
     } else {
         double dmax = fmin(BIOIK_DBL_MAX, fmin(p_fresh(dpos), dtwist));  // (p_fresh: computed here, not in front of the step loop and carried through it)
-        double d = goal_eval(pb, type, pb->primary[g].var_op, pb->primary[g].var_seed, P, fb, x, qc) * pb->primary[g].weight_sq;
+        double d = goal_eval(pb, type, pb->primary[g].var_op, pb->primary[g].var_seed, P, fb, x, qc, pb->primary[g].pad) * pb->primary[g].weight_sq;
         ok = ok && (d < dmax * dmax);
     }
     return ok;

@@ -1832,7 +1832,7 @@ BIOIK_DEV void solve_memetic(Frame& F, SpeciesState& S, double*& popS, int rank_
                             }
                         }
                     } else {
-                        e = goal_eval<false, PerturbX>(pb, type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, xown, qc);
+                        e = goal_eval<false, PerturbX>(pb, type, pb->secondary[g].var_op, pb->secondary[g].var_seed, qc.par + pb->secondary[g].param_off, zero, xown, qc, pb->secondary[g].pad);
                     }
                     sum += e * pb->secondary[g].weight_sq;
                 }

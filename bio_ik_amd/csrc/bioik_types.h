@@ -76,10 +76,10 @@ struct DevGoal {
     double weight_sq;   // Problem::GoalInfo::weight_sq (problem.cpp:178)
     int32_t type;       // BIOIK_GOAL_*
     int32_t tip;        // device tip index, -1 when the goal reads no link
-    int32_t var_op;     // op index of the goal's variable (JointVariableGoal), -1 none.  TouchGoal (a link goal: it has no variable): its first point in touch_points
+    int32_t var_op;     // op index of the goal's variable (JointVariableGoal), -1 none.  TouchGoal (a link goal: it has no variable): its first point in touch_points, counted in rows of four doubles
     int32_t var_seed;   // robot variable index when the goal's joint is fixed (GoalContext::getVariablePosition, goal.h:70-77), -1 none.  TouchGoal: its number of points
     int32_t param_off;  // offset of the goal's numbers inside the per-query parameter vector
-    int32_t pad;
+    int32_t pad;        // TouchGoal: its number of disks, whose rows lie directly behind its points in touch_points (0 for every other goal)
 };
 
 struct DevProblem {
@@ -122,8 +122,8 @@ struct DevProblem {
     DevGoal primary[BIOIK_MAX_GOALS];
     DevGoal secondary[BIOIK_MAX_GOALS];
     DevGoal balance[BIOIK_MAX_BALANCE];  // params: target[3] axis[3]
-    // TouchGoals: the collision points (x y z r, link frame) of the links they name, goal after goal, in a buffer of global memory that the problem handle
-    // owns (null without such a goal).  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
+    // TouchGoals: the collision points (x y z r, link frame) of the links they name and behind each goal's points its disks (cx cy cz r ax ay az 0: the
+    // ends of cylinders, the bases of cones), goal after goal, in a buffer of global memory that the problem handle owns (null without such a goal).  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
     const double* touch_points;
 };
 

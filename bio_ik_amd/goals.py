@@ -238,7 +238,7 @@ class PlaneGoal(LinkGoalBase):
 
 class TouchGoal(LinkGoalBase):
     """goal_types.h:330-377, goal_types.cpp:152-228: the collision shapes of the link touch the plane through `position` with `normal`.  The shapes are the
-    link's collision points of the robot model (RobotModel.add_collision_box / _sphere / _points, or the URDF reader): no FCL."""
+    link's collision points and disks of the robot model (RobotModel.add_collision_box / _sphere / _points / _cylinder / _cone, or the URDF reader): no FCL."""
     opcode = abi.GOAL_TOUCH
 
     def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0):
@@ -255,15 +255,18 @@ class TouchGoal(LinkGoalBase):
     def params(self):
         return np.concatenate([self.position, self.normal])
 
-    def evaluate(self, frame, points):
-        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link).  The device's formula in numpy."""
+    def evaluate(self, frame, points, disks=None):
+        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link), disks [m][8] =
+        RobotModel.collision_disks(link) (optional).  The device's formula in numpy."""
         f = np.asarray(frame, dtype=np.float64)
         pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        dks = np.zeros((0, 8)) if disks is None else np.asarray(disks, dtype=np.float64).reshape(-1, 8)
         x, y, z, w = f[3:7]
         u = np.array([-x, -y, -z])  # tf2's inverse(): the conjugate
         t = 2.0 * np.cross(u, self.normal)
         n_l = self.normal + w * t + np.cross(u, t)
-        d = float(np.min(pts[:, :3] @ n_l - pts[:, 3])) - float(np.dot(self.normal, self.position - f[:3]))
+        support = np.concatenate([pts[:, :3] @ n_l - pts[:, 3], dks[:, :3] @ n_l - dks[:, 3] * np.linalg.norm(np.cross(n_l[None], dks[:, 4:7]), axis=1)])
+        d = float(np.min(support)) - float(np.dot(self.normal, self.position - f[:3]))
         return d * d
 
 

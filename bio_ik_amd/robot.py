@@ -57,6 +57,8 @@ class RobotModel:
         self.link_points = {}   # link index -> list of (x, y, z, r): collision points in the link frame (TouchGoal); r < 0 marks a shape without a point form
         self.link_meshes = {}   # link index -> list of (filename, scale xyz, origin px py pz qx qy qz qw): <mesh> collisions a URDF names; the caller supplies their vertices
         self.link_unsupported = {}  # link index -> kinds of shapes without a point form (add_collision_unsupported)
+        self.link_disks = {}    # link index -> list of (cx, cy, cz, r, ax, ay, az, 0): collision disks in the link frame (TouchGoal): the ends of cylinders, the bases of cones
+        self.link_solids = {}   # link index -> list of (kind, radius, length, origin px py pz qx qy qz qw): <cylinder> collisions a URDF names (resolve_collision_solids)
         self.meshes_resolved = set()  # links of link_meshes whose vertices the caller has supplied (add_collision_points)
         self.groups = {}
         self._keep = None
@@ -160,11 +162,67 @@ class RobotModel:
         self.add_collision_points(link, [(0.0, 0.0, 0.0)], [float(radius)], origin, _shape=True)
 
     def add_collision_unsupported(self, link, kind="cylinder"):
-        """A shape that is no set of points (cylinder, cone): recorded (link_unsupported: its kind), and a TouchGoal on this link is refused
-        (BIOIK_ERR_UNSUPPORTED); never approximated."""
+        """A shape the caller did not convert into points or disks (a cylinder or a cone left as it was: add_collision_cylinder / _cone convert them): recorded
+        (link_unsupported: its kind), and a TouchGoal on this link is refused (BIOIK_ERR_UNSUPPORTED); never approximated."""
         i = link if isinstance(link, int) else self.link_index(link)
         self.link_unsupported.setdefault(i, []).append(str(kind))
         self.link_points.setdefault(i, []).append((0.0, 0.0, 0.0, -1.0))
+        self._keep = None
+
+    # ---- cylinders and cones: the convex hull of disks and points, whose support function is exact in closed form (include/bioik_hip.h: BIOIK_GOAL_TOUCH) ----
+    def add_collision_disks(self, link, disks, origin=None):
+        """Raw disks of `link` (name or index): rows cx cy cz r ax ay az (an eighth number, if given, must be 0) -- centre, radius >= 0, axis of unit length
+        (within 1e-9).  origin: as in add_collision_points; centres are moved and axes turned by it."""
+        i = link if isinstance(link, int) else self.link_index(link)
+        rows = np.asarray(disks, dtype=np.float64)
+        rows = rows.reshape(-1, 8 if rows.ndim == 2 and rows.shape[1] == 8 else 7)
+        if not np.all(np.isfinite(rows)) or np.any(rows[:, 3] < 0) or (rows.shape[1] == 8 and np.any(rows[:, 7] != 0)):
+            raise ValueError("collision disks must be finite, their radii >= 0 and their eighth number 0")
+        if np.any(np.abs(np.linalg.norm(rows[:, 4:7], axis=1) - 1.0) > 1e-9):
+            raise ValueError("the axis of a collision disk must be of unit length")
+        c, a = rows[:, :3], rows[:, 4:7]
+        if origin is not None and tuple(float(v) for v in origin) != (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0):
+            o = np.asarray(origin, dtype=np.float64).reshape(7)
+            c = np.array([quat_rotate(o[3:], v) + o[:3] for v in c]).reshape(-1, 3)
+            a = np.array([quat_rotate(o[3:], v) for v in a]).reshape(-1, 3)
+        self.link_disks.setdefault(i, []).extend((float(u[0]), float(u[1]), float(u[2]), float(r), float(v[0]), float(v[1]), float(v[2]), 0.0)
+                                                 for u, r, v in zip(c, rows[:, 3], a))
+        self._keep = None
+
+    def add_collision_cylinder(self, link, radius, length, origin=None):
+        """URDF <cylinder radius length> (shapes::Cylinder): centred on its origin, axis z -- its two end disks at z = -length / 2 and z = +length / 2 (exact:
+        a cylinder is their convex hull)."""
+        h = 0.5 * float(length)
+        self.add_collision_disks(link, [(0.0, 0.0, -h, float(radius), 0.0, 0.0, 1.0), (0.0, 0.0, h, float(radius), 0.0, 0.0, 1.0)], origin)
+
+    def add_collision_cone(self, link, radius, length, origin=None):
+        """shapes::Cone of MoveIt: the origin halfway up, the tip on +z -- its base disk at z = -length / 2 and its apex, a point with r = 0 at z = +length / 2
+        (exact: a cone is their convex hull)."""
+        h = 0.5 * float(length)
+        self.add_collision_disks(link, [(0.0, 0.0, -h, float(radius), 0.0, 0.0, 1.0)], origin)
+        self.add_collision_points(link, [(0.0, 0.0, h)], None, origin, _shape=True)
+
+    def collision_disks(self, link):
+        """[n][8] cx cy cz r ax ay az 0 of `link` as the device will read them"""
+        i = link if isinstance(link, int) else self.link_index(link)
+        return np.asarray(self.link_disks.get(i, []), dtype=np.float64).reshape(-1, 8)
+
+    def resolve_collision_solids(self, link=None):
+        """Turns every solid the URDF reader recorded (link_solids; of `link`, or of all links) into disks, and takes away exactly what the reader left in
+        its place: one marker row and one link_unsupported entry per solid.  After it a TouchGoal on the link is accepted (unless another marker remains)."""
+        links = list(self.link_solids) if link is None else [link if isinstance(link, int) else self.link_index(link)]
+        for i in links:
+            for kind, radius, length, origin in self.link_solids.pop(i, []):
+                if kind == "cylinder":
+                    self.add_collision_cylinder(i, radius, length, origin)
+                else:
+                    self.add_collision_cone(i, radius, length, origin)
+                self.link_points[i].remove((0.0, 0.0, 0.0, -1.0))
+                self.link_unsupported[i].remove(kind)
+            if i in self.link_unsupported and not self.link_unsupported[i]:
+                del self.link_unsupported[i]
+            if i in self.link_points and not self.link_points[i]:
+                del self.link_points[i]
         self._keep = None
 
     def collision_points(self, link):
@@ -272,6 +330,9 @@ class RobotModel:
                     for i in range(self.n_links)]
             k["link_point_first"] = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
             k["link_points"] = np.asarray([p for r in rows for p in r], dtype=np.float64).reshape(-1, 4)
+            drows = [self.link_disks.get(i, ()) for i in range(self.n_links)]
+            k["link_disk_first"] = np.concatenate([[0], np.cumsum([len(r) for r in drows])]).astype(np.int32)
+            k["link_disks"] = np.asarray([p for r in drows for p in r], dtype=np.float64).reshape(-1, 8)
             self._keep = k
         return self._keep
 
@@ -300,6 +361,9 @@ class RobotModel:
         if len(k["link_points"]):
             d.link_point_first = abi.iptr(k["link_point_first"])
             d.link_points = abi.dptr(k["link_points"])
+        if len(k["link_disks"]):
+            d.link_disk_first = abi.iptr(k["link_disk_first"])
+            d.link_disks = abi.dptr(k["link_disks"])
         return d
 
 

@@ -13,7 +13,8 @@ src/kinematics_plugin.cpp:167-189) is built here from the robot description itse
     the URDF's root, as MoveIt does for a mobile or free-flying base.
 Read as well: <inertial> mass and origin of every link (BalanceGoal, goal_types.cpp:236-247); <collision> <origin> with <box> / <sphere> as the link's
 collision points (TouchGoal: RobotModel.add_collision_box / _sphere), <mesh filename scale> recorded in RobotModel.link_meshes without loading the file (the
-caller adds its vertices with add_collision_points), <cylinder> recorded as a shape without a point form (a TouchGoal on that link is refused).
+caller adds its vertices with add_collision_points), <cylinder radius length> recorded in RobotModel.link_solids and, until RobotModel.resolve_collision_solids() turns it into its two end disks, as a
+shape without a point form (a TouchGoal on that link is refused).
 Not read: visual geometry, transmissions, <safety_controller>, xacro macros."""
 import xml.etree.ElementTree as ET
 
@@ -132,8 +133,10 @@ def load_urdf(urdf_xml, srdf_xml=None):
             elif shape.tag == "mesh":
                 m.link_meshes.setdefault(i, []).append((shape.get("filename"), _floats(shape.get("scale"), 3, (1, 1, 1)),
                                                         origin if origin is not None else (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)))
-            elif shape.tag == "cylinder":
+            elif shape.tag == "cylinder":  # left as a marker until the caller asks for its disks (RobotModel.resolve_collision_solids)
                 m.add_collision_unsupported(i, "cylinder")
+                m.link_solids.setdefault(i, []).append(("cylinder", float(shape.get("radius")), float(shape.get("length")),
+                                                        origin if origin is not None else (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)))
             else:
                 raise ValueError("link %r: unsupported collision geometry <%s>" % (l.get("name"), shape.tag))
     m._keep = None

@@ -84,19 +84,25 @@ enum {
                                             EVERY link of the model with a positive mass (bioik_model_desc::link_mass), each of which
                                             becomes a tip of the problem, as BalanceGoal::describe does                              */
     BIOIK_GOAL_TOUCH = 17,               /* goal_types.h:330-377, goal_types.cpp:152-228  params: position[3] normal[3].  The collision shapes of the
-                                            link touch the plane through `position` with unit `normal`: with the link's frame (p, q) and its
-                                            points (v_i, r_i) of bioik_model_desc::link_points,
-                                                n_l = rotate(conjugate(q), normal)      d = min_i (n_l . v_i - r_i) - normal . (position - p)
+                                            link touch the plane through `position` with unit `normal`: with the link's frame (p, q), its
+                                            points (v_i, r_i) of bioik_model_desc::link_points and its disks (c_j, a_j, r_j) of link_disks,
+                                                n_l = rotate(conjugate(q), normal)
+                                                d = min( min_i (n_l . v_i - r_i),  min_j (n_l . c_j - r_j |n_l x a_j|) ) - normal . (position - p)
                                             and the cost is d * d.  No FCL: a box is its 8 corners, a sphere one point with a radius, a mesh its
-                                            vertices (the support function along the normal, what the reference's hill climb returns).  A link
-                                            without points: BIOIK_ERR_INVALID_ARGUMENT; more than BIOIK_MAX_TOUCH_POINTS: BIOIK_ERR_UNSUPPORTED   */
+                                            vertices, a cylinder its two end disks, a cone its base disk and its apex (the support function along
+                                            the normal, what the reference's hill climb returns; a disk's is exact in closed form, and n_l is not
+                                            assumed to be of unit length).  A link with neither points nor disks: BIOIK_ERR_INVALID_ARGUMENT; more
+                                            than BIOIK_MAX_TOUCH_POINTS points and disks together: BIOIK_ERR_UNSUPPORTED                        */
     BIOIK_GOAL_TYPE_COUNT = 18
     /* JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
 };
 /* Points one BIOIK_GOAL_TOUCH may read (the table of its link).  The minimum is a loop every evaluation of every individual runs in full: about five
  * FP64 issue slots per point (three fused multiply-adds, a minimum and its canonicalisation; counted in the compiled loop, not timed), so by that count a few
  * hundred points cost as much as the whole chain walk of a 7-joint arm (profiles/touch_goal_metadata_and_bench.log has measured solves per second at 8, 64 and 1024 points).
- * Hand meshes over as their convex hull or decimated: only hull vertices can be the minimum. */
+ * Hand meshes over as their convex hull or decimated: only hull vertices can be the minimum.
+ * A disk counts as one point towards this limit and costs about 29 FP64 issue slots, as much as six points: six for the cross product, three for its
+ * squared norm, fourteen for the square root (a reciprocal square root estimate, its refinement to the correctly rounded root and the scaling around it), three
+ * for n . c, and the closing fused multiply-add, minimum and canonicalisation (again counted in the compiled loop, not timed). */
 #define BIOIK_MAX_TOUCH_POINTS 1024
 
 /* number of per-query parameter doubles of a goal opcode, or -1 for an unknown opcode */
@@ -177,10 +183,17 @@ typedef struct bioik_model_desc {
     const double* link_center;           /* [n_links*3] urdf::Link::inertial->origin.position (link frame); NULL with link_mass   */
     /* Collision points of the links (only BIOIK_GOAL_TOUCH reads them), in compressed rows: link l owns the points link_point_first[l] ... link_point_first[l + 1]
        - 1.  A point is x y z r IN THE LINK FRAME (the shape's collision origin already applied by the caller), r >= 0 the radius of a sphere around it.  A row with
-       r == -1 exactly is no point but a MARKER (any other negative radius is BIOIK_ERR_INVALID_ARGUMENT): the link carries a shape that is no set of points (a cylinder, a cone, a mesh whose vertices are not there) -- the model is accepted, a BIOIK_GOAL_TOUCH that names
+       r == -1 exactly is no point but a MARKER (any other negative radius is BIOIK_ERR_INVALID_ARGUMENT): the link carries a mesh whose vertices are not there, or a shape the caller did not convert into points or disks (a cylinder or a cone it left as it was) -- the model is accepted, a BIOIK_GOAL_TOUCH that names
        the link is refused with BIOIK_ERR_UNSUPPORTED (such a shape is never approximated silently).  Both NULL: no link has shapes.  A caller whose struct_size ends in front of these two fields (a build against the header without them) gets none.                    */
     const int32_t* link_point_first;     /* [n_links + 1] ascending, [0] = 0                                                       */
     const double* link_points;           /* [link_point_first[n_links] * 4]                                                        */
+    /* Collision disks of the links (only BIOIK_GOAL_TOUCH reads them), rows like the points': link l owns the disks link_disk_first[l] ... link_disk_first[l + 1] - 1.
+       A disk is cx cy cz r ax ay az 0 IN THE LINK FRAME: centre, radius r >= 0, axis of unit length (|a| within 1e-9 of 1), and a zero that fills the row;
+       everything finite, else BIOIK_ERR_INVALID_ARGUMENT.  A cylinder is the hull of its two end disks, a cone that of its base disk and its apex (a point with
+       r = 0 in link_points): both exact.  Both NULL: no link has disks.  A caller whose struct_size ends in front of these two fields, or in front of
+       link_point_first (builds against the two earlier headers), gets none; a size between two of the three is BIOIK_ERR_INVALID_ARGUMENT.                  */
+    const int32_t* link_disk_first;      /* [n_links + 1] ascending, [0] = 0                                                       */
+    const double* link_disks;            /* [link_disk_first[n_links] * 8]                                                         */
 } bioik_model_desc;
 
 /* ---- one goal of the problem template (structure shared by every query of a batch; the numeric
@@ -276,7 +289,7 @@ void bioik_model_destroy(bioik_model* m);
  * (problem.cpp:72-228, ik_base.h:154-161, forward_kinematics.h:253-330, 566-599).
  * Size limits of one problem (BIOIK_ERR_UNSUPPORTED beyond them): 64 moving joints on the union of the goal chains (a short
  * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals,
- * BIOIK_MAX_TOUCH_POINTS collision points per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS).
+ * BIOIK_MAX_TOUCH_POINTS collision points and disks together per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS).
  * Tips and joints are further bounded TOGETHER by the 160 KiB of LDS of a CU: the function-level entry points hold 7 x tips x joints doubles
  * of tables plus a genotype column per lane (64 tips on 12 joints: 71 KiB; 24 tips on 63 joints: about 137 KiB; 64 tips on 63 joints: about
  * 290 KiB), the solvers hold more.  A problem beyond that is accepted here and refused with BIOIK_ERR_UNSUPPORTED by every entry point that
