@@ -32,11 +32,68 @@ using bioik::Error;
 
 static thread_local std::string g_err;
 
+// The solve kernels, each described ONCE: name, __launch_bounds__, the kernel body it is a build of -- solve_body<LEAN, CL, JOINT, SLIM, FIXED> (bioik_kernels.h) or
+// point_body (bioik_gradient.h).  The __global__ definitions of the HIP back end, the SolveKernel enum, the names of the BIOIK_SOLVE_REPORT lines, launch_kernel (both
+// back ends) and the solve kernels' part of BIOIK_WIDE_LDS_KERNELS all come from these rows; SolveLauncher::choose_kernel says which row a launch takes.
+//
+// k_solve, k_solve_lean: two flavours of the solver (bioik_platform.h, pb_flavour): k_solve_lean for problems without floating / planar joints whose ops
+// meet the genes in gene order (every BASELINE.json configuration), k_solve for everything
+// k_solve_lean_cl: the lean flavour with the children computed where they are read (no genotype columns in LDS: the LDS-bound problems, C3 / C4)
+// k_solve_lean_cl4: the same body under the register budget of FOUR wavefronts per SIMD (128 VGPRs instead of 168).  The hot loops of the computed-children
+// flavour fit it; its once-per-step code then keeps some values in scratch memory, so a lone step is slower (110 against 102 us) and it
+// only pays where the LDS footprint lets the fourth wavefront be resident AND the generation loops dominate a step: the launcher
+// picks it when a CU holds at least 16 wavefronts of the problem and a lane walks eight or more children per generation (the
+// 31-joint, 512-children configuration: +12 %; the first launch of a 7-joint, 128-children solve: -2 %; profiles/r03_ab_four_waves.log).
+// (solve_body<.., SLIM>: the species record is read from LDS per generation instead of living in scratch memory across the chain walks: 67 -> 31 spilled values)
+// k_solve_lean_cl4h: k_solve_lean_cl4 with two HELPER wavefronts (solve_body<.., FIXED = 5>), for launches that leave most of the chip idle -- a single pose of the plugin, a few
+// hundred queries, the stragglers a chip-filling call hands over when the chip runs empty: wavefronts 0 and 1 are k_solve_lean_cl4's (a species each), wavefronts
+// 2 and 3 walk half of every generation's children for them, so that a generation's walks take a wavefront half the instructions.  A lone wavefront issues one
+// instruction per ~4.3 cycles whatever it does and k_solve_lean_cl4 keeps two of a CU's four SIMDs busy: this keeps four.  Hand-overs between the wavefronts
+// are words in LDS, the helpers reach no barrier (profiles/r05_helped_kernel.log)
+// k_solve_lean_cl64w4: the computed-children kernel for BIOIK_SCHEDULE_THROUGHPUT: ONE wavefront per query (both species on its halves; the compiler knows it and drops the
+// barriers) under the register budget of four wavefronts per SIMD
+// (solve_body<.., DENSE>: what the launcher guarantees for this kernel -- 64 lanes, the species on the halves of the wavefront, exact FK, children in
+// pairs, no secondary goal -- is known at compile time, and the fitness values of a generation cross its walks in LDS instead of in registers).
+// The whole solve of a stream of batches under the dense mapping: sixteen queries per CU instead of twelve (+11 % with six solves in flight;
+// 30 values -- the lane's best two across the chain walk, a few kernel-lifetime ones -- then live in scratch memory; profiles/r03_ab_dense_four_waves.log)
+// k_solve_lean_lin: populations of up to 32 children per species with LINEARISED phenotypes (the reference's own parameters: 16 children, RobotFK_Mutator): both species on
+// the halves of one wavefront, children computed where they are read, under the register budget of four wavefronts per SIMD (solve_body<.., FIXED = 3>).
+// Such solves are bound by the latency of their single-individual phases (linearisation, line search, ranking), not by arithmetic: sixteen queries
+// per CU instead of twelve (profiles/r04_ab_small_population_kernel.log)
+// k_solve_lean_clj4: computed children with both species of a query on the halves of one wavefront AND secondary goals: the children of the two species are walked as one list over
+// the 64 lanes (solve_body<.., JOINT>), so that the wavefront does not wait for the longer of two random prefixes (C3: +7 %, profiles/r03_ab_joint_walk.log) -- under
+// the register budget of four wavefronts per SIMD (FIXED = 4: fitness values parked in LDS, accessors rebuilt behind the walks).  (Its 168-register sibling
+// k_solve_lean_clj of rounds 3 - 5 served the one LDS band in which a CU holds exactly twelve queries; retired in round 6: this build runs there too.)
+// k_solve_point: the point solvers gd_c / jac (bioik_gradient.h): one wavefront per query, at most 64 KiB of LDS (SolveLauncher::solve_point)
+#ifndef BIOIK_SOLVE_WAVES_PER_SIMD
+#define BIOIK_SOLVE_WAVES_PER_SIMD 3  // register budget of k_solve: wavefronts per SIMD (its __launch_bounds__)
+#endif
+#ifndef BIOIK_DENSE_WAVES
+#define BIOIK_DENSE_WAVES 4
+#endif
+// (ROW(X, name, bounds, body...): X is handed through to the row macro, for lists whose entries are X(name))
+#define BIOIK_SOLVE_BODY_KERNELS(ROW, X)                                                                   \
+    ROW(X, k_solve, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<false>)                                  \
+    ROW(X, k_solve_lean, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<true>)                              \
+    ROW(X, k_solve_lean_cl, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<true, true>)                     \
+    ROW(X, k_solve_lean_cl4, (128, 4), solve_body<true, true, false, true, 2>)                             \
+    ROW(X, k_solve_lean_cl4h, (256, 4), solve_body<true, true, false, true, 5>)                            \
+    ROW(X, k_solve_lean_cl64w4, (64, BIOIK_DENSE_WAVES), solve_body<true, true, false, true, 1>)           \
+    ROW(X, k_solve_lean_lin, (64, 4), solve_body<true, true, false, true, 3>)                              \
+    ROW(X, k_solve_lean_clj4, (64, 4), solve_body<true, true, true, true, 4>)
+#define BIOIK_SOLVE_KERNELS(ROW) BIOIK_SOLVE_BODY_KERNELS(ROW, ) ROW(, k_solve_point, (64), point_body)
+#define BIOIK_ENUM_(X, name, ...) name,
+enum class SolveKernel { BIOIK_SOLVE_KERNELS(BIOIK_ENUM_) };
+#undef BIOIK_ENUM_
+#define BIOIK_NAME_(X, name, ...) #name,
+static const char* const kSolveKernelNames[] = {BIOIK_SOLVE_KERNELS(BIOIK_NAME_)};
+#undef BIOIK_NAME_
+
 // The kernels that may be launched with more than 64 KiB of dynamic LDS: above 64 KiB a launch needs an explicit allowance, which be_allow_lds(bytes)
 // gives every kernel of this list.  Both back ends take the list from here.
-#define BIOIK_WIDE_LDS_KERNELS(X)                                                                                                              \
-    X(k_solve) X(k_solve_lean) X(k_solve_lean_cl) X(k_solve_lean_cl4) X(k_solve_lean_cl64w4) X(k_solve_lean_lin) X(k_solve_lean_clj4) X(k_solve_lean_cl4h) \
-    X(k_eval_fk) X(k_eval_fitness) X(k_eval_approximator) X(k_eval_reproduce) X(k_eval_check) X(k_stream_fitness)
+#define BIOIK_WIDE_ROW_(X, name, ...) X(name)
+#define BIOIK_WIDE_LDS_KERNELS(X) \
+    BIOIK_SOLVE_BODY_KERNELS(BIOIK_WIDE_ROW_, X) X(k_eval_fk) X(k_eval_fitness) X(k_eval_approximator) X(k_eval_reproduce) X(k_eval_check) X(k_stream_fitness)
 
 // ------------------------------------------------------------------------------------------------------------
 // back end: memory + launch
@@ -190,75 +247,13 @@ static void be_stream_destroy(stream_t s) {
     if (s) (void)hipStreamDestroy(s);
 }
 
-#ifndef BIOIK_SOLVE_WAVES_PER_SIMD
-#define BIOIK_SOLVE_WAVES_PER_SIMD 3
-#endif
-// two flavours of the solver (bioik_platform.h, pb_flavour): k_solve_lean for problems without floating / planar joints whose ops
-// meet the genes in gene order (every BASELINE.json configuration), k_solve for everything
-__global__ void __launch_bounds__(256, BIOIK_SOLVE_WAVES_PER_SIMD) k_solve(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<false>(a, blockIdx.x, lds);
-}
-__global__ void __launch_bounds__(256, BIOIK_SOLVE_WAVES_PER_SIMD) k_solve_lean(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true>(a, blockIdx.x, lds);
-}
-// the lean flavour with the children computed where they are read (no genotype columns in LDS: the LDS-bound problems, C3 / C4)
-__global__ void __launch_bounds__(256, BIOIK_SOLVE_WAVES_PER_SIMD) k_solve_lean_cl(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true>(a, blockIdx.x, lds);
-}
-// The same body under the register budget of FOUR wavefronts per SIMD (128 VGPRs instead of 168).  The hot loops of the computed-children
-// flavour fit it; its once-per-step code then keeps some values in scratch memory, so a lone step is slower (110 against 102 us) and it
-// only pays where the LDS footprint lets the fourth wavefront be resident AND the generation loops dominate a step: the launcher
-// picks it when a CU holds at least 16 wavefronts of the problem and a lane walks eight or more children per generation (the
-// 31-joint, 512-children configuration: +12 %; the first launch of a 7-joint, 128-children solve: -2 %; profiles/r03_ab_four_waves.log).
-// (solve_body<.., SLIM>: the species record is read from LDS per generation instead of living in scratch memory across the chain walks: 67 -> 31 spilled values)
-__global__ void __launch_bounds__(128, 4) k_solve_lean_cl4(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true, false, true, 2>(a, blockIdx.x, lds);
-}
-// k_solve_lean_cl4 with two HELPER wavefronts (solve_body<.., FIXED = 5>), for launches that leave most of the chip idle -- a single pose of the plugin, a few
-// hundred queries, the stragglers a chip-filling call hands over when the chip runs empty: wavefronts 0 and 1 are k_solve_lean_cl4's (a species each), wavefronts
-// 2 and 3 walk half of every generation's children for them, so that a generation's walks take a wavefront half the instructions.  A lone wavefront issues one
-// instruction per ~4.3 cycles whatever it does and k_solve_lean_cl4 keeps two of a CU's four SIMDs busy: this keeps four.  Hand-overs between the wavefronts
-// are words in LDS, the helpers reach no barrier (profiles/r05_helped_kernel.log)
-__global__ void __launch_bounds__(256, 4) k_solve_lean_cl4h(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true, false, true, 5>(a, blockIdx.x, lds);
-}
-// The computed-children kernel for BIOIK_SCHEDULE_THROUGHPUT: ONE wavefront per query (both species on its halves; the compiler knows it and drops the
-// barriers) under the register budget of four wavefronts per SIMD
-// (solve_body<.., DENSE>: what the launcher guarantees for this kernel -- 64 lanes, the species on the halves of the wavefront, exact FK, children in
-// pairs, no secondary goal -- is known at compile time, and the fitness values of a generation cross its walks in LDS instead of in registers)
-#ifndef BIOIK_DENSE_WAVES
-#define BIOIK_DENSE_WAVES 4
-#endif
-__global__ void __launch_bounds__(64, BIOIK_DENSE_WAVES) k_solve_lean_cl64w4(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true, false, true, 1>(a, blockIdx.x, lds);
-}
-// Populations of up to 32 children per species with LINEARISED phenotypes (the reference's own parameters: 16 children, RobotFK_Mutator): both species on
-// the halves of one wavefront, children computed where they are read, under the register budget of four wavefronts per SIMD (solve_body<.., FIXED = 3>).
-// Such solves are bound by the latency of their single-individual phases (linearisation, line search, ranking), not by arithmetic: sixteen queries
-// per CU instead of twelve (profiles/r04_ab_small_population_kernel.log)
-__global__ void __launch_bounds__(64, 4) k_solve_lean_lin(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true, false, true, 3>(a, blockIdx.x, lds);
-}
-// Computed children with both species of a query on the halves of one wavefront AND secondary goals: the children of the two species are walked as one list over
-// the 64 lanes (solve_body<.., JOINT>), so that the wavefront does not wait for the longer of two random prefixes (C3: +7 %, profiles/r03_ab_joint_walk.log) -- under
-// the register budget of four wavefronts per SIMD (FIXED = 4: fitness values parked in LDS, accessors rebuilt behind the walks).  (Its 168-register sibling
-// k_solve_lean_clj of rounds 3 - 5 served the one LDS band in which a CU holds exactly twelve queries; retired in round 6: this build runs there too.)
-__global__ void __launch_bounds__(64, 4) k_solve_lean_clj4(SolveArgs a) {
-    extern __shared__ double lds[];
-    solve_body<true, true, true, true, 4>(a, blockIdx.x, lds);
-}
-// the point solvers gd_c / jac (bioik_gradient.h): one wavefront per query
-__global__ void __launch_bounds__(64) k_solve_point(SolveArgs a) {
-    extern __shared__ double lds[];
-    point_body(a, blockIdx.x, lds);
-}
+#define BIOIK_GLOBAL_(X, name, bounds, ...)                      \
+    __global__ void __launch_bounds__ bounds name(SolveArgs a) { \
+        extern __shared__ double lds[];                          \
+        __VA_ARGS__(a, blockIdx.x, lds);                         \
+    }
+BIOIK_SOLVE_KERNELS(BIOIK_GLOBAL_)
+#undef BIOIK_GLOBAL_
 __global__ void k_select(SelectArgs a) { select_body(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(64) k_select_wave(SelectArgs a) { select_coop(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }  // a wavefront per query: calls of few queries with many islands
 // the k best distinct islands of every query, ranked (bioik_solve_batch_ranked): a wavefront per query, lane = island
@@ -305,6 +300,17 @@ static void be_allow_lds(size_t bytes) {
 #undef BIOIK_ALLOW_
 }
 #endif
+// a launch of the solve kernel `kind` (its row of BIOIK_SOLVE_KERNELS: the kernel, and its body for back ends that call it directly)
+static void launch_kernel(SolveKernel kind, const SolveArgs& args, uint64_t grid, int lanes, size_t lds, stream_t stream) {
+    switch (kind) {
+#define BIOIK_LAUNCH_(X, name, bounds, ...)                                        \
+    case SolveKernel::name:                                                        \
+        LAUNCH(name, (__VA_ARGS__(args, b_, l_)), grid, lanes, lds, stream, args); \
+        break;
+        BIOIK_SOLVE_KERNELS(BIOIK_LAUNCH_)
+#undef BIOIK_LAUNCH_
+    }
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // handles
@@ -571,9 +577,6 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
-#ifndef BIOIK_SOLVE_WAVES_PER_SIMD
-#define BIOIK_SOLVE_WAVES_PER_SIMD 3  // register budget of k_solve: wavefronts per SIMD (its __launch_bounds__)
-#endif
 static size_t lds_bytes(const bioik_problem* p, int nthreads, int lambda, int child_cols = 1, int groups = 1, int slot_sets = 1, bool exact = false, bool fit_park = false, bool helped = false) {
     const DevProblem& d = p->host.dev;
     return (size_t)make_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, nthreads, lambda, d.n_secondary > 0 ? (exact ? 2 : 1) : 0, child_cols, groups, slot_sets, fit_park ? 1 : 0, lambda > 0 ? 1 : 0, helped ? 1 : 0).total * 8;  // (lambda > 0: a solve's layout; the function-level kernels keep their own)
@@ -587,6 +590,9 @@ static size_t eval_lds(const bioik_problem* p, size_t bytes) {
     if (bytes > 64 * 1024) be_allow_lds(bytes);
     return bytes;
 }
+
+// a problem a lean kernel can run (bioik_platform.h, pb_flavour): no floating / planar joints, ops that meet the genes in gene order, no BalanceGoal, no TouchGoal
+static bool lean_capable(const DevProblem& d) { return d.multi_op < 0 && d.n_quat == 0 && d.genes_follow_ops != 0 && d.n_balance == 0 && d.touch_points == nullptr; }
 
 // the timeout of a solve on the device clock (bioik_problem: clock_*)
 static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t stream, SolveArgs& a) {
@@ -623,8 +629,8 @@ static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t st
 
 // ------------------------------------------------------------------------------------------------------------
 // One solve = SolveLauncher: what the call was given, where its results go (scratch, result_arrays, select_islands), the lane mapping the rules below pick
-// for it (choose_mapping), the kernel that mapping is compiled as (launch), and the launches it is cut into (plan_handovers, run).  launch_solve at the end
-// puts them in order.
+// for it (choose_mapping), the kernel that mapping is compiled as (choose_kernel: a row of BIOIK_SOLVE_KERNELS, which launch reports by the row's name and hands to
+// launch_kernel), and the launches it is cut into (plan_handovers, run).  launch_solve at the end puts them in order.
 // ------------------------------------------------------------------------------------------------------------
 struct SolveLauncher {
     bioik_problem* p;
@@ -783,8 +789,8 @@ struct SolveLauncher {
         result_arrays(pa, false);
         pa.phase_cycles = nullptr;
         set_deadline(p, sp, stream, pa);
-        if (sw.report) std::fprintf(stderr, "[bioik] launch: k_solve_point, 64 lanes, %zu B of LDS\n", lds_point);
-        LAUNCH(k_solve_point, point_body(pa, b_, l_), units, 64, lds_point, stream, pa);
+        if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, 64 lanes, %zu B of LDS\n", kSolveKernelNames[(int)SolveKernel::k_solve_point], lds_point);
+        launch_kernel(SolveKernel::k_solve_point, pa, units, 64, lds_point, stream);
         select_islands(pa);
     }
     void choose_mapping() {
@@ -799,7 +805,7 @@ struct SolveLauncher {
         quat = dp.n_quat > 0;  // winners re-derived: their momentum is taken before the quaternion genes are renormalised
         manual = sw.manual();
         // children computed where they are read (no genotype columns in LDS): the lean flavour can, whenever it is chosen below
-        can_columnless = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr && !sw.general_set;
+        can_columnless = lean_capable(dp) && !sw.general_set;
         sp.columnless = 0;
         // k_solve_lean_cl4's mapping first -- 128 lanes, a wavefront per species, children computed where they are read and walked in pairs, the kernel compiled
         // for exactly that under the budget of four wavefronts per SIMD (no register spills since round 4): for problems without a secondary goal whose
@@ -896,8 +902,8 @@ struct SolveLauncher {
         // resident from the start, most steps retired per ms while the chip is full -- and, when the chip runs empty, the stragglers on to k_solve_lean_cl4 whose lone
         // step is a third shorter (SolveArgs::resident).  An isolated 4096-query call: 9.2 -> 8.5 ms (profiles/r04_drain_handover.log).  Streams of solves keep the
         // chip full, never see the hand-over and pay for its bookkeeping: the throughput schedule does without (BIOIK_SOLVE_DRAIN_THROUGHPUT=1: with).
-        dense_ok = !manual && can_columnless && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 && dp.n_secondary == 0 && !sw.three_waves && dp.multi_op < 0 &&
-                              dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr && dp.serial_chain != 0;
+        dense_ok = !manual && can_columnless && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 && dp.n_secondary == 0 && !sw.three_waves &&
+                              dp.serial_chain != 0;  // (can_columnless: a lean-capable problem)
         // (BIOIK_SOLVE_CAPTURE_ONE_LAUNCH=1: round 4's rule -- a call on a stream that is being captured gets a one-launch mapping.  The replay defect it worked around
         // was the runtime's memset NODE in front of the kernels, not the hand-over; the library fills its words with a kernel of its own now
         // and captured calls take the same mapping as eager ones)
@@ -912,8 +918,7 @@ struct SolveLauncher {
         groups = sp.species_parallel ? 2 : 1;
         lds = lds_bytes(p, nth, sp.lambda, sp.columnless ? 0 : sp.child_cols, groups, sp.child_pairs ? 2 : 1, exact, sp.columnless && exact);
         if (lds > kLds) throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs more LDS per workgroup than a CU has");
-        lean = dp.multi_op < 0 && dp.n_quat == 0 && dp.genes_follow_ops != 0 && dp.n_balance == 0 && dp.touch_points == nullptr;
-        if (sw.general_set && sw.general) lean = false;
+        lean = lean_capable(dp) && !(sw.general_set && sw.general);
         halves_ok = lean && can_columnless && exact && sp.lambda >= 128 && dp.D < 32;  // the first launch's mapping exists for this problem
     }
     void report_mapping() const {  // diagnostics: the lane mapping and the residency it gives
@@ -935,7 +940,8 @@ struct SolveLauncher {
                      dp.n_ops, dp.D, dp.T, dp.n_slots, nth, sp.species_parallel, sp.child_cols, sp.child_pairs, sp.columnless, lds, (L.slots - L.xcol) * 8,
                      (L.g_first - L.slots) * 8, L.g_stride * 8, groups, (int)(kLds / lds), (int)(kLds / lds) * (nth / 64));
     }
-    void launch(const SolveArgs& args, int lanes, size_t lds_b) {
+    // the kernel a launch of `lanes` lanes and `lds_b` bytes of LDS under the mapping of args.sp is compiled as
+    SolveKernel choose_kernel(const SolveArgs& args, int lanes, size_t lds_b) const {
         // computed children: the 128-register build when a CU's LDS holds at least the 16 wavefronts it makes room for and a lane walks
         // at least eight children per generation (the generation loops, which fit the smaller budget, are then most of a step)
         const int group_lanes = lanes / (args.sp.species_parallel ? 2 : 1);
@@ -948,7 +954,6 @@ struct SolveLauncher {
         // profiles/r03_ab_joint_walk.log)
         const bool joint = lanes == 64 && args.sp.species_parallel && args.sp.child_pairs && dp.n_secondary > 0 && args.sp.fk_mode == BIOIK_FK_EXACT &&
                            !sw.no_joint;
-        const bool joint4 = joint;  // (k_solve_lean_clj4 wherever the joint walk applies)
         const bool dense_launch = lanes == 64 && dense && args.sp.species_parallel && args.sp.child_pairs && args.sp.columnless;  // (what solve_body<.., FIXED = 1> is compiled for)
         const bool lin_launch = small_linear && lanes == 64 && args.sp.species_parallel && args.sp.columnless && !args.sp.child_pairs && args.sp.fk_mode == BIOIK_FK_LINEAR;
         // k_solve_lean_cl4's helped build: launches that leave most of the chip idle (every unit gets four wavefronts instead of two), and the stragglers of a
@@ -957,36 +962,25 @@ struct SolveLauncher {
         // pre-selected children's walks)
         const bool helped_launch = lean && four_waves && !manual && !sw.four_waves && args.sp.columnless && sw.helped > 0 &&
                                    (units <= (uint64_t)sw.helped || (args.unit_list != nullptr && args.resident != nullptr));
-        if (helped_launch) {
-            const size_t lds_h = lds_b + 64;  // (make_layout: the sixteen words of the hand-overs)
-            if (lds_h > 64 * 1024) be_allow_lds(lds_h);
-            if (sw.report)
-                std::fprintf(stderr, "[bioik] launch: k_solve_lean_cl4h, 256 lanes (two of the four wavefronts are helpers), %zu B of LDS, steps [%d, %d)\n", lds_h, (int)args.step_begin,
-                             (int)(args.step_end < args.sp.max_steps ? args.step_end : args.sp.max_steps));
-            LAUNCH(k_solve_lean_cl4h, (solve_body<true, true, false, true, 5>(args, b_, l_)), units, 256, lds_h, stream, args);
-            return;
+        if (helped_launch) return SolveKernel::k_solve_lean_cl4h;
+        if (!lean) return SolveKernel::k_solve;
+        if (lin_launch) return SolveKernel::k_solve_lean_lin;
+        if (!args.sp.columnless) return SolveKernel::k_solve_lean;
+        if (joint) return SolveKernel::k_solve_lean_clj4;
+        if (dense_launch) return SolveKernel::k_solve_lean_cl64w4;
+        return four_waves ? SolveKernel::k_solve_lean_cl4 : SolveKernel::k_solve_lean_cl;
+    }
+    void launch(const SolveArgs& args, int lanes, size_t lds_b) {
+        const SolveKernel kind = choose_kernel(args, lanes, lds_b);
+        const bool helped = kind == SolveKernel::k_solve_lean_cl4h;
+        if (helped) {
+            lanes = 256, lds_b += 64;  // (make_layout: the sixteen words of the hand-overs)
+            if (lds_b > 64 * 1024) be_allow_lds(lds_b);
         }
         if (sw.report)
-            std::fprintf(stderr, "[bioik] launch: %s, %d lanes, %zu B of LDS, steps [%d, %d)\n",
-                         !lean ? "k_solve" : lin_launch ? "k_solve_lean_lin" : !args.sp.columnless ? "k_solve_lean" : joint ? "k_solve_lean_clj4" : dense_launch ? "k_solve_lean_cl64w4" : four_waves ? "k_solve_lean_cl4" : "k_solve_lean_cl",
-                         lanes, lds_b, (int)args.step_begin, (int)(args.step_end < args.sp.max_steps ? args.step_end : args.sp.max_steps));
-        if (lean && lin_launch)
-            LAUNCH(k_solve_lean_lin, (solve_body<true, true, false, true, 3>(args, b_, l_)), units, lanes, lds_b, stream, args);
-        else if (lean && args.sp.columnless && joint && joint4)
-            LAUNCH(k_solve_lean_clj4, (solve_body<true, true, true, true, 4>(args, b_, l_)), units, lanes, lds_b, stream, args);
-        else if (lean && args.sp.columnless && dense_launch)
-            // the whole solve of a stream of batches under the dense mapping: sixteen queries per CU instead of twelve (+11 % with six solves in flight;
-            // 30 values -- the lane's best two across the chain walk, a few kernel-lifetime ones -- then live in scratch memory;
-            // profiles/r03_ab_dense_four_waves.log)
-            LAUNCH(k_solve_lean_cl64w4, (solve_body<true, true, false, true, 1>(args, b_, l_)), units, lanes, lds_b, stream, args);
-        else if (lean && args.sp.columnless && four_waves)
-            LAUNCH(k_solve_lean_cl4, (solve_body<true, true, false, true, 2>(args, b_, l_)), units, lanes, lds_b, stream, args);
-        else if (lean && args.sp.columnless)
-            LAUNCH(k_solve_lean_cl, (solve_body<true, true>(args, b_, l_)), units, lanes, lds_b, stream, args);
-        else if (lean)
-            LAUNCH(k_solve_lean, solve_body<true>(args, b_, l_), units, lanes, lds_b, stream, args);
-        else
-            LAUNCH(k_solve, solve_body<false>(args, b_, l_), units, lanes, lds_b, stream, args);
+            std::fprintf(stderr, "[bioik] launch: %s, %d lanes%s, %zu B of LDS, steps [%d, %d)\n", kSolveKernelNames[(int)kind], lanes,
+                         helped ? " (two of the four wavefronts are helpers)" : "", lds_b, (int)args.step_begin, (int)(args.step_end < args.sp.max_steps ? args.step_end : args.sp.max_steps));
+        launch_kernel(kind, args, units, lanes, lds_b, stream);
     }
     // One launch, or two (SolveArgs::step_begin ...).  Measured on streams of distinct 4096-query PoseGoal batches (profiles/r02_two_launch_sweep.log):
     // split after the first step(), the state of the unsolved queries handed over through HBM, the first launch with both species of a query on
