@@ -6,11 +6,17 @@ trig mode 1 (bioik_sincos shared with the device) wherever bit-exactness is asse
 import contextlib
 
 import numpy as np
+import pytest
 
-from bio_ik_amd import abi
+from bio_ik_amd import (AvoidJointLimitsGoal, BalanceGoal, CenterJointsGoal, ConeGoal, JointVariableGoal, LineGoal, LookAtGoal, MaxDistanceGoal,
+                        MinimalDisplacementGoal, OrientationGoal, PoseGoal, PositionGoal, ProblemTemplate, RegularizationGoal, RobotModel, abi, snake)
+from bio_ik_amd.robot import quat_rotate
+from bio_ik_amd.solver import BioIKError
 from bio_ik_amd.workload import make_queries
-from conftest import random_configuration
+from conftest import balance_robot, gnarly_goals, gnarly_robot, hand_robot, mimic_robot, mobile_robot, random_configuration, stage_robot
 from oracle import orc
+
+POS_TOL, ROT_TOL = 1e-4, 1e-3  # north-star tolerance on PoseGoal results [m], [rad]
 
 
 @contextlib.contextmanager
@@ -104,6 +110,14 @@ def pose_errors(o, sol, params, tip=0, off=0):
     return perr, rerr
 
 
+def assert_poses_reached(o, sol, suc, params, tip=0, off=0, mode0=True):
+    """Result level: every reported success reproduces its goal pose under the ORACLE's exact FK within POS_TOL / ROT_TOL.  mode0: the FK of the
+    reference-pinned arithmetic, whatever mode the oracle is in (False: the mode the caller has it in -- which one is part of what is asserted)."""
+    with oracle_arithmetic(0) if mode0 else contextlib.nullcontext():
+        perr, rerr = pose_errors(o, sol, params, tip=tip, off=off)
+    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+
+
 def balance_queries(template, o, n, seed=5):
     """FK -> IK -> FK round trip with a BalanceGoal: goals [PoseGoal(tip), BalanceGoal]; the pose AND the centre-of-mass target are those of
     a random reachable configuration (oracle FK), the seed is another random configuration.  Returns seeds, params, (pose offset, balance offset)."""
@@ -112,7 +126,6 @@ def balance_queries(template, o, n, seed=5):
     mass = np.asarray(model.link_mass)
     share = mass / mass.sum()
     centers = np.asarray(model.link_center)
-    from bio_ik_amd.robot import quat_rotate
     off = [off for g, off in zip(template.goals, template.param_offsets) if g.opcode == abi.GOAL_BALANCE][0]
     full = np.tile(model.default_positions(), (n, 1))
     full[:, o.active_variables] = targets
@@ -133,7 +146,6 @@ def balance_errors(template, o, sol, params, off):
     mass = np.asarray(model.link_mass)
     share = mass / mass.sum()
     centers = np.asarray(model.link_center)
-    from bio_ik_amd.robot import quat_rotate
     tips = o.fk(sol)
     tip_of_link = {int(l): i for i, l in enumerate(o.tip_links)}
     err = np.zeros(sol.shape[0])
@@ -177,14 +189,194 @@ def point_solvers(h, o, template, n=8, exact_jac=True):
     return b
 
 
+# Whole scenarios.  make_solver: template -> HipSolver (on the device, or on the host simulator's library); the sizes are the caller's:
+# `n` the genotypes of a function_level, `trajectories` a list of keyword dicts, one trajectory() each, in that order.
+
+def function_level_gnarly(make_solver, gnarly, n):
+    """conftest.gnarly_robot: rotated origins, oblique axes, a prismatic joint, branches with parked frames, a tip on the root, all 16 goal opcodes (to 1e-12: the
+    folded joint program rounds differently there) -- and the same with two of its joints fixed"""
+    t = ProblemTemplate(gnarly, "body", gnarly_goals())
+    h, o = make_solver(t), orc.Oracle(t)
+    function_level(h, o, gnarly, np.random.default_rng(2), n=n)
+    t2 = ProblemTemplate(gnarly, "body", gnarly_goals(), fixed_joints=["lift_joint", "antenna_joint"])
+    h2, o2 = make_solver(t2), orc.Oracle(t2)
+    assert h2.D == 8
+    function_level(h2, o2, gnarly, np.random.default_rng(3), n=n)
+
+
+def mimic_joints(make_solver, n, trajectories):
+    """a joint that follows a gene and a joint that follows a joint outside every goal chain (MoveIt mimic joints, forward_kinematics.h:230-246, 623-636):
+    function level, and whole solves bit for bit"""
+    m = mimic_robot()
+    sec = MinimalDisplacementGoal(weight=0.5)
+    sec.secondary_ = True
+    t = ProblemTemplate(m, "arm", [PoseGoal("tool"), PositionGoal("finger_r_tip", weight=0.3), sec])
+    h, o = make_solver(t), orc.Oracle(t)
+    assert h.D == o.D == 5  # s1 s2 e1 w1 w2: the mimic joints and the off-chain finger are not genes
+    function_level(h, o, m, np.random.default_rng(5), n=n)  # 1e-12: the folded prismatic finger rounds differently
+    # whole solves, bit for bit, on the revolute part (the elbow that follows the shoulder)
+    t2 = ProblemTemplate(m, "arm", [PoseGoal("tool"), sec])
+    h2, o2 = make_solver(t2), orc.Oracle(t2)
+    function_level(h2, o2, m, np.random.default_rng(6), n=n, exact_bits=True)
+    for kw in trajectories:
+        trajectory(h2, o2, t2, **kw)
+
+
+def mimic_of_a_mimic(make_solver, trajectory_kw, queries, population, max_steps):
+    """a joint that follows a joint that itself follows a gene (the reference never meets one: MoveIt's RobotModel::buildMimic resolves such chains to the joint
+    at their end before bio_ik sees the model; this library does the same wherever a model is built or handed in): the oracle's trajectories, and a batch of
+    `queries` the same bits as on the robot with the resolution written out by hand"""
+    sols = []
+    for chain in ("chain", "resolved"):
+        m = mimic_robot(chain)
+        t = ProblemTemplate(m, "arm", [PoseGoal("tool")])
+        h, o = make_solver(t), orc.Oracle(t)
+        assert h.D == o.D == 4  # s1 s2 e1 w2
+        function_level(h, o, m, np.random.default_rng(6), n=40, exact_bits=True)
+        trajectory(h, o, t, **trajectory_kw)
+        seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, queries, seed=8)
+        sols.append(h.solve_batch(abi.default_solve_params(population=population, max_steps=max_steps, random_seed=2), seeds, params))
+    assert all(np.array_equal(x, y) for x, y in zip(*sols))
+
+
+def no_active_variable(make_solver, pr2, rows):
+    """every joint of the group fixed (BioIKKinematicsQueryOptions::fixed_joints, problem.cpp:104-114): D = 0, the solve runs its budget and returns the seed,
+    as the oracle does"""
+    t0 = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")])
+    names = [pr2.variable_names[v] for v in make_solver(t0).active_variables]
+    t = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")], fixed_joints=names)
+    h, o = make_solver(t), orc.Oracle(t)
+    assert h.D == o.D == 0
+    seeds, params = np.tile(pr2.default_positions(), (rows, 1)), np.tile(t.pack_params(), (rows, 1))
+    for pop, fk in ((16, abi.FK_EXACT), (128, abi.FK_EXACT), (16, abi.FK_LINEAR)):
+        p = abi.default_solve_params(population=pop, max_steps=2, random_seed=1, fk_mode=fk)
+        got, want = h.solve_batch(p, seeds, params), o.solve_batch(p, orc.RNG_COUNTER, seeds, params)
+        assert all(np.array_equal(a, b) for a, b in zip(got, want))
+        assert np.array_equal(got[0], seeds) and not got[2].any()
+
+
+def more_than_32_joints(make_solver, n, trajectories):
+    """48 moving joints on one chain (op masks, winner copy and the memetic lanes beyond 32 ops): function level and whole solves bit for bit, under whatever lane
+    mapping the launcher picks for the populations asked; 64 active variables are refused (the memetic phase needs lane D of a 64-lane wavefront)."""
+    m = snake(48)
+    t = ProblemTemplate(m, "snake", [PoseGoal("tip"), AvoidJointLimitsGoal()])
+    h, o = make_solver(t), orc.Oracle(t)
+    assert h.D == o.D == 48
+    function_level(h, o, m, np.random.default_rng(11), n=n, exact_bits=True)
+    for kw in trajectories:
+        trajectory(h, o, t, **kw)
+    with pytest.raises(BioIKError):
+        make_solver(ProblemTemplate(snake(64), "snake", [PoseGoal("tip")]))
+
+
+def _multi_variable_joint(make_solver, m, link, D, rng_seed, n, trajectories):
+    """the common head of the two scenarios below: PoseGoal on the tool and a light PositionGoal on `link`; returns h, o, t, m for the caller's own tail"""
+    t = ProblemTemplate(m, "whole", [PoseGoal("tool"), PositionGoal(link, weight=0.2)])
+    h, o = make_solver(t), orc.Oracle(t)
+    assert h.D == o.D == D
+    function_level(h, o, m, np.random.default_rng(rng_seed), n=n, exact_bits=True)
+    for kw in trajectories:
+        trajectory(h, o, t, **kw)
+    return h, o, t, m
+
+
+def floating_and_planar_joints(make_solver, base, n, trajectories):
+    """conftest.mobile_robot: a free base in front of the arm -- 7 (translation + quaternion) or 3 (x, y, theta) genes for one joint, quaternion genes renormalised
+    after reproduction (forward_kinematics.h:120-135, 695-726; ik_evolution_2.cpp:203-215, 320-324).  The Jacobian columns of these joints come from a forward
+    difference through acos / sqrt (frame.h:240-259) -- since round 6 the shared acos of bioik_acos.h and the IEEE sqrt: tables and solves bit for bit, memetic
+    solves included."""
+    return _multi_variable_joint(make_solver, mobile_robot(base), "base", 10 if base == "floating" else 6, 8, n, trajectories)
+
+
+def floating_and_planar_joints_anywhere(make_solver, mid, with_base, n, trajectories):
+    """conftest.stage_robot: a planar stage / a floating coupling in the MIDDLE of the chain, and two multi-variable joints on one chain (round 5:
+    forward_kinematics.h:120-135, 331-354 take them wherever they are): (F_src o C) o J with the joint frame parked per individual, forward-difference Jacobian
+    columns against the frame of the op in front.  As for the free base above, the columns go through the shared acos and the IEEE sqrt: everything bit for bit."""
+    D = 4 + (7 if mid == "floating" else 3) + (3 if with_base else 0)
+    return _multi_variable_joint(make_solver, stage_robot(mid, with_base), "stage", D, 9, n, trajectories)
+
+
+def tool_pose_round_trips(make_solver, m, n, seed, min_rate):
+    """Result level behind the two scenarios above, at 48 steps and on the tool pose alone (the two-goal problem converges slowly: a low-weight goal against
+    dtwist = 1e-5): FK -> IK -> FK on `n` queries, the success rate the oracle's own to 0.03 and above min_rate, every success's pose reproduced under the
+    oracle's FK in the arithmetic it shares with the device."""
+    t1 = ProblemTemplate(m, "whole", [PoseGoal("tool")])
+    h1, o1 = make_solver(t1), orc.Oracle(t1)
+    seeds, params, _ = make_queries(t1, o1.active_variables, o1.fk_genes, n, seed=seed)
+    p = abi.default_solve_params(population=64, max_steps=48, random_seed=3)
+    sol, fit, suc, steps = h1.solve_batch(p, seeds, params)
+    so = o1.solve_batch(p, orc.RNG_COUNTER, seeds, params, n_threads=8)
+    assert suc.mean() >= so[2].mean() - 0.03 and suc.mean() > min_rate
+    assert_poses_reached(o1, sol, suc, params, tip=0, off=0, mode0=False)
+
+
+def balance_goal(make_solver, n, queries, population, max_steps, enough):
+    """BalanceGoal (goal_types.cpp:231-272) on conftest.balance_robot: every link with a URDF mass is a tip (ten of them), and the device accumulates the centre
+    of mass as the chain walk reaches them.  Function level against both oracle arithmetics (the device visits the tips in walk order, the reference in link
+    order: the sums agree to rounding), and `queries` FK -> IK -> FK round trips on pose + balance, of which `enough(success flags)` must have succeeded."""
+    m = balance_robot()
+    for goals in ([PoseGoal("a_tool"), BalanceGoal((0.02, -0.01, 0.0), weight=0.8)], [BalanceGoal((0.0, 0.0, 0.0))],
+                  [BalanceGoal((0.01, 0.0, 0.0)), PoseGoal("b_tool"), AvoidJointLimitsGoal(weight=0.2)]):
+        t = ProblemTemplate(m, "body", goals)
+        h, o = make_solver(t), orc.Oracle(t)
+        assert h.T == o.T >= 10 and np.array_equal(h.tip_links, o.tip_links)
+        for mode in (0, 1):
+            with oracle_arithmetic(mode):
+                function_level(h, o, m, np.random.default_rng(15), n=n, frame_tol=1e-12, fit_rtol=1e-10)
+    t = ProblemTemplate(m, "body", [PoseGoal("a_tool"), BalanceGoal(weight=1.0)])
+    h, o = make_solver(t), orc.Oracle(t)
+    with oracle_arithmetic(0):
+        seeds, params, off = balance_queries(t, o, queries, seed=8)
+    sol, fit, suc, steps = h.solve_batch(abi.default_solve_params(population=population, max_steps=max_steps, random_seed=4), seeds, params)
+    assert enough(suc)
+    assert_poses_reached(o, sol, suc, params)
+    with oracle_arithmetic(0):
+        berr = balance_errors(t, o, sol, params, off)
+    assert berr[suc == 1].max() < POS_TOL
+
+
+def selection_ties_are_decided_by_position(make_solver, monkeypatch, envs, n, steps):
+    """joints without any range: every child of a generation is the same genotype, so every fitness of a generation is the same number and the elitist selection is
+    decided by position alone (ik_evolution_2.cpp:410-431) -- the tie path of the wavefront-minimum top-2 (whole wavefronts) and of the merging butterfly
+    (half-wavefront groups), bit for bit against the oracle, under every lane mapping of `envs` (128 children where one is forced, else 16)"""
+    t = ProblemTemplate(snake(4, limit=0.0), "snake", [PoseGoal("tip")])
+    o = orc.Oracle(t)
+    for env in envs:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        trajectory(make_solver(t), o, t, n=n, pop=128 if env else 16, steps_list=(steps,))
+        for k in env:
+            monkeypatch.delenv(k)
+
+
+def secondary_goals_of_every_kind(make_solver, model, joint_variable_goal, arm, both_arms, function_level_n=None):
+    """Whole solves with five secondary goals at once -- MinimalDisplacementGoal, AvoidJointLimitsGoal, CenterJointsGoal and a RegularizationGoal made secondary
+    (sums over the joint values, whose terms the lanes of the line search share: solve_body's secondary_shared) and, between them in the goals' order, a
+    JointVariableGoal (evaluated lane by lane), which also puts its variable in front of the chains' so that the genes do NOT follow the ops (the sums then run in
+    gene order, as the reference's do: goal_eval_joint_set_x); joint_variable_goal=False: the list without it (the lean kernels).  The oracle's trajectories bit
+    for bit, pre-selection and memetic phase included: `arm` on the seven-joint arm, `both_arms` on both arms with the torso."""
+    reg = RegularizationGoal(weight=0.6)
+    reg.secondary_ = True
+    goals = [MinimalDisplacementGoal(weight=0.7), AvoidJointLimitsGoal(weight=0.3), JointVariableGoal("r_elbow_flex_joint", -1.0, weight=0.5, secondary=True),
+             CenterJointsGoal(weight=0.2), reg]
+    if not joint_variable_goal:
+        goals = [g for g in goals if not isinstance(g, JointVariableGoal)]
+    t = ProblemTemplate(model, "right_arm", [PoseGoal("r_wrist_roll_link")] + goals)
+    h, o = make_solver(t), orc.Oracle(t)
+    if function_level_n:
+        function_level(h, o, model, np.random.default_rng(5), n=function_level_n, exact_bits=True)
+    for kw in arm:
+        trajectory(h, o, t, **kw)
+    t2 = ProblemTemplate(model, "all", [PoseGoal("r_wrist_roll_link"), PoseGoal("l_wrist_roll_link")] + goals)
+    trajectory(make_solver(t2), orc.Oracle(t2), t2, **both_arms)
+
+
 def goal_sets_beyond_one_goal_per_tip(model, make_solver, whole_solves=True):
     """Several goals on one tip, goals on a link in the middle of the chain, several gene-only primary goals, goals that name variables of their own (a
     JointVariableGoal puts its variable in FRONT of the chains' among the active variables, problem.cpp:103-125: the genes then do not follow the ops) -- the
     reference adds goal after goal to one running sum (problem.cpp:244-257) and its sums over the joint values run over the genes in their order.  The device
     evaluates a tip's goals when the walk completes the tip: listed in that order (the links from the root outwards, gene-only goals behind them) the goals give
     the oracle's fitness and trajectories bit for bit; listed otherwise the same terms are added in another order -- the last bit of a fitness may differ."""
-    from bio_ik_amd import (AvoidJointLimitsGoal, CenterJointsGoal, JointVariableGoal, MinimalDisplacementGoal, PoseGoal, PositionGoal, ProblemTemplate,
-                            RegularizationGoal)
     elbow = [PositionGoal("r_elbow_flex_link", weight=0.3), PositionGoal("r_elbow_flex_link", (0.1, 0.2, 0.3), weight=0.2)]
     tail = [RegularizationGoal(weight=0.2), CenterJointsGoal(weight=0.1, secondary=False), MinimalDisplacementGoal(weight=0.3)]
     in_order = {
@@ -213,9 +405,6 @@ def branching_hand(make_solver):
     values, a JointVariableGoal -- listed in walk order: fitness, tables and whole solves bit for bit, every mode, both phenotype models, islands.  With the
     arm's third joint PRISMATIC the tip positions agree to the last bit or two instead (the joint program applies origin and slide as one folded constant
     where the reference concatenates frame by frame)."""
-    from conftest import hand_robot
-    from bio_ik_amd import (AvoidJointLimitsGoal, CenterJointsGoal, JointVariableGoal, LookAtGoal, MinimalDisplacementGoal, OrientationGoal, PoseGoal, PositionGoal,
-                            ProblemTemplate)
     model = hand_robot()
     cases = {
         "three tips": [PositionGoal("f0_tip"), PositionGoal("f1_tip", weight=0.8), PoseGoal("f2_tip", weight=0.5)],
@@ -247,8 +436,6 @@ def exact_joint_program(make_solver, templates):
     fixture, where folding is exact, the two programs give the same bits (through other kernels: the unfolded program is not a serial chain).
     (Until round 5 the GPU suite left the whole solves with LookAtGoal / ConeGoal out: their acos was the device library's.  Since round 6 it is bioik_acos.h's on
     both sides.)"""
-    from conftest import gnarly_goals, gnarly_robot, hand_robot
-    from bio_ik_amd import PoseGoal, PositionGoal, ProblemTemplate
     g = gnarly_robot()
     order = {n: i for i, n in enumerate(g.link_names)}
     goals = gnarly_goals()
@@ -274,7 +461,6 @@ def line_search_on_a_flat_model(make_solver):
     the goals are the case tools/robot_fuzz_hostsim.py met (three links, the last joint turns its link about the link's own origin, so a goal on that link's POSITION
     is flat in it): the literal oracle (quirk mode 1) returns NaN genes with a finite fitness, the default oracle (mode 0) and the device the same finite solves,
     bit for bit.  The caller has set BIOIK_COMPILE_EXACT (the last origin is rotated)."""
-    from bio_ik_amd import LineGoal, MaxDistanceGoal, PositionGoal, ProblemTemplate, RobotModel
     m = RobotModel("flat")
     m.add_link("l0")
     m.add_link("l1", "l0", "j1", "fixed", xyz=(0.2893761985906587, 0.03248937499002066, -0.014841302929549098))
@@ -310,7 +496,6 @@ def line_search_step_without_bound(make_solver):
     7252 of seed 1001): a link on a continuous joint under a ConeGoal without a position term -- acos of a NaN is NaN, max(0, NaN - angle) = 0.  The literal oracle
     (quirk mode 1) returns +-DBL_MAX; the default oracle and the device take such a candidate for none, return the same finite solves bit for bit, and no joint
     value of magnitude 1e300 or more ever leaves the product.  The caller has set BIOIK_COMPILE_EXACT (rotated origins)."""
-    from bio_ik_amd import ConeGoal, ProblemTemplate, RobotModel
     m = RobotModel("unbounded")
     m.add_link("l0")
     m.add_link("l1", "l0", "j1", "continuous", xyz=(0.0, 0.0, 0.0), rpy=(0.0, 0.0, 0.0), axis=(1.0, 0.0, 0.0), velocity=0.5426426563843417)
@@ -359,9 +544,6 @@ def island_selection_three_ways(h, template, monkeypatch, n=3, pop=16, steps=5, 
     """The best island of every query (ik_parallel.h:220-269) three ways -- by the query's last island inside the solve's launch (a wavefront: select_coop), by a
     wavefront per query in a launch of its own (k_select_wave), by a lane per query walking the islands (k_select: the loop that restates the reference) -- on solves
     whose islands pass at different steps, pass not at all (the fallback: least fitness of all), and number more than a wavefront has lanes: the same answer."""
-    from bio_ik_amd import abi
-    from bio_ik_amd.workload import make_queries
-    import numpy as np
     seeds, params, _ = make_queries(template, h.active_variables, h.fk_genes, n, seed=77, kind=kind, noise=noise)
     far = params.copy()
     far[:, 0:3] += 10.0  # out of reach: no island ever passes

@@ -10,16 +10,14 @@ import numpy as np
 import pytest
 
 import parity_cases as pc
-from bio_ik_amd import ProblemTemplate, abi
+from bio_ik_amd import BalanceGoal, JointVariableGoal, MinimalDisplacementGoal, PoseGoal, ProblemTemplate, RobotModel, abi, pr2_like, snake
+from bio_ik_amd.solver import BioIKError, HipSolver, device_count
 from bio_ik_amd.workload import make_queries
-from conftest import gnarly_goals
 from oracle import orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
-
-POS_TOL, ROT_TOL = 1e-4, 1e-3  # north-star tolerance on PoseGoal results [m], [rad]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,9 +29,14 @@ def shared_trigonometry():
 
 @pytest.fixture(scope="module")
 def gpus(templates):
-    from bio_ik_amd.solver import HipSolver, device_count
     assert device_count() >= 1, "no HIP device: the product path has no CPU fallback"
     return {k: HipSolver(t, device=0) for k, t in templates.items()}
+
+
+@pytest.fixture(scope="module")
+def make_solver():
+    """what the cases of parity_cases.py build their solvers with: the product library on device 0"""
+    return lambda t: HipSolver(t, device=0)
 
 
 @pytest.mark.parametrize("cfg", ["c2", "c3", "c4"])
@@ -41,57 +44,24 @@ def test_function_level(gpus, oracles, templates, cfg):
     pc.function_level(gpus[cfg], oracles[cfg], templates[cfg].model, np.random.default_rng(1), n=3000, exact_bits=True)
 
 
-def test_function_level_gnarly(gnarly):
-    from bio_ik_amd.solver import HipSolver
-    t = ProblemTemplate(gnarly, "body", gnarly_goals())
-    pc.function_level(HipSolver(t), orc.Oracle(t), gnarly, np.random.default_rng(2), n=2000)
-    t2 = ProblemTemplate(gnarly, "body", gnarly_goals(), fixed_joints=["lift_joint", "antenna_joint"])
-    pc.function_level(HipSolver(t2), orc.Oracle(t2), gnarly, np.random.default_rng(3), n=2000)
+def test_function_level_gnarly(make_solver, gnarly):
+    """parity_cases.function_level_gnarly on the device"""
+    pc.function_level_gnarly(make_solver, gnarly, n=2000)
 
 
-def test_mimic_of_a_mimic():
-    """a joint that follows a joint that itself follows a gene: resolved to the joint at the end of the chain as MoveIt's RobotModel::buildMimic does; the
-    oracle's trajectories, and the same bits as the robot with the resolution written out by hand"""
-    from bio_ik_amd import PoseGoal
-    from bio_ik_amd.solver import HipSolver
-    from conftest import mimic_robot
-    sols = []
-    for chain in ("chain", "resolved"):
-        m = mimic_robot(chain)
-        t = ProblemTemplate(m, "arm", [PoseGoal("tool")])
-        h, o = HipSolver(t, device=0), orc.Oracle(t)
-        assert h.D == o.D == 4
-        pc.function_level(h, o, m, np.random.default_rng(6), n=40, exact_bits=True)
-        pc.trajectory(h, o, t, n=4, pop=128, steps_list=(3,))
-        seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 64, seed=8)
-        sols.append(h.solve_batch(abi.default_solve_params(population=128, max_steps=24, random_seed=2), seeds, params))
-    assert all(np.array_equal(x, y) for x, y in zip(*sols))
+def test_mimic_of_a_mimic(make_solver):
+    """parity_cases.mimic_of_a_mimic on the device: 64 queries at the full population"""
+    pc.mimic_of_a_mimic(make_solver, dict(n=4, pop=128, steps_list=(3,)), queries=64, population=128, max_steps=24)
 
 
-def test_mimic_joints():
-    """a joint that follows a gene and a joint that follows a joint outside every goal chain (MoveIt mimic joints,
-    forward_kinematics.h:230-246, 623-636): function level, and whole solves bit for bit"""
-    from bio_ik_amd import MinimalDisplacementGoal, PoseGoal, PositionGoal
-    from bio_ik_amd.solver import HipSolver
-    from conftest import mimic_robot
-    m = mimic_robot()
-    sec = MinimalDisplacementGoal(weight=0.5)
-    sec.secondary_ = True
-    t = ProblemTemplate(m, "arm", [PoseGoal("tool"), PositionGoal("finger_r_tip", weight=0.3), sec])
-    h, o = HipSolver(t), orc.Oracle(t)
-    assert h.D == o.D == 5
-    pc.function_level(h, o, m, np.random.default_rng(5), n=500)
-    t2 = ProblemTemplate(m, "arm", [PoseGoal("tool"), sec])
-    h2, o2 = HipSolver(t2), orc.Oracle(t2)
-    pc.function_level(h2, o2, m, np.random.default_rng(6), n=500, exact_bits=True)
-    pc.trajectory(h2, o2, t2, n=16, pop=128, steps_list=(1, 6))
-    pc.trajectory(h2, o2, t2, n=8, pop=70, steps_list=(3,), fk_mode=abi.FK_LINEAR)
+def test_mimic_joints(make_solver):
+    """parity_cases.mimic_joints on the device"""
+    pc.mimic_joints(make_solver, n=500, trajectories=[dict(n=16, pop=128, steps_list=(1, 6)), dict(n=8, pop=70, steps_list=(3,), fk_mode=abi.FK_LINEAR)])
+
 
 def test_urdf_loaded_model_solves_on_the_device():
     """URDF + SRDF text -> bio_ik_amd.urdf.load_urdf -> flat model -> libbioik_hip.so: the device solves on a robot description that
     never went through a hand-built fixture (mimic joints, nested SRDF groups), function level and whole solves against the oracle"""
-    from bio_ik_amd import MinimalDisplacementGoal, PoseGoal
-    from bio_ik_amd.solver import HipSolver
     from bio_ik_amd.urdf import load_urdf
     from test_urdf import SRDF, URDF
     m = load_urdf(URDF, SRDF)
@@ -109,37 +79,12 @@ def test_urdf_loaded_model_solves_on_the_device():
     so = o.solve_batch(p, orc.RNG_COUNTER, seeds[:32], params[:32], n_threads=8)
     assert np.array_equal(so[0], sol[:32]) and np.array_equal(so[2], suc[:32])
     assert suc.mean() > 0.6  # (an arm whose second elbow follows the shoulder, with a secondary goal: about three in four within 64 steps)
-    with pc.oracle_arithmetic(0):
-        perr, rerr = pc.pose_errors(o, sol, params)
-    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+    pc.assert_poses_reached(o, sol, suc, params)
 
 
-def test_balance_goal():
-    """BalanceGoal on the device (goal_types.cpp:231-272): ten links with mass = ten more tips, centre of mass accumulated along the
-    chain walk.  Function level against the reference-pinned oracle arithmetic, and 512 FK -> IK -> FK round trips on pose + balance."""
-    from bio_ik_amd import AvoidJointLimitsGoal, BalanceGoal, PoseGoal
-    from bio_ik_amd.solver import BioIKError, HipSolver
-    from conftest import balance_robot
-    m = balance_robot()
-    for goals in ([PoseGoal("a_tool"), BalanceGoal((0.02, -0.01, 0.0), weight=0.8)], [BalanceGoal((0.0, 0.0, 0.0))],
-                  [BalanceGoal((0.01, 0.0, 0.0)), PoseGoal("b_tool"), AvoidJointLimitsGoal(weight=0.2)]):
-        t = ProblemTemplate(m, "body", goals)
-        h, o = HipSolver(t), orc.Oracle(t)
-        assert h.T == o.T >= 10 and np.array_equal(h.tip_links, o.tip_links)
-        for mode in (0, 1):
-            with pc.oracle_arithmetic(mode):
-                pc.function_level(h, o, m, np.random.default_rng(15), n=1000, frame_tol=1e-12, fit_rtol=1e-10)
-    t = ProblemTemplate(m, "body", [PoseGoal("a_tool"), BalanceGoal(weight=1.0)])
-    h, o = HipSolver(t), orc.Oracle(t)
-    with pc.oracle_arithmetic(0):
-        seeds, params, off = pc.balance_queries(t, o, 512, seed=8)
-    sol, fit, suc, steps = h.solve_batch(abi.default_solve_params(population=128, max_steps=96, random_seed=4), seeds, params)
-    assert suc.mean() > 0.8
-    with pc.oracle_arithmetic(0):
-        perr, rerr = pc.pose_errors(o, sol, params)
-        berr = pc.balance_errors(t, o, sol, params, off)
-    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL and berr[suc == 1].max() < POS_TOL
-    from bio_ik_amd import pr2_like
+def test_balance_goal(make_solver):
+    """parity_cases.balance_goal on the device: 512 round trips; and a model without inertials is refused"""
+    pc.balance_goal(make_solver, n=1000, queries=512, population=128, max_steps=96, enough=lambda suc: suc.mean() > 0.8)
     with pytest.raises(BioIKError) as e:  # a model without inertials cannot carry a BalanceGoal
         HipSolver(ProblemTemplate(pr2_like(), "right_arm", [PoseGoal("r_wrist_roll_link"), BalanceGoal()]))
     assert e.value.code == abi.ERR_INVALID_ARGUMENT
@@ -155,96 +100,34 @@ def test_gradient_descent_and_jacobian_solvers(gpus, oracles, templates, cfg):
             seeds, params, _ = make_queries(t, o.active_variables, o.fk_genes, 2048, seed=17, kind="tracking")
         sol, fit, suc, steps = h.solve_batch(abi.default_solve_params(mode="jac", max_steps=32), seeds, params)
         assert suc.mean() > 0.9
-        with pc.oracle_arithmetic(0):
-            perr, rerr = pc.pose_errors(o, sol, params)
-        assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+        pc.assert_poses_reached(o, sol, suc, params)
 
 
-def test_no_active_variable(pr2):
-    """every joint of the group fixed: D = 0, the solve runs its budget and returns the seed, as the oracle does"""
-    from bio_ik_amd import PoseGoal
-    from bio_ik_amd.solver import HipSolver
-    t0 = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")])
-    names = [pr2.variable_names[v] for v in HipSolver(t0).active_variables]
-    t = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")], fixed_joints=names)
-    h, o = HipSolver(t), orc.Oracle(t)
-    assert h.D == o.D == 0
-    seeds, params = np.tile(pr2.default_positions(), (64, 1)), np.tile(t.pack_params(), (64, 1))
-    for pop, fk in ((16, abi.FK_EXACT), (128, abi.FK_EXACT), (16, abi.FK_LINEAR)):
-        p = abi.default_solve_params(population=pop, max_steps=2, random_seed=1, fk_mode=fk)
-        got, want = h.solve_batch(p, seeds, params), o.solve_batch(p, orc.RNG_COUNTER, seeds, params)
-        assert all(np.array_equal(a, b) for a, b in zip(got, want))
-        assert np.array_equal(got[0], seeds) and not got[2].any()
+def test_no_active_variable(make_solver, pr2):
+    """parity_cases.no_active_variable on the device: 64 rows"""
+    pc.no_active_variable(make_solver, pr2, rows=64)
 
 
-def test_more_than_32_joints():
-    """48 moving joints on one chain: function level and whole solves bit for bit, every lane mapping the launcher picks
-    for 16 / 70 / 128 children per species; 64 active variables are refused"""
-    from bio_ik_amd import AvoidJointLimitsGoal, PoseGoal, snake
-    from bio_ik_amd.solver import BioIKError, HipSolver
-    m = snake(48)
-    t = ProblemTemplate(m, "snake", [PoseGoal("tip"), AvoidJointLimitsGoal()])
-    h, o = HipSolver(t), orc.Oracle(t)
-    assert h.D == o.D == 48
-    pc.function_level(h, o, m, np.random.default_rng(11), n=300, exact_bits=True)
-    pc.trajectory(h, o, t, n=8, pop=16, steps_list=(1, 3))
-    pc.trajectory(h, o, t, n=4, pop=128, steps_list=(2,))
-    pc.trajectory(h, o, t, n=4, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)
-    with pytest.raises(BioIKError):
-        HipSolver(ProblemTemplate(snake(64), "snake", [PoseGoal("tip")]))
+def test_more_than_32_joints(make_solver):
+    """parity_cases.more_than_32_joints on the device: every lane mapping the launcher picks for 16 / 128 / 70 children per species"""
+    pc.more_than_32_joints(make_solver, n=300, trajectories=[dict(n=8, pop=16, steps_list=(1, 3)), dict(n=4, pop=128, steps_list=(2,)),
+                                                              dict(n=4, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)])
 
 
 @pytest.mark.parametrize("mid,with_base", [("planar", False), ("floating", False), ("planar", True)])
-def test_floating_and_planar_joints_anywhere(mid, with_base):
-    """a planar stage / a floating coupling in the MIDDLE of the chain, and two multi-variable joints on one chain (round 5: forward_kinematics.h:120-135,
-    331-354 take them wherever they are).  As for the free base below: the forward-difference Jacobian columns go through acos / sqrt -- since round 6 the
-    shared acos of bioik_acos.h and the IEEE sqrt: everything bit for bit, memetic solves included, plus the result level at 48 steps."""
-    from bio_ik_amd import PoseGoal, PositionGoal
-    from bio_ik_amd.solver import HipSolver
-    from conftest import stage_robot
-    m = stage_robot(mid, with_base)
-    t = ProblemTemplate(m, "whole", [PoseGoal("tool"), PositionGoal("stage", weight=0.2)])
-    h, o = HipSolver(t), orc.Oracle(t)
-    assert h.D == o.D == 4 + (7 if mid == "floating" else 3) + (3 if with_base else 0)
-    pc.function_level(h, o, m, np.random.default_rng(9), n=500, exact_bits=True)
-    pc.trajectory(h, o, t, n=16, pop=128, steps_list=(1, 5), mode="bio2")
-    pc.trajectory(h, o, t, n=8, pop=64, steps_list=(3,))
-    t1 = ProblemTemplate(m, "whole", [PoseGoal("tool")])
-    h1, o1 = HipSolver(t1), orc.Oracle(t1)
-    seeds, params, _ = make_queries(t1, o1.active_variables, o1.fk_genes, 256, seed=22)
-    p = abi.default_solve_params(population=64, max_steps=48, random_seed=3)
-    sol, fit, suc, steps = h1.solve_batch(p, seeds, params)
-    so = o1.solve_batch(p, orc.RNG_COUNTER, seeds, params, n_threads=8)
-    assert suc.mean() >= so[2].mean() - 0.03 and suc.mean() > 0.7  # (the oracle's own rate on this fixture at 48 steps: 0.79 ... 0.9)
-    perr, rerr = pc.pose_errors(o1, sol, params, tip=0, off=0)
-    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+def test_floating_and_planar_joints_anywhere(make_solver, mid, with_base):
+    """parity_cases.floating_and_planar_joints_anywhere on the device, plus the result level at 48 steps"""
+    *_, m = pc.floating_and_planar_joints_anywhere(make_solver, mid, with_base, n=500, trajectories=[
+        dict(n=16, pop=128, steps_list=(1, 5), mode="bio2"), dict(n=8, pop=64, steps_list=(3,))])
+    pc.tool_pose_round_trips(make_solver, m, n=256, seed=22, min_rate=0.7)  # (the oracle's own rate on this fixture at 48 steps: 0.79 ... 0.9)
 
 
 @pytest.mark.parametrize("base", ["floating", "planar"])
-def test_floating_and_planar_joints(base):
-    """a free base in front of the arm (forward_kinematics.h:120-135, 695-726; ik_evolution_2.cpp:203-215, 320-324).  The Jacobian
-    columns of these joints come from a forward difference through acos / sqrt (frame.h:240-259) -- since round 6 the shared acos of
-    bioik_acos.h and the IEEE sqrt: tables and solves bit for bit, memetic solves included, plus the result level at 48 steps."""
-    from bio_ik_amd import PoseGoal, PositionGoal
-    from bio_ik_amd.solver import HipSolver
-    from conftest import mobile_robot
-    m = mobile_robot(base)
-    t = ProblemTemplate(m, "whole", [PoseGoal("tool"), PositionGoal("base", weight=0.2)])
-    h, o = HipSolver(t), orc.Oracle(t)
-    assert h.D == o.D == (10 if base == "floating" else 6)
-    pc.function_level(h, o, m, np.random.default_rng(8), n=500, exact_bits=True)
-    pc.trajectory(h, o, t, n=16, pop=128, steps_list=(1, 5), mode="bio2")
-    pc.trajectory(h, o, t, n=8, pop=64, steps_list=(3,))
-    # result level on the tool pose alone (the two-goal problem converges slowly: a low-weight goal against dtwist = 1e-5)
-    t1 = ProblemTemplate(m, "whole", [PoseGoal("tool")])
-    h1, o1 = HipSolver(t1), orc.Oracle(t1)
-    seeds, params, _ = make_queries(t1, o1.active_variables, o1.fk_genes, 256, seed=21)
-    p = abi.default_solve_params(population=64, max_steps=48, random_seed=3)
-    sol, fit, suc, steps = h1.solve_batch(p, seeds, params)
-    so = o1.solve_batch(p, orc.RNG_COUNTER, seeds, params, n_threads=8)
-    assert suc.mean() >= so[2].mean() - 0.03 and suc.mean() > 0.9
-    perr, rerr = pc.pose_errors(o1, sol, params, tip=0, off=0)
-    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+def test_floating_and_planar_joints(make_solver, base):
+    """parity_cases.floating_and_planar_joints on the device, plus the result level at 48 steps"""
+    *_, m = pc.floating_and_planar_joints(make_solver, base, n=500, trajectories=[
+        dict(n=16, pop=128, steps_list=(1, 5), mode="bio2"), dict(n=8, pop=64, steps_list=(3,))])
+    pc.tool_pose_round_trips(make_solver, m, n=256, seed=21, min_rate=0.9)
 
 
 def test_success_check_near_threshold(gpus, oracles, templates):
@@ -329,9 +212,7 @@ def test_full_batch_c2_result_level(gpus, oracles, templates):
     p = abi.default_solve_params(population=128, max_steps=64, random_seed=1)
     sol, fit, suc, steps = h.solve_batch(p, seeds, params)
     assert suc.mean() >= 0.99
-    with pc.oracle_arithmetic(0):  # ... and the returned poses verified under it
-        perr, rerr = pc.pose_errors(o, sol, params)
-    assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+    pc.assert_poses_reached(o, sol, suc, params)  # ... and the returned poses verified under it
     info = o.robot_info()
     bounded = info[:, 1] != np.finfo(float).max
     assert np.all(sol[:, bounded] >= info[bounded, 3] - 1e-12) and np.all(sol[:, bounded] <= info[bounded, 4] + 1e-12)
@@ -357,9 +238,7 @@ def test_full_batch_c3_c4_result_level(gpus, oracles, templates):
         assert suc.mean() >= min_rate
         off = 0
         for tip in range(h.T):
-            with pc.oracle_arithmetic(0):
-                perr, rerr = pc.pose_errors(o, sol, params, tip=tip, off=off)
-            assert perr[suc == 1].max() < POS_TOL and rerr[suc == 1].max() < ROT_TOL
+            pc.assert_poses_reached(o, sol, suc, params, tip=tip, off=off)
             off += 8
         k = 8
         so = o.solve_batch(p, orc.RNG_COUNTER, seeds[:k], params[:k], n_threads=8)
@@ -385,9 +264,7 @@ def test_full_size_mixed_batch_on_one_gpu(gpus, oracles, templates):
     for (h, p, seeds, params), g, w in zip(blocks, got, want):
         assert all(np.array_equal(a, b) for a, b in zip(g, w))
         assert g[2].mean() > 0.98
-        with pc.oracle_arithmetic(0):
-            perr, rerr = pc.pose_errors(oracles["c2" if h is gpus["c2"] else "c4"], g[0], params)
-        assert perr[g[2] == 1].max() < POS_TOL and rerr[g[2] == 1].max() < ROT_TOL
+        pc.assert_poses_reached(oracles["c2" if h is gpus["c2"] else "c4"], g[0], g[2], params)
 
 
 def test_c5_full_size_on_one_gpu(gpus, oracles, templates):
@@ -413,17 +290,13 @@ def test_c5_full_size_on_one_gpu(gpus, oracles, templates):
         h.set_first_query(0)
         assert all(np.array_equal(a[off:off + win], b) for a, b in zip(g, w)), cfg
         idx = np.random.default_rng(5).choice(n, 4096, replace=False)
-        with pc.oracle_arithmetic(0):
-            perr, rerr = pc.pose_errors(oracles[cfg], g[0][idx], params[idx])
-        ok = g[2][idx] == 1
-        assert perr[ok].max() < POS_TOL and rerr[ok].max() < ROT_TOL
+        pc.assert_poses_reached(oracles[cfg], g[0][idx], g[2][idx], params[idx])
 
 
 def test_solve_batch_multi_two_handles_on_one_gpu(gpus, templates):
     """the C-ABI form of the multi-GPU split (bioik_solve_batch_multi): on this one-GPU box two handles on device 0 take the two shards
     on their own host threads and streams; the result equals the single-handle solve bit for bit, and the caller's device is untouched"""
     import torch
-    from bio_ik_amd.solver import HipSolver
     h, t = gpus["c2"], templates["c2"]
     other = HipSolver(t, device=0)
     seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 4096, seed=77)
@@ -441,7 +314,6 @@ def test_solve_batch_multi_on_distinct_devices(gpus, templates):
     """bioik_solve_batch_multi with one handle per GPU of the node (every visible device): the shards run on different devices and the
     result equals the single-device solve bit for bit.  Skipped on a one-GPU box (the two-handle test above covers the control flow)."""
     import torch
-    from bio_ik_amd.solver import HipSolver, device_count
     nd = device_count()
     if nd < 2:
         pytest.skip("needs at least two HIP devices")
@@ -479,19 +351,10 @@ def test_submit_wait_pipelining_full_size(gpus, templates):
     print("five 4096-query batches: one at a time %.1f ms, pipelined %.1f ms" % (t_sync * 1e3, t_pipe * 1e3))
 
 
-def test_selection_ties_are_decided_by_position(monkeypatch):
-    """joints without any range: every child of a generation has the same fitness, the elitist selection is decided by position alone
-    (ik_evolution_2.cpp:410-431) -- the tie path of the wavefront-minimum top-2 and of the merging butterfly, bit for bit against the oracle"""
-    from bio_ik_amd import PoseGoal, snake
-    from bio_ik_amd.solver import HipSolver
-    t = ProblemTemplate(snake(4, limit=0.0), "snake", [PoseGoal("tip")])
-    o = orc.Oracle(t)
-    for env in ({"BIOIK_SOLVE_THREADS": "128"}, {"BIOIK_SOLVE_THREADS": "256"}, {"BIOIK_SOLVE_THREADS": "64", "BIOIK_SOLVE_SPECIES_PARALLEL": "1"}, {}):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        pc.trajectory(HipSolver(t, device=0), o, t, n=3, pop=128 if env else 16, steps_list=(3,))
-        for k in env:
-            monkeypatch.delenv(k)
+def test_selection_ties_are_decided_by_position(make_solver, monkeypatch):
+    """parity_cases.selection_ties_are_decided_by_position on the device: also two wavefronts per species (256 lanes)"""
+    pc.selection_ties_are_decided_by_position(make_solver, monkeypatch, n=3, steps=3, envs=(
+        {"BIOIK_SOLVE_THREADS": "128"}, {"BIOIK_SOLVE_THREADS": "256"}, {"BIOIK_SOLVE_THREADS": "64", "BIOIK_SOLVE_SPECIES_PARALLEL": "1"}, {}))
 
 
 def test_preselection_by_selection_gives_what_the_sort_gives(gpus, oracles, templates, monkeypatch):
@@ -521,61 +384,40 @@ def test_preselection_by_selection_gives_what_the_sort_gives(gpus, oracles, temp
     monkeypatch.delenv("BIOIK_SOLVE_PRESELECT")
 
 
-def test_secondary_goals_of_every_kind_in_whole_solves(templates):
-    """Five secondary goals at once -- MinimalDisplacementGoal, AvoidJointLimitsGoal, CenterJointsGoal, a RegularizationGoal made secondary (sums over the joint
-    values: the lanes of the line search share their terms, solve_body's secondary_shared) and a JointVariableGoal between them, which also puts its variable
-    in front of the chains' so that the genes do NOT follow the ops (the sums then run in gene order, as the reference's do: goal_eval_joint_set_x) --: the
-    oracle's trajectories bit for bit on the seven-joint arm and on both arms with the torso, and the same without the JointVariableGoal (the lean kernels)"""
-    from bio_ik_amd import AvoidJointLimitsGoal, CenterJointsGoal, JointVariableGoal, MinimalDisplacementGoal, PoseGoal, RegularizationGoal
-    from bio_ik_amd.solver import HipSolver
-    model = templates["c2"].model
-    reg = RegularizationGoal(weight=0.6)
-    reg.secondary_ = True
-    sec = [MinimalDisplacementGoal(weight=0.7), AvoidJointLimitsGoal(weight=0.3), JointVariableGoal("r_elbow_flex_joint", -1.0, weight=0.5, secondary=True),
-           CenterJointsGoal(weight=0.2), reg]
-    for goals in (sec, [g for g in sec if not isinstance(g, JointVariableGoal)]):
-        t = ProblemTemplate(model, "right_arm", [PoseGoal("r_wrist_roll_link")] + goals)
-        h, o = HipSolver(t), orc.Oracle(t)
-        pc.function_level(h, o, model, np.random.default_rng(5), n=500, exact_bits=True)
-        pc.trajectory(h, o, t, n=24, pop=16, steps_list=(6,))
-        pc.trajectory(h, o, t, n=8, pop=128, steps_list=(4,))
-        pc.trajectory(h, o, t, n=8, pop=40, steps_list=(5,), fk_mode=abi.FK_LINEAR)
-        pc.trajectory(h, o, t, n=8, pop=16, steps_list=(6,), mode="bio2_memetic_l")
-        t2 = ProblemTemplate(model, "all", [PoseGoal("r_wrist_roll_link"), PoseGoal("l_wrist_roll_link")] + goals)
-        pc.trajectory(HipSolver(t2), orc.Oracle(t2), t2, n=16, pop=128, steps_list=(4,))
+def test_secondary_goals_of_every_kind_in_whole_solves(make_solver, templates):
+    """parity_cases.secondary_goals_of_every_kind on the device: function level too, and the same without the JointVariableGoal (the lean kernels)"""
+    for joint_variable_goal in (True, False):
+        pc.secondary_goals_of_every_kind(make_solver, templates["c2"].model, joint_variable_goal, function_level_n=500, arm=[
+            dict(n=24, pop=16, steps_list=(6,)), dict(n=8, pop=128, steps_list=(4,)), dict(n=8, pop=40, steps_list=(5,), fk_mode=abi.FK_LINEAR),
+            dict(n=8, pop=16, steps_list=(6,), mode="bio2_memetic_l")], both_arms=dict(n=16, pop=128, steps_list=(4,)))
 
 
-def test_goal_sets_beyond_one_goal_per_tip(templates):
+def test_goal_sets_beyond_one_goal_per_tip(make_solver, templates):
     """parity_cases.goal_sets_beyond_one_goal_per_tip on the device"""
-    from bio_ik_amd.solver import HipSolver
-    pc.goal_sets_beyond_one_goal_per_tip(templates["c2"].model, lambda t: HipSolver(t))
+    pc.goal_sets_beyond_one_goal_per_tip(templates["c2"].model, make_solver)
 
 
-def test_branching_hand():
+def test_branching_hand(make_solver):
     """parity_cases.branching_hand on the device"""
-    from bio_ik_amd.solver import HipSolver
-    pc.branching_hand(lambda t: HipSolver(t))
+    pc.branching_hand(make_solver)
 
 
-def test_exact_joint_program(templates, monkeypatch):
+def test_exact_joint_program(make_solver, templates, monkeypatch):
     """parity_cases.exact_joint_program on the device"""
-    from bio_ik_amd.solver import HipSolver
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.exact_joint_program(lambda t: HipSolver(t), templates)
+    pc.exact_joint_program(make_solver, templates)
 
 
-def test_line_search_step_without_bound(monkeypatch):
+def test_line_search_step_without_bound(make_solver, monkeypatch):
     """parity_cases.line_search_step_without_bound (quirk Q7: the reference's candidate at +-DBL_MAX; no joint value of magnitude 1e300 leaves the product)"""
-    from bio_ik_amd.solver import HipSolver
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.line_search_step_without_bound(lambda t: HipSolver(t))
+    pc.line_search_step_without_bound(make_solver)
 
 
-def test_line_search_on_a_flat_model(monkeypatch):
+def test_line_search_on_a_flat_model(make_solver, monkeypatch):
     """parity_cases.line_search_on_a_flat_model (quirk Q5: the reference's NaN candidate)"""
-    from bio_ik_amd.solver import HipSolver
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.line_search_on_a_flat_model(lambda t: HipSolver(t))
+    pc.line_search_on_a_flat_model(make_solver)
 
 
 def test_four_wavefront_build_of_the_computed_children_kernel(gpus, oracles, templates, monkeypatch):
@@ -651,8 +493,6 @@ def test_measured_mapping_choice_changes_no_result(templates, monkeypatch):
     """bioik_hip.hip: solve_dispatch -- a handle's first chip-filling call under the latency schedule runs once per eligible lane mapping and keeps the fastest;
     whatever it keeps, the answers are those of the rules alone (BIOIK_SOLVE_AUTOTUNE=0), for a problem of BASELINE.json and for one outside every fitted
     threshold (a 12-joint chain, 64 children per species); the device-pointer entry then uses the handle's choice without waiting"""
-    from bio_ik_amd import PoseGoal, snake
-    from bio_ik_amd.solver import HipSolver
     for t, pop in ((templates["c2"], 128), (ProblemTemplate(snake(12), "snake", [PoseGoal("tip")]), 64)):
         p = abi.default_solve_params(population=pop, max_steps=32, random_seed=4)
         monkeypatch.setenv("BIOIK_SOLVE_AUTOTUNE", "0")
@@ -952,8 +792,6 @@ def test_wall_clock_timeout(gpus, templates):
 
 def test_error_conventions(pr2):
     """status codes instead of exceptions/aborts (include/bioik_hip.h)"""
-    from bio_ik_amd import PoseGoal, RobotModel
-    from bio_ik_amd.solver import BioIKError, HipSolver
     m = RobotModel("float")  # a planar joint that mimics another joint: what the device still has no form for (a floating joint behind a moving joint runs since round 5)
     m.add_link("base")
     m.add_link("turret", "base", "yaw", "revolute", axis=(0, 0, 1), lower=-1.0, upper=1.0, velocity=1.0)
@@ -969,7 +807,6 @@ def test_error_conventions(pr2):
     with pytest.raises(BioIKError) as e:
         HipSolver(ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")]), device=99)
     assert e.value.code == abi.ERR_NO_DEVICE
-    from bio_ik_amd import JointVariableGoal
     with pytest.raises(BioIKError) as e:  # variable outside the group: reference ERROR("joint variable not found"), problem.cpp:125
         HipSolver(ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link"), JointVariableGoal("l_elbow_flex_joint", 0.0)]))
     assert e.value.code == abi.ERR_NOT_FOUND

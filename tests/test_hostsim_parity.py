@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 import parity_cases as pc
-from bio_ik_amd import PoseGoal, ProblemTemplate, abi
-from bio_ik_amd.solver import HipSolver
+from bio_ik_amd import MinimalDisplacementGoal, PoseGoal, ProblemTemplate, abi
+from bio_ik_amd.solver import BioIKError, HipSolver
 from bio_ik_amd.workload import make_queries
-from conftest import gnarly_goals
 from oracle import orc
 
 
@@ -54,21 +53,21 @@ def sims(hostsim_lib, templates, oracles):
     return {k: HipSolver(t, lib=hostsim_lib) for k, t in templates.items()}
 
 
+@pytest.fixture(scope="module")
+def make_solver(hostsim_lib):
+    """what the cases of parity_cases.py build their solvers with: the kernel bodies built for the host"""
+    return lambda t: HipSolver(t, lib=hostsim_lib)
+
+
 @pytest.mark.parametrize("cfg", ["c2", "c3", "c4"])
 def test_function_level_bit_exact(sims, oracles, templates, cfg):
     """the fixtures have axis-aligned joint origins, for which folding fixed links into the joint program is exact"""
     pc.function_level(sims[cfg], oracles[cfg], templates[cfg].model, np.random.default_rng(1), n=70, exact_bits=True)
 
 
-def test_function_level_gnarly(hostsim_lib, gnarly):
-    """rotated origins, oblique axes, prismatic joint, branches with parked frames, root tip, all 16 goal opcodes"""
-    t = ProblemTemplate(gnarly, "body", gnarly_goals())
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    pc.function_level(h, o, gnarly, np.random.default_rng(2), n=70)
-    t2 = ProblemTemplate(gnarly, "body", gnarly_goals(), fixed_joints=["lift_joint", "antenna_joint"])
-    h2, o2 = HipSolver(t2, lib=hostsim_lib), orc.Oracle(t2)
-    assert h2.D == 8
-    pc.function_level(h2, o2, gnarly, np.random.default_rng(3), n=70)
+def test_function_level_gnarly(make_solver, gnarly):
+    """parity_cases.function_level_gnarly on the host simulator"""
+    pc.function_level_gnarly(make_solver, gnarly, n=70)
 
 
 def test_success_check_near_threshold(sims, oracles, templates):
@@ -163,7 +162,6 @@ def test_edge_cases(sims, oracles, templates):
     sol, fit, suc, steps = h.solve_batch(p, seeds[:0], params[:0])  # empty batch
     assert sol.shape == (0, h.V)
     # a query that starts at its goal succeeds after the first step
-    from bio_ik_amd.workload import make_queries
     s2, p2, targets = make_queries(t, o.active_variables, o.fk_genes, 2, seed=3)
     s2[:, o.active_variables] = targets
     p = abi.default_solve_params(population=16, max_steps=5)
@@ -171,55 +169,39 @@ def test_edge_cases(sims, oracles, templates):
     assert suc.all() and np.all(steps == 1)
 
 
-
-def test_secondary_goals_of_every_kind_in_whole_solves(hostsim_lib, templates):
-    """Whole solves with five secondary goals at once -- MinimalDisplacementGoal, AvoidJointLimitsGoal, CenterJointsGoal and a RegularizationGoal made secondary
-    (sums over the joint values, whose terms the lanes of the line search share: solve_body's secondary_shared) and, between them in the goals' order, a
-    JointVariableGoal (evaluated lane by lane) -- on the seven-joint arm and on both arms with the torso: the oracle's trajectories bit for bit, pre-selection
-    and memetic phase included, exact and linearised phenotypes, the quadratic and the linear line search"""
-    from bio_ik_amd import AvoidJointLimitsGoal, CenterJointsGoal, JointVariableGoal, MinimalDisplacementGoal, RegularizationGoal
-    model = templates["c2"].model
-    reg = RegularizationGoal(weight=0.6)
-    reg.secondary_ = True
-    sec = [MinimalDisplacementGoal(weight=0.7), AvoidJointLimitsGoal(weight=0.3), JointVariableGoal("r_elbow_flex_joint", -1.0, weight=0.5, secondary=True),
-           CenterJointsGoal(weight=0.2), reg]
-    t = ProblemTemplate(model, "right_arm", [PoseGoal("r_wrist_roll_link")] + sec)
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    pc.trajectory(h, o, t, n=2, pop=16, steps_list=(3,))
-    pc.trajectory(h, o, t, n=1, pop=128, steps_list=(2,))
-    pc.trajectory(h, o, t, n=1, pop=40, steps_list=(2,), fk_mode=abi.FK_LINEAR)
-    pc.trajectory(h, o, t, n=1, pop=16, steps_list=(3,), mode="bio2_memetic_l")
-    t2 = ProblemTemplate(model, "all", [PoseGoal("r_wrist_roll_link"), PoseGoal("l_wrist_roll_link")] + sec)
-    h2, o2 = HipSolver(t2, lib=hostsim_lib), orc.Oracle(t2)
-    pc.trajectory(h2, o2, t2, n=2, pop=128, steps_list=(2,))
+def test_secondary_goals_of_every_kind_in_whole_solves(make_solver, templates):
+    """parity_cases.secondary_goals_of_every_kind on the host simulator: the list with the JointVariableGoal"""
+    pc.secondary_goals_of_every_kind(make_solver, templates["c2"].model, joint_variable_goal=True, arm=[
+        dict(n=2, pop=16, steps_list=(3,)), dict(n=1, pop=128, steps_list=(2,)), dict(n=1, pop=40, steps_list=(2,), fk_mode=abi.FK_LINEAR),
+        dict(n=1, pop=16, steps_list=(3,), mode="bio2_memetic_l")], both_arms=dict(n=2, pop=128, steps_list=(2,)))
 
 
-def test_goal_sets_beyond_one_goal_per_tip(hostsim_lib, templates):
+def test_goal_sets_beyond_one_goal_per_tip(make_solver, templates):
     """parity_cases.goal_sets_beyond_one_goal_per_tip on the host simulator"""
-    pc.goal_sets_beyond_one_goal_per_tip(templates["c2"].model, lambda t: HipSolver(t, lib=hostsim_lib))
+    pc.goal_sets_beyond_one_goal_per_tip(templates["c2"].model, make_solver)
 
 
-def test_branching_hand(hostsim_lib):
+def test_branching_hand(make_solver):
     """parity_cases.branching_hand on the host simulator"""
-    pc.branching_hand(lambda t: HipSolver(t, lib=hostsim_lib))
+    pc.branching_hand(make_solver)
 
 
-def test_exact_joint_program(hostsim_lib, templates, monkeypatch):
+def test_exact_joint_program(make_solver, templates, monkeypatch):
     """parity_cases.exact_joint_program on the host simulator"""
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.exact_joint_program(lambda t: HipSolver(t, lib=hostsim_lib), templates)
+    pc.exact_joint_program(make_solver, templates)
 
 
-def test_line_search_step_without_bound(hostsim_lib, monkeypatch):
+def test_line_search_step_without_bound(make_solver, monkeypatch):
     """parity_cases.line_search_step_without_bound (quirk Q7: the reference's candidate at +-DBL_MAX; no joint value of magnitude 1e300 leaves the product)"""
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.line_search_step_without_bound(lambda t: HipSolver(t, lib=hostsim_lib))
+    pc.line_search_step_without_bound(make_solver)
 
 
-def test_line_search_on_a_flat_model(hostsim_lib, monkeypatch):
+def test_line_search_on_a_flat_model(make_solver, monkeypatch):
     """parity_cases.line_search_on_a_flat_model (quirk Q5: the reference's NaN candidate)"""
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
-    pc.line_search_on_a_flat_model(lambda t: HipSolver(t, lib=hostsim_lib))
+    pc.line_search_on_a_flat_model(make_solver)
 
 
 def test_random_trees_and_goal_lists(hostsim_lib):
@@ -234,65 +216,24 @@ def test_random_trees_and_goal_lists(hostsim_lib):
         assert "0 mismatches" in r.stdout
 
 
-def test_mimic_joints(hostsim_lib):
-    """a joint that follows a gene and a joint that follows a joint outside every goal chain: function level and whole solves"""
-    from bio_ik_amd import MinimalDisplacementGoal, PoseGoal, PositionGoal
-    from conftest import mimic_robot
-    m = mimic_robot()
-    sec = MinimalDisplacementGoal(weight=0.5)
-    sec.secondary_ = True
-    t = ProblemTemplate(m, "arm", [PoseGoal("tool"), PositionGoal("finger_r_tip", weight=0.3), sec])
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    assert h.D == o.D == 5  # s1 s2 e1 w1 w2: the mimic joints and the off-chain finger are not genes
-    pc.function_level(h, o, m, np.random.default_rng(5), n=60)  # 1e-12: the folded prismatic finger rounds differently
-    # whole solves, bit for bit, on the revolute part (the elbow that follows the shoulder)
-    t2 = ProblemTemplate(m, "arm", [PoseGoal("tool"), sec])
-    h2, o2 = HipSolver(t2, lib=hostsim_lib), orc.Oracle(t2)
-    pc.function_level(h2, o2, m, np.random.default_rng(6), n=60, exact_bits=True)
-    pc.trajectory(h2, o2, t2, n=2, pop=16, steps_list=(1, 3))
-    pc.trajectory(h2, o2, t2, n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)
+def test_mimic_joints(make_solver):
+    """parity_cases.mimic_joints on the host simulator"""
+    pc.mimic_joints(make_solver, n=60, trajectories=[dict(n=2, pop=16, steps_list=(1, 3)), dict(n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)])
 
 
-def test_mimic_of_a_mimic(hostsim_lib):
-    """a joint that follows a joint that itself follows a gene (the reference never meets one: MoveIt's RobotModel::buildMimic resolves such chains before
-    bio_ik sees the model; this library does the same wherever a model is built or handed in): the oracle's trajectories, and the same bits as the robot
-    with the resolution written out by hand"""
-    from bio_ik_amd import PoseGoal
-    from conftest import mimic_robot
-    sols = []
-    for chain in ("chain", "resolved"):
-        m = mimic_robot(chain)
-        t = ProblemTemplate(m, "arm", [PoseGoal("tool")])
-        h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-        assert h.D == o.D == 4  # s1 s2 e1 w2
-        pc.function_level(h, o, m, np.random.default_rng(6), n=40, exact_bits=True)
-        pc.trajectory(h, o, t, n=2, pop=16, steps_list=(3,))
-        seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 3, seed=8)
-        sols.append(h.solve_batch(abi.default_solve_params(population=32, max_steps=4, random_seed=2), seeds, params))
-    assert all(np.array_equal(x, y) for x, y in zip(*sols))
+def test_mimic_of_a_mimic(make_solver):
+    """parity_cases.mimic_of_a_mimic on the host simulator: three queries"""
+    pc.mimic_of_a_mimic(make_solver, dict(n=2, pop=16, steps_list=(3,)), queries=3, population=32, max_steps=4)
 
 
-def test_no_active_variable(hostsim_lib, pr2):
-    """every joint of the group fixed (BioIKKinematicsQueryOptions::fixed_joints, problem.cpp:104-114): D = 0, the solve runs its
-    budget and returns the seed, as the oracle does"""
-    from bio_ik_amd import PoseGoal
-    t0 = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")])
-    names = [pr2.variable_names[v] for v in HipSolver(t0, lib=hostsim_lib).active_variables]
-    t = ProblemTemplate(pr2, "right_arm", [PoseGoal("r_wrist_roll_link")], fixed_joints=names)
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    assert h.D == o.D == 0
-    seeds, params = np.tile(pr2.default_positions(), (2, 1)), np.tile(t.pack_params(), (2, 1))
-    for pop, fk in ((16, abi.FK_EXACT), (128, abi.FK_EXACT), (16, abi.FK_LINEAR)):
-        p = abi.default_solve_params(population=pop, max_steps=2, random_seed=1, fk_mode=fk)
-        got, want = h.solve_batch(p, seeds, params), o.solve_batch(p, orc.RNG_COUNTER, seeds, params)
-        assert all(np.array_equal(a, b) for a, b in zip(got, want))
-        assert np.array_equal(got[0], seeds) and not got[2].any()
+def test_no_active_variable(make_solver, pr2):
+    """parity_cases.no_active_variable on the host simulator: two rows"""
+    pc.no_active_variable(make_solver, pr2, rows=2)
 
 
 def test_streamed_fitness(sims, oracles, templates):
     """bioik_stream_fitness_device (genes [unit][D][pop] -> fitness [unit][pop]): odd
     tails, several blocks per unit, a tree with parked branch frames; in the host simulator device pointers are host pointers"""
-    from bio_ik_amd.workload import make_queries
     for cfg, pop, units in (("c2", 128, 2), ("c2", 77, 2), ("c2", 600, 1), ("c3", 130, 2)):
         h, o, t = sims[cfg], oracles[cfg], templates[cfg]
         seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, units, seed=6)
@@ -304,59 +245,25 @@ def test_streamed_fitness(sims, oracles, templates):
             assert np.array_equal(got[u], want), (cfg, pop, u)
 
 
-def test_more_than_32_joints(hostsim_lib):
-    """48 moving joints on one chain (op masks, winner copy and the memetic lanes beyond 32 ops): function level and whole
-    solves bit for bit; 64 active variables are refused (the memetic phase needs lane D of a 64-lane wavefront)."""
-    from bio_ik_amd import AvoidJointLimitsGoal, PoseGoal, snake
-    from bio_ik_amd.solver import BioIKError
-    m = snake(48)
-    t = ProblemTemplate(m, "snake", [PoseGoal("tip"), AvoidJointLimitsGoal()])
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    assert h.D == o.D == 48
-    pc.function_level(h, o, m, np.random.default_rng(11), n=24, exact_bits=True)
-    pc.trajectory(h, o, t, n=2, pop=20, steps_list=(1, 2))
-    pc.trajectory(h, o, t, n=1, pop=70, steps_list=(1,), fk_mode=abi.FK_LINEAR)
-    with pytest.raises(BioIKError):
-        HipSolver(ProblemTemplate(snake(64), "snake", [PoseGoal("tip")]), lib=hostsim_lib)
+def test_more_than_32_joints(make_solver):
+    """parity_cases.more_than_32_joints on the host simulator"""
+    pc.more_than_32_joints(make_solver, n=24, trajectories=[dict(n=2, pop=20, steps_list=(1, 2)), dict(n=1, pop=70, steps_list=(1,), fk_mode=abi.FK_LINEAR)])
 
 
 @pytest.mark.parametrize("base", ["floating", "planar"])
-def test_floating_and_planar_joints(hostsim_lib, base):
-    """a free base in front of the arm: 7 (translation + quaternion) or 3 (x, y, theta) genes for one joint, Jacobian columns by
-    forward difference, quaternion genes renormalised after reproduction (forward_kinematics.h:120-135, 695-726,
-    ik_evolution_2.cpp:203-215, 320-324)"""
-    from bio_ik_amd import PoseGoal, PositionGoal
-    from conftest import mobile_robot
-    m = mobile_robot(base)
-    t = ProblemTemplate(m, "whole", [PoseGoal("tool"), PositionGoal("base", weight=0.2)])
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    assert h.D == o.D == (10 if base == "floating" else 6)
-    pc.function_level(h, o, m, np.random.default_rng(8), n=60, exact_bits=True)
-    pc.trajectory(h, o, t, n=2, pop=16, steps_list=(1, 3))
-    pc.trajectory(h, o, t, n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)
-    monkey = {"BIOIK_SOLVE_THREADS": "128"}
-    os.environ.update(monkey)
-    try:
-        pc.trajectory(h, o, t, n=1, pop=130, steps_list=(2,))
-    finally:
-        for k in monkey:
-            os.environ.pop(k, None)
+def test_floating_and_planar_joints(make_solver, monkeypatch, base):
+    """parity_cases.floating_and_planar_joints on the host simulator, plus 130 children on 128 lanes"""
+    h, o, t, _ = pc.floating_and_planar_joints(make_solver, base, n=60, trajectories=[
+        dict(n=2, pop=16, steps_list=(1, 3)), dict(n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)])
+    monkeypatch.setenv("BIOIK_SOLVE_THREADS", "128")
+    pc.trajectory(h, o, t, n=1, pop=130, steps_list=(2,))
 
 
 @pytest.mark.parametrize("mid,with_base", [("planar", False), ("floating", False), ("planar", True)])
-def test_floating_and_planar_joints_anywhere(hostsim_lib, mid, with_base):
-    """a planar stage / a floating coupling in the MIDDLE of the chain, and two multi-variable joints on one chain (round 5: forward_kinematics.h:120-135,
-    331-354 take them wherever they are): (F_src o C) o J with the joint frame parked per individual, forward-difference Jacobian columns against the
-    frame of the op in front; function level against the oracle, whole solves, the gradient family"""
-    from bio_ik_amd import PoseGoal, PositionGoal
-    from conftest import stage_robot
-    m = stage_robot(mid, with_base)
-    t = ProblemTemplate(m, "whole", [PoseGoal("tool"), PositionGoal("stage", weight=0.2)])
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    assert h.D == o.D == 4 + (7 if mid == "floating" else 3) + (3 if with_base else 0)
-    pc.function_level(h, o, m, np.random.default_rng(9), n=60, exact_bits=True)
-    pc.trajectory(h, o, t, n=2, pop=16, steps_list=(1, 3))
-    pc.trajectory(h, o, t, n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)
+def test_floating_and_planar_joints_anywhere(make_solver, mid, with_base):
+    """parity_cases.floating_and_planar_joints_anywhere on the host simulator, plus the gradient family"""
+    h, o, t, _ = pc.floating_and_planar_joints_anywhere(make_solver, mid, with_base, n=60, trajectories=[
+        dict(n=2, pop=16, steps_list=(1, 3)), dict(n=1, pop=70, steps_list=(2,), fk_mode=abi.FK_LINEAR)])
     pc.trajectory(h, o, t, n=2, pop=8, steps_list=(6,), mode="gd_c")
     pc.trajectory(h, o, t, n=2, pop=8, steps_list=(4,), mode="jac")
 
@@ -365,7 +272,6 @@ def test_wall_clock_timeout(sims, oracles, templates):
     """the caller's timeout (ik_parallel.h:160): every query runs at least one step, then stops when the launch's clock passes the
     budget; a generous timeout changes nothing"""
     h, o, t = sims["c2"], oracles["c2"], templates["c2"]
-    from bio_ik_amd.workload import make_queries
     seeds, params, _ = make_queries(t, o.active_variables, o.fk_genes, 3, seed=9)
     free = h.solve_batch(abi.default_solve_params(population=16, max_steps=6, random_seed=2), seeds, params)
     slack = h.solve_batch(abi.default_solve_params(population=16, max_steps=6, random_seed=2, timeout=3600.0), seeds, params)
@@ -380,7 +286,6 @@ def test_solve_batch_multi_equals_single_handle(hostsim_lib, templates, sims):
     """bioik_solve_batch_multi: three handles of one template (on a node: one per GPU), contiguous shards, one host thread each;
     identical to the single-handle solve, also with a query offset and with fewer queries than handles"""
     t = templates["c2"]
-    from bio_ik_amd.workload import make_queries
     h0 = sims["c2"]
     others = [HipSolver(t, lib=hostsim_lib) for _ in range(2)]
     seeds, params, _ = make_queries(t, h0.active_variables, h0.fk_genes, 7, seed=31)
@@ -393,36 +298,13 @@ def test_solve_batch_multi_equals_single_handle(hostsim_lib, templates, sims):
         got2 = h0.solve_batch_multi(others, p, seeds[:2], params[:2])
         assert all(np.array_equal(a[:2], b) for a, b in zip(want, got2))
     h0.set_first_query(0)
-    from bio_ik_amd.solver import BioIKError
     with pytest.raises(BioIKError):
         h0.solve_batch_multi([sims["c3"]], p, seeds, params)  # another template
 
 
-def test_balance_goal(hostsim_lib):
-    """BalanceGoal (goal_types.cpp:231-272): every link with a URDF mass is a tip; the device accumulates the centre of mass as the
-    walk reaches the tips.  Function level against both oracle arithmetics (the device visits the tips in walk order, the reference in
-    link order: sums agree to rounding), and a small FK -> IK -> FK round trip on pose + balance."""
-    from bio_ik_amd import AvoidJointLimitsGoal, BalanceGoal, PoseGoal
-    from conftest import balance_robot
-    m = balance_robot()
-    for goals in ([PoseGoal("a_tool"), BalanceGoal((0.02, -0.01, 0.0), weight=0.8)], [BalanceGoal((0.0, 0.0, 0.0))],
-                  [BalanceGoal((0.01, 0.0, 0.0)), PoseGoal("b_tool"), AvoidJointLimitsGoal(weight=0.2)]):
-        t = ProblemTemplate(m, "body", goals)
-        h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-        assert h.T == o.T >= 10
-        for mode in (0, 1):
-            with pc.oracle_arithmetic(mode):
-                pc.function_level(h, o, m, np.random.default_rng(15), n=40, frame_tol=1e-12, fit_rtol=1e-10)
-    t = ProblemTemplate(m, "body", [PoseGoal("a_tool"), BalanceGoal(weight=1.0)])
-    h, o = HipSolver(t, lib=hostsim_lib), orc.Oracle(t)
-    with pc.oracle_arithmetic(0):
-        seeds, params, off = pc.balance_queries(t, o, 3, seed=8)
-    sol, fit, suc, steps = h.solve_batch(abi.default_solve_params(population=24, max_steps=80, random_seed=4), seeds, params)
-    assert suc.sum() >= 2
-    with pc.oracle_arithmetic(0):
-        perr, rerr = pc.pose_errors(o, sol, params)
-        berr = pc.balance_errors(t, o, sol, params, off)
-    assert perr[suc == 1].max() < 1e-4 and rerr[suc == 1].max() < 1e-3 and berr[suc == 1].max() < 1e-4
+def test_balance_goal(make_solver):
+    """parity_cases.balance_goal on the host simulator: three round trips"""
+    pc.balance_goal(make_solver, n=40, queries=3, population=24, max_steps=80, enough=lambda suc: suc.sum() >= 2)
 
 
 @pytest.mark.parametrize("cfg", ["c2", "c3", "c4"])
@@ -436,7 +318,6 @@ def test_gradient_descent_and_jacobian_solvers(sims, oracles, templates, cfg):
 def test_submit_wait_pipelining(sims, templates):
     """bioik_solve_batch_submit / _wait (host-simulated kernels): batches kept in flight on the handle's six slots return what the
     synchronous call returns, in any order of waiting, and a seventh submit completes the oldest ticket by itself"""
-    from bio_ik_amd.workload import make_queries
     h, t = sims["c2"], templates["c2"]
     p = abi.default_solve_params(population=16, max_steps=2, random_seed=5)
     batches = []
@@ -462,7 +343,6 @@ def test_throughput_schedule_changes_no_result(sims, oracles, templates):
     with pytest.raises(Exception):
         sims["c2"].solve_batch(abi.default_solve_params(schedule=7), np.zeros((1, sims["c2"].V)), np.zeros((1, sims["c2"].P)))
     # BIOIK_SCHEDULE_AUTO: the asynchronous entry turns to the dense mapping once two solves of the handle are in flight
-    from bio_ik_amd.workload import make_queries
     h, t = sims["c2"], templates["c2"]
     p = abi.default_solve_params(population=128, max_steps=2, random_seed=5, schedule="auto")
     seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 1, seed=300)
@@ -478,8 +358,6 @@ def test_a_helper_that_never_answers_is_an_error_not_a_result(sims, templates, m
     whose helper never answers (BIOIK_SOLVE_DEBUG_FLAGS=1: the helper of species 0 leaves at once) must not go on as if nothing had happened: it sets the call's
     error word (SolveArgs::error), and the host-pointer entries report BIOIK_ERR_HIP instead of handing out the arrays -- the synchronous call, the ticket's wait,
     and the device-pointer entry at the handle's next call.  The reference's boost::barrier cannot time out (ik_parallel.h:64-67)."""
-    from bio_ik_amd.solver import BioIKError
-    from bio_ik_amd.workload import make_queries
     h, t = sims["c2"], templates["c2"]
     seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 1, seed=21)
     p = abi.default_solve_params(population=128, max_steps=2, random_seed=3)
@@ -526,7 +404,6 @@ def test_helper_wavefronts(sims, oracles, templates, monkeypatch):
     monkeypatch.setenv("BIOIK_SOLVE_HELPED", "1024")
     # ... with secondary goals (the main wavefront pre-selects, the helper takes the upper half of the survivors' walks): the 31-joint chain at 512 and at an odd
     # number of children, a 7-joint arm with a MinimalDisplacementGoal at one and two trips per wavefront
-    from bio_ik_amd import MinimalDisplacementGoal, PoseGoal
     pc.trajectory(sims["c4"], oracles["c4"], templates["c4"], n=1, pop=512, steps_list=(2,))
     pc.trajectory(sims["c4"], oracles["c4"], templates["c4"], n=1, pop=150, steps_list=(2,), islands=2)
     ts = ProblemTemplate(templates["c2"].model, "right_arm", [PoseGoal("r_wrist_roll_link"), MinimalDisplacementGoal()])
@@ -666,7 +543,6 @@ def test_islands_that_stop_each_other(sims, oracles, templates, monkeypatch):
     monkeypatch.setenv("BIOIK_SOLVE_TWO_PHASE", "2,5")
     pc.trajectory(sims["c2"], oracles["c2"], templates["c2"], n=6, pop=32, steps_list=(12,), islands=3, island_sync=1, seed=3)
     # the two selection rules do differ: somewhere an island that passes later has the better fitness
-    from bio_ik_amd.workload import make_queries
     h, t = sims["c2"], templates["c2"]
     seeds, params, _ = make_queries(t, h.active_variables, h.fk_genes, 24, seed=3)
     a = h.solve_batch(abi.default_solve_params(population=32, max_steps=16, random_seed=5, islands=3, island_sync=0), seeds, params)
@@ -704,18 +580,7 @@ def test_best_island_three_ways(sims, templates, monkeypatch):
     pc.island_selection_three_ways(sims["c2"], templates["c2"], monkeypatch, n=2, pop=8, steps=4, fk_mode=abi.FK_LINEAR, kind="tracking", noise=0.02, configs=((9, 1, False), (70, 1, True), (66, 0, False)))
 
 
-def test_selection_ties_are_decided_by_position(hostsim_lib, monkeypatch):
-    """joints without any range: every child of a generation is the same genotype, so every fitness of a generation is the same number and
-    the elitist selection is decided by position alone (ik_evolution_2.cpp:410-431) -- the tie path of the wavefront-minimum top-2
-    (whole wavefronts) and of the merging butterfly (half-wavefront groups) against the oracle"""
-    from bio_ik_amd import snake
-    m = snake(4, limit=0.0)
-    t = ProblemTemplate(m, "snake", [PoseGoal("tip")])
-    o = orc.Oracle(t)
-    for env in ({"BIOIK_SOLVE_THREADS": "128"}, {"BIOIK_SOLVE_THREADS": "64", "BIOIK_SOLVE_SPECIES_PARALLEL": "1"}, {}):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        h = HipSolver(t, lib=hostsim_lib)
-        pc.trajectory(h, o, t, n=2, pop=128 if env else 16, steps_list=(2,))
-        for k in env:
-            monkeypatch.delenv(k)
+def test_selection_ties_are_decided_by_position(make_solver, monkeypatch):
+    """parity_cases.selection_ties_are_decided_by_position on the host simulator"""
+    pc.selection_ties_are_decided_by_position(make_solver, monkeypatch, n=2, steps=2, envs=(
+        {"BIOIK_SOLVE_THREADS": "128"}, {"BIOIK_SOLVE_THREADS": "64", "BIOIK_SOLVE_SPECIES_PARALLEL": "1"}, {}))
