@@ -1748,6 +1748,8 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
     API_END
 }
 
+double bioik_sincos_domain(void) { return BIOIK_SINCOS_DOMAIN; }
+
 int bioik_stream_fitness_device(bioik_problem* p, size_t n_units, int population, const double* d_seeds, const double* d_goal_params, const double* d_genes,
                                 double* d_fitness, void* hip_stream) {
     API_BEGIN

@@ -18,7 +18,10 @@
 
 
 #ifndef BIOIK_CANDIDATE_BOUND
-#define BIOIK_CANDIDATE_BOUND 1e300  // a candidate of the memetic line search with a gene of this magnitude or more is no candidate (quirk Q7; the oracle's default mode has the same bound)
+// a candidate of the memetic line search with a gene of this magnitude or more is no candidate (quirk Q7; the oracle's default mode has the same bound): the end of the
+// domain on which the shared sincos is right (bioik_sincos.h).  A joint's half angle is factor x gene / 2, so every angle the solver evaluates lies inside the domain
+// for mimic factors of magnitude up to 2.
+#define BIOIK_CANDIDATE_BOUND BIOIK_SINCOS_DOMAIN
 #endif
 #ifndef BIOIK_COOP_WALKS
 #define BIOIK_COOP_WALKS 1  // single-individual walks of the solver share the joints' trigonometry over the lanes (fk_walk<COOP>); 0: every lane repeats it
@@ -1934,7 +1937,9 @@ BIOIK_DEV void solve_memetic(Frame& F, SpeciesState& S, double*& popS, int rank_
                         // of its error -- the literal reference ACCEPTS the NaN genes and can return them: quirk Q5)
                         // A step without bound -- v / 0 of a model without curvature -- puts a joint WITHOUT limits at its clip range's end, +-DBL_MAX
                         // (robot_info.h:109-113), where the linear model overflows; the literal reference may accept that vector and return it (quirk Q7,
-                        // DESIGN.md section 3).  A candidate with a gene of magnitude 1e300 or more is no candidate either: the search stops.
+                        // DESIGN.md section 3).  A candidate with a gene of magnitude BIOIK_CANDIDATE_BOUND or more is no candidate either: the search stops.  (The bound is
+                        // the end of the shared sincos's domain, 2^47: a rotation is periodic, so a candidate at 1e10 rad is an ordinary pose -- and must be the pose
+                        // the caller's own trigonometry makes of that value; half angle = factor x gene / 2, inside the domain for mimic factors up to 2.)
                         bool nan_here = false;
                         for (int k = gtid; k < n_ops; k += Gw) {
                             const double e = el[k], gv = s_gop[k] * fnorm;

@@ -11,7 +11,19 @@
 // tests/test_oracle_frame.py.  32 instructions on gfx950 against 45 for the three-term reduction with a tail carried through the
 // kernels (1.02 ulp) that it replaces: +3 % chip-wide step rate (profiles/r02_ab_sincos.log).
 // Polynomial coefficients: fdlibm k_sin.c, k_cos.c (Sun Microsystems, 1993).
+//
+// Domain.  Every double gives the same bits on x86-64 and gfx950 (IEEE operations only, the quadrant included); the values are RIGHT for |x| < BIOIK_SINCOS_DOMAIN,
+// the largest power of two up to which the worst absolute error of either component stays within 1.1 x its worst on |x| <= 1e5.  Measured in the host simulator
+// (the device's bits) against long double, itself within 6e-20 of mpmath at 50 digits, 400 000 arguments per binade (python tools/arith_reference.py --sincos-domain):
+//     |x| <= 1e5        1.72e-16   (1.56 ulp of a value in [0.5, 1))
+//     2^17 ... 2^47     1.67e-16 ... 1.76e-16 in every binade (0.97 x ... 1.02 x)
+//     2^47 ... 2^48     2.00e-16   (1.16 x)          2^48 ... 2^49   8.7e-16
+//     2^49 ... 2^50     1.2e-14                      2^50 ... 2^51   4.9e-13
+//     2^51 and beyond   no digit is right (x * 2 / pi no longer rounds to the right integer; from 2^53 on the values leave [-1, 1], at 1e300 they are infinite)
+// Beyond the domain the solver evaluates nothing: BIOIK_CANDIDATE_BOUND (bioik_kernels.h), and the same bound in the test-suite's CPU checker.
 #pragma once
+
+#define BIOIK_SINCOS_DOMAIN 140737488355328.0  // 2^47
 
 #ifndef BIOIK_SINCOS_FN
 #define BIOIK_SINCOS_FN inline
@@ -35,21 +47,31 @@ BIOIK_SINCOS_FN void bioik_sincos(double x, double* sn, double* cs) {
     const double s = __builtin_fma(z * r, ps, r);
     const double pc = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, C6, C5), C4), C3), C2), C1);
     const double c = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
-    const int q = ((int)fn) & 3;
+    // The quadrant, fn mod 4: the low word of fn + 1.5 * 2^52 holds fn's low 32 bits in two's complement (|fn| < 2^51) -- ONE IEEE addition, the same
+    // bits on every target for every double.  (A conversion to int is out of range from |fn| = 2^31 on, a half angle of 3.37e9: undefined in C++, INT_MIN
+    // on x86-64 and a saturated value on gfx950, so the two sides parted and both were wrong.)
+    unsigned w[2];
+    const double shifted = fn + 6755399441055744.0;
+    __builtin_memcpy(w, &shifted, 8);
+#if defined(BIOIK_SINCOS_SIGN_BRANCHES)
+    const unsigned q = w[0] & 3u;
     const double so = (q & 1) ? c : s;
     const double co = (q & 1) ? s : c;
-#if defined(BIOIK_SINCOS_SIGN_BRANCHES)
     *sn = q >= 2 ? -so : so;
     *cs = (q == 1 || q == 2) ? -co : co;
 #else
-    // quadrants 2, 3 negate the sine, quadrants 1, 2 the cosine: bit 1 of q (of q + 1) moved onto the sign bit -- a shift, an and, an
-    // exclusive or on the high word instead of a comparison and a select per value (negation IS the sign flip, for every double)
-    unsigned long long sb, cb;
-    __builtin_memcpy(&sb, &so, 8);
-    __builtin_memcpy(&cb, &co, 8);
-    sb ^= (unsigned long long)(((unsigned)q << 30) & 0x80000000u) << 32;
-    cb ^= (unsigned long long)((((unsigned)q + 1u) << 30) & 0x80000000u) << 32;
-    __builtin_memcpy(sn, &sb, 8);
-    __builtin_memcpy(cs, &cb, 8);
+    // quadrants 2, 3 negate both kernels' values (bit 1 of fn moved onto the sign bit: a shift and one bit operation on each high word; negation IS the
+    // sign flip, for every double); the odd quadrants then take (c, -s) for (s, c): a select per word, the negation in the select
+    const unsigned m1 = (w[0] << 30) & 0x80000000u;
+    const bool odd = (w[0] << 31) != 0u;
+    unsigned sw[2], cw[2];
+    __builtin_memcpy(sw, &s, 8);
+    __builtin_memcpy(cw, &c, 8);
+    sw[1] ^= m1;
+    cw[1] ^= m1;
+    const unsigned so[2] = {odd ? cw[0] : sw[0], odd ? cw[1] : sw[1]};
+    const unsigned co[2] = {odd ? sw[0] : cw[0], odd ? sw[1] ^ 0x80000000u : cw[1]};
+    __builtin_memcpy(sn, so, 8);
+    __builtin_memcpy(cs, co, 8);
 #endif
 }

@@ -28,7 +28,7 @@ EXPORTS = [
     "bioik_problem_param_count", "bioik_problem_variable_count", "bioik_problem_set_first_query", "bioik_solve_batch", "bioik_solve_batch_multi",
     "bioik_solve_batch_device", "bioik_eval_fk", "bioik_eval_fitness", "bioik_eval_approximator", "bioik_eval_reproduce",
     "bioik_eval_check", "bioik_stream_fitness_device", "bioik_solve_batch_submit", "bioik_solve_batch_wait", "bioik_debug_reload_switches", "bioik_eval_arith",
-    "bioik_resolve_islands", "bioik_solve_batch_ranked", "bioik_solve_batch_ranked_device",
+    "bioik_resolve_islands", "bioik_solve_batch_ranked", "bioik_solve_batch_ranked_device", "bioik_sincos_domain",
 ]
 
 
@@ -148,6 +148,13 @@ def eval_arith(op, x, device=0, lib=None):
     if rc != abi.OK:
         raise BioIKError(rc, L.bioik_last_error().decode())
     return out
+
+
+def sincos_domain(lib=None):
+    """bioik_sincos_domain: BIOIK_SINCOS_DOMAIN as library `lib` was compiled with it -- where the shared sincos stops being accurate and the line search stops taking candidates"""
+    L = lib if lib is not None else load_library()
+    L.bioik_sincos_domain.restype = C.c_double
+    return float(L.bioik_sincos_domain())
 
 
 def device_count():

@@ -36,7 +36,9 @@ extern "C" {
 
 #define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_batch_ranked, bioik_solve_batch_ranked_device (the k best distinct islands of every query).
                                6 (round 6): bioik_resolve_islands (the island count BIOIK_ISLANDS_AUTO gives a call of n queries, for callers that shard a request themselves);
-                               a rendezvous time-out inside a workgroup is BIOIK_ERR_HIP for its call; a line-search candidate with a joint value of magnitude >= 1e300 is no candidate.
+                               a rendezvous time-out inside a workgroup is BIOIK_ERR_HIP for its call; a line-search candidate with a joint value of magnitude >= bioik_sincos_domain()
+                               (2^47; 1e300 until the shared sincos had a stated domain) is no candidate: no solve returns such a value for a variable without bounds.  A joint's half angle
+                               is factor x value / 2, so every angle a solve evaluates lies inside the domain for mimic factors of magnitude up to 2.
                                5 (round 5): bioik_solve_params::islands = 0 means BIOIK_ISLANDS_AUTO (versions up to 4 took 0 as 1); `timeout` counts from the call */
 
 /* ---- status codes ------------------------------------------------------------------------- */
@@ -453,6 +455,10 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
  *   7 atan2         y x                                    -> atan2(y, x)             (reference: KDL::Rotation::GetRot -> libm, src/problem.cpp:281-321)
  * Host pointers. */
 int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out);
+
+/* BIOIK_SINCOS_DOMAIN (bio_ik_amd/csrc/bioik_sincos.h), a power of two: the shared sincos gives the same bits on the host and on the device for every double and is
+ * accurate for |x| below this value; a line-search candidate with a joint value of this magnitude or more is no candidate (BIOIK_CANDIDATE_BOUND). */
+double bioik_sincos_domain(void);
 
 /* streamed (unfused) generation: n_units (query,species) populations resident in HBM, layout
  * genes [n_units][D][population] (individual index fastest — coalesced), fitness [n_units][population].

@@ -55,6 +55,8 @@ void orc_shared_sincos(size_t n, const double* x, double* s, double* c) {
 }
 int orc_get_trig_mode(void) { return trig_mode(); }
 unsigned long long orc_debug_unbounded_candidates(void) { return unbounded_candidates().load(); }
+unsigned long long orc_debug_huge_candidates(void) { return huge_candidates().load(); }
+double orc_candidate_bound(void) { return ORC_CANDIDATE_BOUND; }
 void orc_set_quirk_mode(int mode) { quirk_mode() = mode ? 1 : 0; }
 
 void* orc_model_create(const bioik_model_desc* desc) {

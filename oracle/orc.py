@@ -61,10 +61,24 @@ def shared_sincos(x, kind="strict"):
 
 
 def unbounded_candidates(kind="strict"):
-    """how many line-search candidates with a gene of magnitude >= 1e300 the oracle has met so far (quirk Q7, orc_evolution.h)"""
+    """how many line-search candidates with a gene of magnitude >= candidate_bound() the oracle has met so far (quirk Q7, orc_evolution.h)"""
     L = lib(kind)
     L.orc_debug_unbounded_candidates.restype = C.c_ulonglong
     return int(L.orc_debug_unbounded_candidates())
+
+
+def huge_candidates(kind="strict"):
+    """... and how many with a gene of magnitude in [2^32, 1e300): past the int32 quadrant of the sincos as first written, below the bound of that time"""
+    L = lib(kind)
+    L.orc_debug_huge_candidates.restype = C.c_ulonglong
+    return int(L.orc_debug_huge_candidates())
+
+
+def candidate_bound(kind="strict"):
+    """ORC_CANDIDATE_BOUND: BIOIK_SINCOS_DOMAIN as the oracle was compiled with it"""
+    L = lib(kind)
+    L.orc_candidate_bound.restype = C.c_double
+    return float(L.orc_candidate_bound())
 
 
 def set_quirk_mode(mode, kind="strict"):

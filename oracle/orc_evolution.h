@@ -17,7 +17,9 @@
 // Q7 (round 6) the same line search on a model without curvature but with a slope: v / 0 is an INFINITE step, RobotInfo::clip puts a joint WITHOUT limits at
 // +-DBL_MAX (robot_info.h:109-113: clip_max = DBL_MAX), the linear model is evaluated at 1.8e308 and -- where a goal hides the overflow, e.g. the angle of a
 // ConeGoal: acos(NaN) under max(0, .) -- the candidate is accepted: the reference can return a joint value of 1.8e308 (tools/robot_fuzz_hostsim.py: 4 of 8000 random
-// robots).  The device takes a candidate with a gene of magnitude >= 1e300 for no candidate (BIOIK_CANDIDATE_BOUND); quirk_mode 0 does the same, mode 1 is literal.
+// robots).  The device takes a candidate with a gene of magnitude >= 2^47 for no candidate (BIOIK_CANDIDATE_BOUND = BIOIK_SINCOS_DOMAIN, the end of the domain on which the
+// shared sincos is right: a candidate at 1e10 rad is an ordinary pose, and beyond the domain it would be the pose of another angle; a joint's half angle is
+// factor x gene / 2, so the guarantee holds for mimic factors of magnitude up to 2); quirk_mode 0 does the same, mode 1 is literal.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -30,7 +32,10 @@
 #include "orc_rng.h"
 
 #ifndef ORC_CANDIDATE_BOUND
-#define ORC_CANDIDATE_BOUND 1e300  // (bioik_kernels.h: BIOIK_CANDIDATE_BOUND)
+#define ORC_CANDIDATE_BOUND BIOIK_SINCOS_DOMAIN  // (bioik_kernels.h: BIOIK_CANDIDATE_BOUND; bioik_sincos.h through orc_model.h)
+#endif
+#ifndef ORC_CANDIDATE_BOUND_ROUND6
+#define ORC_CANDIDATE_BOUND_ROUND6 1e300  // the bound until the sincos had a stated domain (diagnostics only: huge_candidates)
 #endif
 
 namespace orc {
@@ -95,7 +100,8 @@ struct Evolution2 {
         }
         const double c = model->clip(p, var);
         // (quirk Q7: a step without bound clips a joint WITHOUT limits to +-DBL_MAX, robot_info.h:109-113; the default mode takes a candidate with a gene of
-        // magnitude 1e300 or more for no candidate, as the device does -- mode 1 keeps it and evaluates the linear model there, as the reference does)
+        // magnitude ORC_CANDIDATE_BOUND or more for no candidate, as the device does -- mode 1 keeps it and evaluates the linear model there, as the reference does)
+        if (std::fabs(c) >= 4294967296.0 && std::fabs(c) < ORC_CANDIDATE_BOUND_ROUND6) huge_candidates()++;  // (diagnostics: finite, but its multiple of pi / 2 fits no int32)
         if (std::fabs(c) >= ORC_CANDIDATE_BOUND) {
             unbounded_candidates()++;  // (diagnostics: how often a line search met such a candidate, in either mode)
             if (quirk_mode() == 0) candidate_has_nan = true;

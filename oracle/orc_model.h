@@ -26,9 +26,15 @@ inline int& quirk_mode() {
     static int mode = 0;
     return mode;
 }
-// diagnostics (tests, tools/robot_fuzz_hostsim.py): how many candidates of the memetic line search had a gene of magnitude >= 1e300 -- an infinite step (curvature
-// 0, slope not) on a joint WITHOUT limits, clipped to +-DBL_MAX.  Quirk Q7 (orc_evolution.h): no candidate in the default mode, literal in mode 1.
+// diagnostics (tests, tools/robot_fuzz_hostsim.py): how many candidates of the memetic line search had a gene of magnitude >= ORC_CANDIDATE_BOUND (the end of the shared
+// sincos's domain; until then 1e300) -- e.g. an infinite step (curvature 0, slope not) on a joint WITHOUT limits, clipped to +-DBL_MAX.  Quirk Q7 (orc_evolution.h): no
+// candidate in the default mode, literal in mode 1.
 inline std::atomic<unsigned long long>& unbounded_candidates() {
+    static std::atomic<unsigned long long> n{0};
+    return n;
+}
+// ... and how many had a gene of magnitude in [2^32, 1e300): candidates the earlier bound let through although the quadrant of their half angle fitted no int32
+inline std::atomic<unsigned long long>& huge_candidates() {
     static std::atomic<unsigned long long> n{0};
     return n;
 }

@@ -11,6 +11,7 @@ import pytest
 from bio_ik_amd import (AvoidJointLimitsGoal, BalanceGoal, CenterJointsGoal, ConeGoal, JointVariableGoal, LineGoal, LookAtGoal, MaxDistanceGoal,
                         MinimalDisplacementGoal, OrientationGoal, PoseGoal, PositionGoal, ProblemTemplate, RegularizationGoal, RobotModel, abi, snake)
 from bio_ik_amd.robot import quat_rotate
+from bio_ik_amd import solver
 from bio_ik_amd.solver import BioIKError
 from bio_ik_amd.workload import make_queries
 from conftest import balance_robot, gnarly_goals, gnarly_robot, hand_robot, mimic_robot, mobile_robot, random_configuration, stage_robot
@@ -495,7 +496,8 @@ def line_search_step_without_bound(make_solver):
     hides the overflow the candidate is ACCEPTED: the literal algorithm returns a joint value of 1.8e308.  Here: the case tools/robot_fuzz_hostsim.py met (its robot
     7252 of seed 1001): a link on a continuous joint under a ConeGoal without a position term -- acos of a NaN is NaN, max(0, NaN - angle) = 0.  The literal oracle
     (quirk mode 1) returns +-DBL_MAX; the default oracle and the device take such a candidate for none, return the same finite solves bit for bit, and no joint
-    value of magnitude 1e300 or more ever leaves the product.  The caller has set BIOIK_COMPILE_EXACT (rotated origins)."""
+    value of magnitude BIOIK_SINCOS_DOMAIN or more (the end of the domain on which the shared sincos is right: the candidate bound) ever leaves the product.  The caller
+    has set BIOIK_COMPILE_EXACT (rotated origins)."""
     m = RobotModel("unbounded")
     m.add_link("l0")
     m.add_link("l1", "l0", "j1", "continuous", xyz=(0.0, 0.0, 0.0), rpy=(0.0, 0.0, 0.0), axis=(1.0, 0.0, 0.0), velocity=0.5426426563843417)
@@ -530,14 +532,16 @@ def line_search_step_without_bound(make_solver):
     met = orc.unbounded_candidates()
     want, got = o.solve_batch(p, orc.RNG_COUNTER, seeds, params, n_threads=1), h.solve_batch(p, seeds, params)
     assert orc.unbounded_candidates() > met  # (the default mode met such candidates too -- and dropped them)
-    assert np.isfinite(want[0]).all() and np.abs(want[0]).max() < 1e300
-    assert np.isfinite(got[0]).all() and np.abs(got[0]).max() < 1e300
+    domain = solver.sincos_domain(h.L)
+    assert domain == orc.candidate_bound() and 2.0 ** 40 <= domain <= 2.0 ** 50
+    assert np.isfinite(want[0]).all() and np.abs(want[0]).max() < domain
+    assert np.isfinite(got[0]).all() and np.abs(got[0]).max() < domain
     assert all(np.array_equal(a, b) for a, b in zip(want, got))
-    # ... and over a longer search with more streams: nothing of magnitude 1e300 ever comes back from the device
+    # ... and over a longer search with more streams: nothing of magnitude BIOIK_SINCOS_DOMAIN ever comes back from the device
     seeds, params, _ = make_queries(t, o.active_variables, o.fk_genes, 32, seed=99)
     for mode in ("bio2_memetic", "bio2_memetic_l"):
         sol = h.solve_batch(abi.default_solve_params(population=16, max_steps=12, random_seed=5, mode=mode), seeds, params)[0]
-        assert np.isfinite(sol).all() and np.abs(sol).max() < 1e300
+        assert np.isfinite(sol).all() and np.abs(sol).max() < domain
 
 
 def island_selection_three_ways(h, template, monkeypatch, n=3, pop=16, steps=5, fk_mode=None, kind="global", noise=0.1, configs=((9, 1, False), (64, 1, False), (100, 0, False), (100, 1, True), (70, 1, False))):

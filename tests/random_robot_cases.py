@@ -5,7 +5,9 @@ and the host simulator (tests/test_hostsim_random_robots.py, the same kernel bod
       eval_fk, eval_fitness (exact and linearised), eval_approximator and eval_check, on random configurations and on edge inputs, each against an error
       bound derived from the model stated in `Bounds`;
   (b) whole solves bit for bit against the oracle on goal lists in walk order, spread over modes, populations, islands and the launcher's kernels;
-  (c) the result contract of solves that cannot be bit-compared with anything (default program, goals in any order).
+  (c) the result contract of solves that cannot be bit-compared with anything (default program, goals in any order);
+  (d) joint angles from 1e5 rad to the end of the shared sincos's domain (BIOIK_SINCOS_DOMAIN, read from the library under test) on three small robots: FK, fitness and
+      the success test against long double WITHOUT the `Theta` term of the bounds, FK bit for bit against the oracle under the exact program.
 
 `make_solver(template)` makes a bioik_amd.solver.HipSolver of the library under test; `report` is a limit_cases.Report (BIOIK_SOLVE_REPORT through capfd)."""
 import contextlib
@@ -540,7 +542,7 @@ def whole_solve(case, h, o, plan, report, monkeypatch, n=2, steps=2, nan_ok=True
 def result_contract(case, h, n, rng, stats, islands=1, island_sync=0, steps=12, pop=16):
     """solves under the default program, goals in any order: goals put on their edges (edge_params) for the long-double FK of a random target configuration,
     seeds at random or near the target.  For every row:
-      - inactive variables are the seed's, bit for bit; bounded variables lie within [min, max]; steps in [1, max_steps];
+      - inactive variables are the seed's, bit for bit; bounded variables lie within [min, max], the others within +-BIOIK_SINCOS_DOMAIN; steps in [1, max_steps];
       - fitness is the device's own eval_fitness of the returned solution, bit for bit: the primary term, plus the secondary term where the query
         succeeded and the template has secondary goals (ik_parallel.h:222-246, solve_epilogue) -- or DBL_MAX with solution = seed where nothing improved;
       - it agrees with the long-double cost of the solution within the bound;
@@ -565,6 +567,9 @@ def result_contract(case, h, n, rng, stats, islands=1, island_sync=0, steps=12, 
     genes = sol[:, pr.active]
     inside = ((genes >= lo[pr.active]) & (genes <= hi[pr.active])) | ~pr.bounded
     assert inside.all(), "%s: a bounded variable outside [min, max] at rows %s" % (repr(case), np.nonzero(~inside.all(axis=1))[0][:6])
+    # (a variable without bounds: inside the domain on which the shared sincos is right -- a line-search candidate at or beyond it is no candidate, quirk Q7)
+    domain = solver.sincos_domain(h.L)
+    assert (np.abs(genes[:, ~pr.bounded]) < domain).all(), "%s: a variable without bounds of magnitude >= %g came back" % (repr(case), domain)
     assert ((stp >= 1) & (stp <= steps)).all(), "%s: steps %s outside [1, %d]" % (repr(case), stp, steps)
     has_sec = any(g.isSecondary() for g in t.goals)
     kept = fit == DBL_MAX
@@ -591,6 +596,110 @@ def result_contract(case, h, n, rng, stats, islands=1, island_sync=0, steps=12, 
         if suc[i]:
             check_against(case, h, pr, b, seeds[i], params[i], g1, stats, [sp])
     return int(suc.sum()), int(kept.sum()), int(suc.sum()) if has_sec else 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------------------
+# (d) joint angles up to the end of the sincos's domain
+
+HUGE_ROWS = 64
+
+
+def huge_angle_cases():
+    """One continuous joint; a chain of three continuous joints with oblique axes and rotated origins; that chain with a follower of factor -1.5 behind it; that
+    chain with its middle joint held fixed (an INACTIVE continuous variable on the tip's chain: it keeps the seed's value, which huge_angle_level puts at 1e10).
+    One tip on a fixed link behind the last joint, one PoseGoal on it."""
+    from bio_ik_amd import PoseGoal, RobotModel
+
+    def chain(name, n_joints, follower=False):
+        m = RobotModel(name)
+        m.add_link("l0")
+        spec = [((0.1, 0.05, 0.2), (0.3, -0.2, 0.5), (0.3, -0.5, 0.8)), ((0.25, -0.1, 0.05), (-0.4, 0.7, 0.1), (-0.6, 0.2, 0.7)), ((0.05, 0.2, -0.15), (0.9, 0.1, -0.6), (0.5, 0.7, -0.4))]
+        joints = []
+        for k in range(n_joints):
+            m.add_link("l%d" % (k + 1), "l%d" % k, "j%d" % (k + 1), "continuous", xyz=spec[k][0], rpy=spec[k][1], axis=spec[k][2], velocity=1.0 + k)
+            joints.append("j%d" % (k + 1))
+        last = "l%d" % n_joints
+        if follower:  # (offset 0: the follower's angle, -1.5 x the leader's, is then a double wherever the leader's last two mantissa bits are clear)
+            m.add_link("lf", last, "jf", "continuous", xyz=(0.1, -0.05, 0.1), rpy=(0.2, 0.3, -0.7), axis=(0.1, -0.9, 0.4), velocity=2.0, mimic=("j2", -1.5, 0.0))
+            joints.append("jf")
+            last = "lf"
+        m.add_link("tool", last, "tool_joint", "fixed", xyz=(0.15, -0.1, 0.2), rpy=(0.3, 0.3, 0.3))
+        m.add_group("g", joints=joints, tips=["tool"])
+        return m, joints
+
+    out = []
+    for k, (name, n_joints, follower, fixed) in enumerate((("turn1", 1, False, []), ("turn3", 3, False, []), ("turn3_follower", 3, True, []), ("turn3_held", 3, False, ["j2"]))):
+        m, joints = chain(name, n_joints, follower)
+        goals = [PoseGoal("tool", (0.3, -0.2, 0.5), (0.1, -0.3, 0.2, 0.9))]
+        out.append(robot_gen.Case(9000 + k, m, joints, [m.link_index("tool")], goals, fixed, True, None))
+    return out
+
+
+def huge_angles(rng, domain, shape):
+    """log-uniform in 1e5 ... the domain, both signs, the last two mantissa bits clear (so that -1.5 x the value, a follower's angle, is a double also where it
+    falls into the next binade: the comparison is about the sincos, not about an argument that either side has rounded); the first rows: 6.8e9 and 2e10, whose half angles lie just past 2^31 pi / 2 = 3.37e9"""
+    x = np.exp(rng.uniform(np.log(1e5), np.log(domain), shape)) * rng.choice([-1.0, 1.0], shape)
+    x = np.minimum(np.abs(x), np.nextafter(domain, 0.0)) * np.sign(x)
+    x[0], x[1], x[2], x[3] = 6.8e9, 2e10, -6.8e9, -2e10
+    x = (x.view(np.uint64) & ~np.uint64(3)).view(np.float64)
+    assert np.all((np.abs(x) >= 1e5) & (np.abs(x) < domain))
+    return x
+
+
+def huge_angle_level(case, h, o, stats, exact):
+    """eval_fk, eval_fitness and eval_check of handle h at HUGE_ROWS configurations whose continuous joints stand at 1e5 ... BIOIK_SINCOS_DOMAIN rad, against long
+    double to C u (m + 1) Lambda: the bounds of `Bounds` WITHOUT the Theta term, which is vacuous here (u |theta| is 1e-2 at 1e14) -- the measured error of the
+    shared sincos is absolute and flat over its domain (bioik_sincos.h), and a half angle theta / 2 is exact.  Under the exact program eval_fk is the oracle's
+    (arithmetic mode 1) bit for bit."""
+    t = h.template
+    m = case.model
+    pr = np_goals.Problem(t, h.active_variables, h.tip_links)
+    domain = solver.sincos_domain(h.L)
+    rng = np.random.default_rng(case.seed)
+    seed = robot_gen.sample_configurations(m, rng, 1)[0]
+    inactive = np.setdiff1d(np.arange(m.n_variables), pr.active)
+    seed[inactive] = 1e10  # (every variable of these robots is a continuous joint's: the held joint's stays, a follower's is overwritten by its leader's)
+    genes = huge_angles(rng, domain, (HUGE_ROWS, len(pr.active)))
+    tag = repr(case) + (" exact" if exact else " folded")
+    b = Bounds(pr, pr.full(seed, genes).astype(np.float64))
+    assert all(np.all(th >= 1e5 / np.pi) for th in b.theta.values())  # (what the Theta term would have allowed: 1e5 and more times the bound below)
+    b.theta = {l: np.zeros(HUGE_ROWS) for l in b.theta}
+    R, p = pr.frames(seed, genes)
+    dev = device_frames(h, seed, genes)
+    for l in set(pr.tips):
+        ep = np.linalg.norm(dev[l][0] - np.asarray(p[l], dtype=np.float64), axis=1)
+        qr = quat_from_rot_batch(R[l])
+        qd = np.asarray(dev[l][1], dtype=LD)
+        eq = np.asarray(np.minimum(np.linalg.norm(qd - qr, axis=1), np.linalg.norm(qd + qr, axis=1)), dtype=np.float64)
+        for what, err, bound in (("huge_fk_p", ep, b.dp(l)), ("huge_fk_q", eq, b.dq(l))):
+            r = stats.ratio(what, err, bound, tag)
+            i = int(np.argmax(err / bound))
+            assert r <= 1.0, "%s: %s off by %.3g, bound %.3g (ratio %.3g) at row %d, genes %s" % (tag, what, err[i], bound[i], r, i, genes[i])
+    if exact:
+        want = o.fk_genes(seed, genes)
+        got = h.fk_genes(seed, genes)
+        differ = np.nonzero((want != got).any(axis=(1, 2)))[0]
+        assert differ.size == 0, "%s: eval_fk differs from the oracle at rows %s, genes %s: oracle %s, device %s" % (tag, differ[:6], genes[differ[0]], want[differ[0]], got[differ[0]])
+    # the PoseGoal on the pose of row 0 (so that one row passes the success test), every row's cost and success decision
+    params = edge_params(case, pr, t.pack_params(), seed, genes[0], rng)
+    fitness_against(case, h, pr, b, seed, params, genes, (R, p), stats, "huge_cost")
+    before = stats.rows
+    check_against(case, h, pr, b, seed, params, genes, stats, [solve_params(), solve_params(dpos=0.05, drot=5.0, dtwist=-1.0)])
+    assert stats.rows == before + 2 * HUGE_ROWS
+    ok = pr.check(seed, params, genes, *thresholds(solve_params(dpos=0.05, drot=5.0, dtwist=-1.0)), frames=(R, p))[0]
+    assert ok[0] and not ok.all()
+
+
+def huge_angle_levels(case, make_solver, stats):
+    """(d) under both joint programs"""
+    for exact in (False, True):
+        with program(exact):
+            made = make_or_refuse(case, make_solver)
+        assert made is not None, repr(case)
+        h, o = made
+        assert np.array_equal(h.active_variables, o.active_variables) and np.array_equal(h.tip_links, o.tip_links), repr(case)
+        assert (len(h.active_variables) < case.model.n_variables) == bool(case.fixed or "jf" in case.joints), repr(case)
+        huge_angle_level(case, h, o, stats, exact)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------------------------

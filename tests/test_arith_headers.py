@@ -4,12 +4,18 @@ The kernels are bit-identical to the CPU checker only in the checker's "device a
 headers itself: a defect in them would be invisible to every bit-parity test.  Here each function is evaluated where it runs in production (on the
 device through `bioik_eval_arith`; without a GPU: the same sources in the host simulator) for a large set of arguments and compared with
 
-  * `mpmath` at 50 digits (a sample; tools/arith_reference.py is the generating script: nothing is stored, the references are computed at test time),
+  * `mpmath` at 50 digits (a sample; tools/arith_reference.py is the generating script: no reference value is stored, they are computed at test time),
   * NumPy long double (64-bit mantissa, the bulk), whose own agreement with mpmath is asserted first,
 
 with the error bounds asserted in ulps (sincos: the 1.56 ulp its header documents, SURVEY.md section 8(c) function level) or in units of
 eps x the sum of the magnitudes of the terms (the fused dot / cross / Hamilton products: each result is a sum of products rounded a few times).
-The sparse forms of a revolute joint (bioik_device.h: revolute_apply) must equal the general form wherever the struck-out constants are zeros."""
+The sparse forms of a revolute joint (bioik_device.h: revolute_apply) must equal the general form wherever the struck-out constants are zeros.
+
+sincos beyond the few radians of an ordinary joint: the header states a domain (BIOIK_SINCOS_DOMAIN, read from the library under test: solver.sincos_domain) on which its
+values are right -- the quadrant where the multiple of pi / 2 fits no int32 (`_check_sincos_quadrants`), the absolute error binade by binade up to the domain's end
+(`_check_sincos_domain`) -- and promises the same bits on the host and on the device for EVERY double, beyond the domain too (the bit-for-bit test at the end).
+tests/golden/sincos_bits.npz holds the bits of 4096 arguments as the header gave them before its quadrant came from an addition (`_check_sincos_golden`): nothing moved where
+it was right, which no oracle-parity test can see (the oracle shares the header)."""
 import os
 import sys
 
@@ -52,6 +58,61 @@ def _check_sincos(ev, n):
     ulp_s, ulp_c = np.spacing(np.abs(ms.astype(np.float64))), np.spacing(np.abs(mc.astype(np.float64)))
     assert np.all(np.abs(out[:, 0].astype(np.longdouble) - ms) <= 1.6 * ulp_s + 1e-32 * (np.abs(xm) + 1.0))
     assert np.all(np.abs(out[:, 1].astype(np.longdouble) - mc) <= 1.6 * ulp_c + 1e-32 * (np.abs(xm) + 1.0))
+    return worst
+
+
+# The absolute error allowed on the whole domain: 1.1 x the worst on |x| <= 1e5, which is the header's documented 1.56 ulp of a value in [0.5, 1) (ulp = 2^-53 there,
+# EPS of this file): 1.72e-16 measured, 1.73e-16 by that figure.  BIOIK_SINCOS_DOMAIN is defined as the largest power of two below which the error stays within this.
+SINCOS_DOMAIN_BOUND = 1.1 * 1.56 * EPS
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", ar.GOLDEN_SINCOS)
+
+
+def _check_sincos_golden(ev):
+    """the recorded bits (tests/golden/sincos_bits.npz: random over +-4, +-100, +-1e5, +-3.3e9 and the special arguments), exactly"""
+    d = np.load(GOLDEN)
+    x = d["x"].view(np.float64)
+    assert x.shape == (4096,) and np.array_equal(x, ar.sincos_golden_arguments())
+    out = ev(0, x)
+    for k, name in ((0, "sin"), (1, "cos")):
+        got = np.ascontiguousarray(out[:, k]).view(np.uint64)
+        bad = np.nonzero(got != d[name])[0]
+        assert bad.size == 0, "%s: %d of 4096 recorded results moved, first at x = %r" % (name, bad.size, float(x[bad[0]]))
+
+
+def _check_sincos_quadrants(ev, domain):
+    """arguments whose multiple of pi / 2 fits no int32 (from |x| = 3.37e9 on): the right component with the right sign, against mpmath at 50 digits"""
+    x = ar.sincos_quadrant_arguments(domain)
+    assert np.all(np.abs(x) < domain) and np.sum(np.abs(x) > 3.3e9) >= 20
+    out = ev(0, x)
+    ms, mc = ar.sincos_mpmath(x)
+    for got, ref, name in ((out[:, 0], ms, "sin"), (out[:, 1], mc, "cos")):
+        err = np.abs(got.astype(np.longdouble) - ref)
+        i = int(np.argmax(err))
+        assert err[i] <= SINCOS_DOMAIN_BOUND, "%s(%r) = %r, mpmath %r" % (name, float(x[i]), float(got[i]), float(ref[i]))
+        big = np.abs(ref) > 1e-3  # (a sign is a statement about a value that is not a rounding error itself)
+        assert np.array_equal(np.signbit(got[big]), np.signbit(ref[big].astype(np.float64)))
+
+
+def _check_sincos_domain(ev, domain, n):
+    """binade by binade from 2^17 to the domain's end: n random arguments and the neighbours of 64 multiples of pi / 2 each, against long double (held against mpmath
+    at 50 digits on a sample of every binade first)"""
+    worst = 0.0
+    binades = ar.sincos_domain_arguments(domain, n, 20261018)
+    assert binades[0][0] == 17 and 2.0 ** (binades[-1][0] + 1) == domain
+    for e, x in binades:
+        assert np.all((np.abs(x) >= np.nextafter(2.0 ** e, 0.0)) & (np.abs(x) < domain))
+        xm = np.concatenate([x[:40], x[-40:]])
+        ls, lc = ar.sincos_longdouble(xm)
+        ms, mc = ar.sincos_mpmath(xm)
+        assert float(np.max(np.abs(ls - ms))) < 2e-19 and float(np.max(np.abs(lc - mc))) < 2e-19
+        out = ev(0, x)
+        rs, rc = ar.sincos_longdouble(x)
+        for got, ref, name in ((out[:, 0], rs, "sin"), (out[:, 1], rc, "cos")):
+            err = np.abs(got.astype(np.longdouble) - ref)
+            i = int(np.argmax(err))
+            worst = max(worst, float(err[i]))
+            assert err[i] <= SINCOS_DOMAIN_BOUND, "2^%d: %s(%r) off by %.3g (bound %.3g)" % (e, name, float(x[i]), float(err[i]), SINCOS_DOMAIN_BOUND)
+        assert np.all(np.abs(out[:, 0] ** 2 + out[:, 1] ** 2 - 1.0) < 8 * EPS), "2^%d: not a rotation" % e
     return worst
 
 
@@ -136,6 +197,41 @@ def test_shared_arithmetic_headers_in_the_host_simulator(hostsim_lib):
     _check_acos_atan2(ev, 40000)
 
 
+def test_sincos_domain_is_one_constant(hostsim_lib):
+    """BIOIK_SINCOS_DOMAIN as the host simulator and the oracle were compiled with it: a power of two, and the oracle's candidate bound"""
+    from oracle import orc
+    domain = solver.sincos_domain(hostsim_lib)
+    assert domain == orc.candidate_bound() and np.frexp(domain)[0] == 0.5 and 2.0 ** 40 <= domain <= 2.0 ** 50
+
+
+def test_sincos_golden_bits_in_the_host_simulator(hostsim_lib):
+    _check_sincos_golden(lambda op, x: solver.eval_arith(op, x, lib=hostsim_lib))
+
+
+def test_sincos_quadrants_in_the_host_simulator(hostsim_lib):
+    _check_sincos_quadrants(lambda op, x: solver.eval_arith(op, x, lib=hostsim_lib), solver.sincos_domain(hostsim_lib))
+
+
+def test_sincos_over_its_domain_in_the_host_simulator(hostsim_lib):
+    _check_sincos_domain(lambda op, x: solver.eval_arith(op, x, lib=hostsim_lib), solver.sincos_domain(hostsim_lib), 10000)
+
+
+@pytest.mark.gpu
+def test_sincos_golden_bits_on_the_device():
+    _check_sincos_golden(solver.eval_arith)
+
+
+@pytest.mark.gpu
+def test_sincos_quadrants_on_the_device():
+    _check_sincos_quadrants(solver.eval_arith, solver.sincos_domain())
+
+
+@pytest.mark.gpu
+def test_sincos_over_its_domain_on_the_device():
+    worst = _check_sincos_domain(solver.eval_arith, solver.sincos_domain(), 100000)
+    print("sincos worst absolute error from 2^17 to the domain's end %.3g (bound %.3g)" % (worst, SINCOS_DOMAIN_BOUND))
+
+
 @pytest.mark.gpu
 def test_shared_arithmetic_headers_on_the_device():
     """the same on gfx950, a million arguments per function"""
@@ -153,6 +249,17 @@ def test_device_and_host_simulator_agree_bit_for_bit(hostsim_lib):
     rng = np.random.default_rng(3)
     x = rng.uniform(-50.0, 50.0, 200000)
     assert np.array_equal(solver.eval_arith(0, x), solver.eval_arith(0, x, lib=hostsim_lib))
+    # ... and for EVERY double, not only where the values mean something: log-uniform over 1e-308 ... DBL_MAX in both signs, both sides of +-2^31 pi / 2 and +-2^32 pi / 2
+    # (where a conversion of the multiple to int32 / uint32 leaves its range), subnormals, +-0, +-DBL_MAX.  Beyond the domain the values are garbage: the SAME garbage.
+    assert solver.sincos_domain() == solver.sincos_domain(hostsim_lib)
+    xe = ar.sincos_every_double_arguments()
+    assert xe.size >= 200000 and np.sum(np.abs(xe) >= solver.sincos_domain()) > 80000 and np.all(np.isfinite(xe))
+    dev, host = solver.eval_arith(0, xe), solver.eval_arith(0, xe, lib=hostsim_lib)
+    differ = np.nonzero(dev.view(np.uint64) != host.view(np.uint64))[0]
+    assert differ.size == 0, "sincos(%r): device %s, host simulator %s" % (float(xe[differ[0]]), dev[differ[0]], host[differ[0]])
+    xn = np.array([np.inf, -np.inf, np.nan])
+    dev, host = solver.eval_arith(0, xn), solver.eval_arith(0, xn, lib=hostsim_lib)
+    assert np.all(np.isnan(dev)) and np.all(np.isnan(host)) and np.array_equal(dev, host, equal_nan=True)
     for op, w in ((1, 7), (2, 8), (3, 6), (4, 8)):
         y = rng.normal(size=(100000, w))
         assert np.array_equal(solver.eval_arith(op, y), solver.eval_arith(op, y, lib=hostsim_lib))

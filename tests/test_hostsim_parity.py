@@ -193,7 +193,7 @@ def test_exact_joint_program(make_solver, templates, monkeypatch):
 
 
 def test_line_search_step_without_bound(make_solver, monkeypatch):
-    """parity_cases.line_search_step_without_bound (quirk Q7: the reference's candidate at +-DBL_MAX; no joint value of magnitude 1e300 leaves the product)"""
+    """parity_cases.line_search_step_without_bound (quirk Q7: the reference's candidate at +-DBL_MAX; no joint value of magnitude BIOIK_SINCOS_DOMAIN or more leaves the product)"""
     monkeypatch.setenv("BIOIK_COMPILE_EXACT", "1")
     pc.line_search_step_without_bound(make_solver)
 

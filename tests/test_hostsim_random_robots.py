@@ -52,6 +52,15 @@ def test_whole_solves_bit_for_bit(hostsim_lib, monkeypatch, capfd):
     assert "k_solve" in ran_multi
 
 
+def test_huge_joint_angles(hostsim_lib):
+    """(d) of random_robot_cases: joint angles from 1e5 rad to the end of the shared sincos's domain"""
+    stats = rc.Stats()
+    for case in rc.huge_angle_cases():
+        rc.huge_angle_levels(case, lambda t: HipSolver(t, lib=hostsim_lib), stats)
+    print(stats.line())
+    assert stats.rows == 4 * 2 * 2 * rc.HUGE_ROWS
+
+
 @pytest.mark.parametrize("islands,sync", [(1, 0), (3, 1)])
 def test_result_contract(hostsim_lib, islands, sync):
     stats = rc.Stats()

@@ -1,10 +1,12 @@
 """Independent references for the shared arithmetic headers (bio_ik_amd/csrc/bioik_sincos.h, bioik_fused.h, bioik_acos.h): NumPy long double (x87 80-bit: 64-bit
 mantissa) for bulk comparisons and mpmath (50 digits) to validate the long double values themselves.  Used by tests/test_arith_headers.py at test time
-(nothing is stored); `python tools/arith_reference.py` prints the agreement of the two references.  Written from the mathematical definitions
-(frame.h:108-172 of the reference for the quaternion algebra), not from the headers under test."""
+(no reference value is stored); `python tools/arith_reference.py` prints the agreement of the two references, and with `--sincos-domain LIBRARY` the table behind
+BIOIK_SINCOS_DOMAIN.  Written from the mathematical definitions (frame.h:108-172 of the reference for the quaternion algebra), not from the headers under test.
+The one stored file, tests/golden/sincos_bits.npz, holds no reference but the header's OWN bits at 4096 arguments (write_sincos_golden), to pin that they do not move."""
 import numpy as np
 
 LD = np.longdouble
+PIO2_LD = (LD(np.pi) + LD(1.2246467991473532e-16)) / 2  # pi / 2 to long double precision: fl(pi) and the double behind it
 
 
 def sincos_special_arguments():
@@ -12,6 +14,71 @@ def sincos_special_arguments():
     base = np.concatenate([k * (np.pi / 4), k * (np.pi / 2)])
     near = np.concatenate([base, np.nextafter(base, np.inf), np.nextafter(base, -np.inf), base + 1e-9, base - 1e-9])
     return np.concatenate([near, [0.0, -0.0, 1e-300, -1e-300, 1e-8, 0.5, 1.0, 2.0, 3.0, 1e4 + 0.1]])
+
+
+GOLDEN_SINCOS = "sincos_bits.npz"  # under tests/golden
+
+
+def sincos_golden_arguments():
+    """the 4096 fixed arguments of tests/golden/sincos_bits.npz: random over +-4, +-100, +-1e5 and +-3.3e9 (below 2^31 pi / 2, where the quadrant of the header as
+    first written was right on every target), and the special arguments"""
+    rng = np.random.default_rng(20261018)
+    special = sincos_special_arguments()
+    n = (4096 - len(special)) // 4
+    xs = [rng.uniform(-a, a, n) for a in (4.0, 100.0, 1e5)] + [rng.uniform(-3.3e9, 3.3e9, 4096 - len(special) - 3 * n), special]
+    return np.concatenate(xs)
+
+
+def write_sincos_golden(path, ev):
+    """record the bits ev(0, x) gives on the golden arguments (run ONCE, on the commit before bioik_sincos.h took its quadrant from an addition: the file pins
+    that the header's bits did not move where they were right)"""
+    x = sincos_golden_arguments()
+    out = np.ascontiguousarray(ev(0, x))
+    np.savez(path, x=x.view(np.uint64), sin=np.ascontiguousarray(out[:, 0]).view(np.uint64), cos=np.ascontiguousarray(out[:, 1]).view(np.uint64))
+
+
+def sincos_quadrant_arguments(domain):
+    """arguments whose multiple of pi / 2 does not fit an int32: 3.4e9, +-1e10, 1e12, 1e15 (clipped to the domain) and fl(k pi / 2) for k around 2^31 and 2^40, both signs"""
+    k = np.array([2.0 ** 31 + d for d in (-2, -1, 0, 1, 2)] + [2.0 ** 40 - 1, 2.0 ** 40 + 1])
+    a = np.concatenate([[3.4e9, 1e10, 1e12, 1e15], (k.astype(LD) * PIO2_LD).astype(np.float64)])
+    a = np.minimum(a, np.nextafter(domain, 0.0))
+    return np.concatenate([a, -a])
+
+
+def sincos_domain_arguments(domain, n, seed, lo=2.0 ** 17, n_multiples=64):
+    """per binade from lo to the domain end: n random arguments of both signs and the neighbours (nextafter both ways, and itself) of fl(k pi / 2) for n_multiples
+    random k of that binade; returns [(binade exponent, arguments)]"""
+    rng = np.random.default_rng(seed)
+    out = []
+    e = int(np.log2(lo))
+    while 2.0 ** e < domain:
+        a, b = 2.0 ** e, min(2.0 ** (e + 1), domain)
+        x = rng.uniform(a, b, n) * rng.choice([-1.0, 1.0], n)
+        k = np.floor(rng.uniform(a, b, n_multiples) / (np.pi / 2))
+        m = (k.astype(LD) * PIO2_LD).astype(np.float64) * rng.choice([-1.0, 1.0], n_multiples)
+        m = np.concatenate([m, np.nextafter(m, np.inf), np.nextafter(m, -np.inf)])
+        out.append((e, np.concatenate([x, m[np.abs(m) < domain]])))
+        e += 1
+    return out
+
+
+def sincos_every_double_arguments(n=200000, seed=5):
+    """for host == device: log-uniform over 1e-308 ... DBL_MAX in both signs, the neighbourhoods of +-2^31 pi / 2 and +-2^32 pi / 2 on both sides, subnormals, +-0,
+    +-DBL_MAX (no infinity, no NaN)"""
+    rng = np.random.default_rng(seed)
+    big = np.finfo(np.float64).max
+    x = 10.0 ** rng.uniform(-308, np.log10(big), n) * rng.choice([-1.0, 1.0], n)
+    near = []
+    for k in (2.0 ** 31, 2.0 ** 32):
+        c = k * (np.pi / 2)
+        near += [c + rng.uniform(-64.0, 64.0, 4096), c + np.arange(-32, 33) * (np.pi / 2), c + np.arange(-32, 33) * (np.pi / 4)]
+        near.append(c + np.arange(-64, 65) * np.spacing(c))
+    near = np.concatenate(near)
+    tiny = np.finfo(np.float64).tiny
+    sub = np.concatenate([5e-324 * np.array([1.0, 2.0, 3.0, 1e3, 1e10]), [np.nextafter(tiny, 0.0), tiny], rng.uniform(0.0, tiny, 256)])
+    edge = np.array([0.0, big, np.nextafter(big, 0.0), 2.0 ** 52, 2.0 ** 53, 2.0 ** 63, 2.0 ** 64, 2.0 ** 1023])
+    pos = np.concatenate([near, sub, edge])
+    return np.concatenate([x, pos, -pos])
 
 
 def sincos_longdouble(x):
@@ -117,8 +184,39 @@ def revolute_longdouble(x):
     return np.concatenate([p + rp, rq], axis=1), np.concatenate([np.abs(p) + mp, mq + 1e-300], axis=1)
 
 
+def sincos_abs_error(ev, x):
+    """the worst absolute error of either component of ev(0, x) against long double"""
+    out = ev(0, x)
+    rs, rc = sincos_longdouble(x)
+    return float(max(np.max(np.abs(out[:, 0].astype(LD) - rs)), np.max(np.abs(out[:, 1].astype(LD) - rc))))
+
+
+def sincos_domain_table(ev, per_binade=400000, seed=1, n_mp=200):
+    """the measurement behind BIOIK_SINCOS_DOMAIN (bioik_sincos.h): the worst absolute error on |x| <= 1e5, then per binade [2^e, 2^(e+1)) from e = 17 to 52, long double
+    as the reference, itself held against mpmath (50 digits) on n_mp arguments of every binade.  Returns (base, [(e, worst, long double's own error)])."""
+    rng = np.random.default_rng(seed)
+    base = max(sincos_abs_error(ev, rng.uniform(-a, a, per_binade)) for a in (4.0, 100.0, 1e5, 1e5, 1e5))
+    rows = []
+    for e in range(17, 53):
+        x = rng.uniform(2.0 ** e, 2.0 ** (e + 1), per_binade) * rng.choice([-1.0, 1.0], per_binade)
+        ls, lc = sincos_longdouble(x[:n_mp])
+        ms, mc = sincos_mpmath(x[:n_mp])
+        rows.append((e, sincos_abs_error(ev, x), float(max(np.max(np.abs(ls - ms)), np.max(np.abs(lc - mc))))))
+    return base, rows
+
+
 if __name__ == "__main__":
+    import sys
     rng = np.random.default_rng(0)
     xs = np.concatenate([rng.uniform(-1e5, 1e5, 2000), sincos_special_arguments()])
     a, b = sincos_longdouble(xs), sincos_mpmath(xs)
     print("long double vs mpmath (50 digits), %d arguments: max |sin| diff %.3g, max |cos| diff %.3g" % (len(xs), float(np.max(np.abs(a[0] - b[0]))), float(np.max(np.abs(a[1] - b[1])))))
+    if len(sys.argv) > 2 and sys.argv[1] == "--sincos-domain":  # python tools/arith_reference.py --sincos-domain tests/hostsim/libbioik_hostsim.so
+        import os
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+        from bio_ik_amd import solver
+        lib = solver.load_library(sys.argv[2])
+        base, rows = sincos_domain_table(lambda op, x: solver.eval_arith(op, x, lib=lib))
+        print("worst absolute error of either component, |x| <= 1e5: %.3g" % base)
+        for e, worst, ld in rows:
+            print("2^%d .. 2^%d: %.3g (%.2f x)   long double vs mpmath %.1g" % (e, e + 1, worst, worst / base, ld))

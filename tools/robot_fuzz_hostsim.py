@@ -5,6 +5,8 @@ success test and a whole solve must be the oracle's bit for bit on ANY robot, an
 ROBOT_FUZZ_GRADIENT=1: every third robot is solved by a point solver of the gradient family (gd / gd_r / gd_c) instead; ROBOT_FUZZ_BIG=1: 12 - 30 links, up to six tips; ROBOT_FUZZ_PLAIN=1: trees whose default program folds exactly (unrotated origins, no prismatic joint, fixed links without offset) -- the DEFAULT program bit for bit, populations 16 ... 200; ROBOT_FUZZ_BALANCE=1: links with mass and a BalanceGoal (whose sum over the links the device takes in walk order: agreement to rounding, DESIGN.md section 7 -- the strict comparison of this tool then reports it).  (Floating / planar joints are not drawn
 here: tests/random_robot_cases.py draws them with a sampler of their own, on the device and in the host simulator.)  The trees and goal lists come from
 tools/robot_gen.py.
+ROBOT_FUZZ_HUGE=1: the ORACLE's solve of every robot alone, to find solves whose line search meets a candidate with a gene of magnitude in [2^32, 1e300)
+(orc.huge_candidates: finite, but past the int32 quadrant of the sincos as first written, and below the candidate bound of that time); prints those cases and their count.
 usage: python tools/robot_fuzz_hostsim.py [cases] [seed]   (seconds per case; exit code 1 on a mismatch)"""
 import os
 import subprocess
@@ -20,6 +22,16 @@ import parity_cases as pc  # noqa: E402
 import robot_gen  # noqa: E402
 from bio_ik_amd import ProblemTemplate, abi, solver  # noqa: E402
 from oracle import orc  # noqa: E402
+
+
+def huge_candidates_met(o, t, pop, steps, mode, fk, case):
+    """the oracle's side of whole_solve alone: how many line-search candidates of magnitude [2^32, 1e300) it met"""
+    from bio_ik_amd.workload import make_queries
+    seeds, params, _ = make_queries(t, o.active_variables, o.fk_genes, 2, seed=case)
+    p = abi.default_solve_params(population=pop, max_steps=steps, random_seed=11, mode=mode, fk_mode=fk, islands=1 + case % 2)
+    before = orc.huge_candidates()
+    o.solve_batch(p, orc.RNG_COUNTER, seeds, params, n_threads=4)
+    return orc.huge_candidates() - before
 
 
 def whole_solve(h, o, t, pop, steps, mode, fk, case):
@@ -43,7 +55,7 @@ def main():
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
     lib = solver.load_library(os.path.join(ROOT, "tests", "hostsim", "libbioik_hostsim.so"))
     orc.set_trig_mode(1)
-    bad = skipped = 0
+    bad = skipped = met_huge = 0
     for case in range(n_cases):
         drawn = robot_gen.fuzz_case(rng, case, big=bool(os.environ.get("ROBOT_FUZZ_BIG")), plain=bool(os.environ.get("ROBOT_FUZZ_PLAIN")),
                                     balance=bool(os.environ.get("ROBOT_FUZZ_BALANCE")), gradient=bool(os.environ.get("ROBOT_FUZZ_GRADIENT")))
@@ -67,6 +79,12 @@ def main():
                 skipped += 1
                 print("%-3d skip %s (no active variable)" % (case, desc), flush=True)
                 continue
+            if os.environ.get("ROBOT_FUZZ_HUGE"):
+                k = huge_candidates_met(o, t, pop, steps, mode, fk, case)
+                if k:
+                    met_huge += 1
+                    print("%-3d HUGE %s: %d candidates with a gene of magnitude in [2^32, 1e300) (mode %s, fk %d, population %d, steps %d)" % (case, desc, k, mode, fk, pop, steps), flush=True)
+                continue
             if os.environ.get("ROBOT_FUZZ_PLAIN"):  # the default program itself, bit for bit, populations up to the lane counts of the kernels compiled for one mapping
                 os.environ["BIOIK_COMPILE_EXACT"] = "0"
                 h = solver.HipSolver(t, lib=lib)
@@ -89,6 +107,10 @@ def main():
             import traceback
             bad += 1
             print("%-3d BAD  [EXACT=%s] %s: %s @ %s" % (case, os.environ["BIOIK_COMPILE_EXACT"], desc, e, traceback.format_exc().splitlines()[-3].strip()), flush=True)
+    if os.environ.get("ROBOT_FUZZ_HUGE"):
+        print("%d cases, %d skipped, %d solves met a line-search candidate of magnitude in [2^32, 1e300); %d candidates at or beyond the bound of %g" % (
+            n_cases, skipped, met_huge, orc.unbounded_candidates(), orc.candidate_bound()))
+        sys.exit(0)
     print("%d cases, %d skipped (unsupported by the device, or no active variable), %d mismatches" % (n_cases, skipped, bad))
     sys.exit(1 if bad else 0)
 
