@@ -635,7 +635,9 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
     dev.serial_chain = n_chain > 0 ? 1 : 0;
     for (int k = 0; k < n_chain; k++)
         if (ops[k].src != k - 1 || ops[k].load_slot >= 0 || ops[k].save_slot >= 0 || ops[k].mimic_src >= 0 || ops[k].type >= BIOIK_OP_FLOATING) dev.serial_chain = 0;
-    dev.reserved0 = 0;
+    dev.tips_last = dev.serial_chain && dev.n_root_tips == 0 ? 1 : 0;
+    for (int k = 0; k + 1 < n_chain; k++)
+        if (ops[k].tip_count != 0) dev.tips_last = 0;
     dev.genes_follow_ops = 1;
     for (int i = 1; i < D; i++)
         if (dev.op_of_gene[i] <= dev.op_of_gene[i - 1]) dev.genes_follow_ops = 0;

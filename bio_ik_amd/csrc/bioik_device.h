@@ -82,70 +82,82 @@ BIOIK_DEV F7 f7_concat(const F7& a, const F7& b) { return F7{a.p + qrot(a.q, b.p
 // (up to the sign of an exact zero).  Derivation: bk_qrot / bk_qmul of bioik_fused.h with the zero operands struck out, and
 // `p + (2 r + 0)` written as the single rounding fma(2, r, p) (doubling is exact).
 // ---------------------------------------------------------------------------------------------------------
+// (every form reads the position `p` and the rotation `q` in front of the joint and RETURNS what is behind it: where the result goes is the caller's choice)
 template <int AXIS>  // v = cpos[AXIS] on axis AXIS, the other two components are zero
-BIOIK_DEV void revolute_pos_axis(F7& f, double v) {
-    const Q4 q = f.q;
+BIOIK_DEV V3 revolute_pos_axis(const V3& p, const Q4& q, double v) {
     if constexpr (AXIS == 0) {
         const double ty = q.z * v, tz = -(q.y * v);
         const double rx = BK_FMA(q.y, tz, -(q.z * ty)), ry = BK_FMA(q.w, ty, -(q.x * tz)), rz = BK_FMA(q.w, tz, q.x * ty);
-        f.p = V3{f.p.x + BK_FMA(2.0, rx, v), BK_FMA(2.0, ry, f.p.y), BK_FMA(2.0, rz, f.p.z)};
+        return V3{p.x + BK_FMA(2.0, rx, v), BK_FMA(2.0, ry, p.y), BK_FMA(2.0, rz, p.z)};
     } else if constexpr (AXIS == 1) {
         const double tx = -(q.z * v), tz = q.x * v;
         const double rx = BK_FMA(q.w, tx, q.y * tz), ry = BK_FMA(q.z, tx, -(q.x * tz)), rz = BK_FMA(q.w, tz, -(q.y * tx));
-        f.p = V3{BK_FMA(2.0, rx, f.p.x), f.p.y + BK_FMA(2.0, ry, v), BK_FMA(2.0, rz, f.p.z)};
+        return V3{BK_FMA(2.0, rx, p.x), p.y + BK_FMA(2.0, ry, v), BK_FMA(2.0, rz, p.z)};
     } else {
         const double tx = q.y * v, ty = -(q.x * v);
         const double rx = BK_FMA(q.w, tx, -(q.z * ty)), ry = BK_FMA(q.w, ty, q.z * tx), rz = BK_FMA(q.x, ty, -(q.y * tx));
-        f.p = V3{BK_FMA(2.0, rx, f.p.x), BK_FMA(2.0, ry, f.p.y), f.p.z + BK_FMA(2.0, rz, v)};
+        return V3{BK_FMA(2.0, rx, p.x), BK_FMA(2.0, ry, p.y), p.z + BK_FMA(2.0, rz, v)};
     }
 }
 template <int AXIS>  // local rotation (a e_AXIS, c): unrotated constant frame, joint axis on a coordinate axis; a = sn * cb[AXIS], c = cs
-BIOIK_DEV void revolute_rot_axis(F7& f, double a, double c) {
-    const Q4 p = f.q;
+BIOIK_DEV Q4 revolute_rot_axis(const Q4& p, double a, double c) {
     if constexpr (AXIS == 0)
-        f.q = Q4{BK_FMA(p.w, a, p.x * c), BK_FMA(p.y, c, p.z * a), BK_FMA(p.z, c, -(p.y * a)), BK_FMA(p.w, c, -(p.x * a))};
+        return Q4{BK_FMA(p.w, a, p.x * c), BK_FMA(p.y, c, p.z * a), BK_FMA(p.z, c, -(p.y * a)), BK_FMA(p.w, c, -(p.x * a))};
     else if constexpr (AXIS == 1)
-        f.q = Q4{BK_FMA(p.x, c, -(p.z * a)), BK_FMA(p.w, a, p.y * c), BK_FMA(p.z, c, p.x * a), BK_FMA(p.w, c, -(p.y * a))};
+        return Q4{BK_FMA(p.x, c, -(p.z * a)), BK_FMA(p.w, a, p.y * c), BK_FMA(p.z, c, p.x * a), BK_FMA(p.w, c, -(p.y * a))};
     else
-        f.q = Q4{BK_FMA(p.x, c, p.y * a), BK_FMA(p.y, c, -(p.x * a)), BK_FMA(p.w, a, p.z * c), BK_FMA(p.w, c, -(p.z * a))};
+        return Q4{BK_FMA(p.x, c, p.y * a), BK_FMA(p.y, c, -(p.x * a)), BK_FMA(p.w, a, p.z * c), BK_FMA(p.w, c, -(p.z * a))};
 }
 struct RevConst {  // the constants of one revolute op as the walk holds them (scalar registers)
     double cp0, cp1, cp2, ca0, ca1, ca2, ca3, cb0, cb1, cb2, cb3;
     int pos_kind, rot_kind;
 };
-// N individuals through the same joint: the branches are wavefront-uniform, the constants stay scalar operands
+// N individuals through the same joint, f = a o joint: the branches are wavefront-uniform, the constants stay scalar operands.  The frames in front of the
+// joint are read from `a`, those behind it written to `f`: a new rotation needs all four numbers of the old one, so a caller that wants no copy between the
+// two names two arrays (fk_walk_n); any other names the same one twice -- every number of `a` is read before the first of `f` is written
 template <int N>
-BIOIK_DEV void revolute_apply(F7 (&f)[N], const double (&sn)[N], const double (&cs)[N], const RevConst& k) {
+BIOIK_DEV void revolute_apply(const F7 (&a)[N], F7 (&f)[N], const double (&sn)[N], const double (&cs)[N], const RevConst& k) {
     // position first: it reads the frame's rotation in front of the joint
+    V3 p[N];
     if (k.pos_kind == BIOIK_POS_GENERAL) {
 #pragma unroll
-        for (int j = 0; j < N; j++) f[j].p = f[j].p + qrot(f[j].q, v3(k.cp0, k.cp1, k.cp2));
+        for (int j = 0; j < N; j++) p[j] = a[j].p + qrot(a[j].q, v3(k.cp0, k.cp1, k.cp2));
     } else if (k.pos_kind == BIOIK_POS_X) {
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_pos_axis<0>(f[j], k.cp0);
+        for (int j = 0; j < N; j++) p[j] = revolute_pos_axis<0>(a[j].p, a[j].q, k.cp0);
     } else if (k.pos_kind == BIOIK_POS_Y) {
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_pos_axis<1>(f[j], k.cp1);
-    } else if (k.pos_kind == BIOIK_POS_Z) {
+        for (int j = 0; j < N; j++) p[j] = revolute_pos_axis<1>(a[j].p, a[j].q, k.cp1);
+    } else if (k.pos_kind == BIOIK_POS_ZERO) {  // the joint sits at its parent's origin
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_pos_axis<2>(f[j], k.cp2);
-    }  // BIOIK_POS_ZERO: the joint sits at its parent's origin
+        for (int j = 0; j < N; j++) p[j] = a[j].p;
+    } else {  // BIOIK_POS_Z (the last of the kinds and not a test of its own: no path is left on which the position in front of the joint would have to be kept)
+#pragma unroll
+        for (int j = 0; j < N; j++) p[j] = revolute_pos_axis<2>(a[j].p, a[j].q, k.cp2);
+    }
+    Q4 q[N];
     if (k.rot_kind == BIOIK_ROT_GENERAL) {
 #pragma unroll
         for (int j = 0; j < N; j++) {
             const Q4 lq = Q4{BK_FMA(cs[j], k.ca0, sn[j] * k.cb0), BK_FMA(cs[j], k.ca1, sn[j] * k.cb1), BK_FMA(cs[j], k.ca2, sn[j] * k.cb2), BK_FMA(cs[j], k.ca3, sn[j] * k.cb3)};
-            f[j].q = qmul(f[j].q, lq);
+            q[j] = qmul(a[j].q, lq);
         }
     } else if (k.rot_kind == BIOIK_ROT_X) {
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_rot_axis<0>(f[j], sn[j] * k.cb0, cs[j]);
+        for (int j = 0; j < N; j++) q[j] = revolute_rot_axis<0>(a[j].q, sn[j] * k.cb0, cs[j]);
     } else if (k.rot_kind == BIOIK_ROT_Y) {
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_rot_axis<1>(f[j], sn[j] * k.cb1, cs[j]);
+        for (int j = 0; j < N; j++) q[j] = revolute_rot_axis<1>(a[j].q, sn[j] * k.cb1, cs[j]);
     } else {
 #pragma unroll
-        for (int j = 0; j < N; j++) revolute_rot_axis<2>(f[j], sn[j] * k.cb2, cs[j]);
+        for (int j = 0; j < N; j++) q[j] = revolute_rot_axis<2>(a[j].q, sn[j] * k.cb2, cs[j]);
     }
+#pragma unroll
+    for (int j = 0; j < N; j++) f[j] = F7{p[j], q[j]};
+}
+template <int N>  // ... in place
+BIOIK_DEV void revolute_apply(F7 (&f)[N], const double (&sn)[N], const double (&cs)[N], const RevConst& k) {
+    revolute_apply<N>(f, f, sn, cs, k);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -884,9 +896,55 @@ BIOIK_DEV double eval_exact_primary(PB pb, const XA& x, const QueryCtx& qc, doub
 // dependency chains, so that the scalar loads of a joint's constants, the LDS reads of the gene values and the latency of the
 // polynomial chains are paid once per joint instead of once per joint and child.  Arithmetic per individual is identical
 // to fk_walk.  Parked branch frames: child j uses the slot set at slots + j * slot_set_stride.
-// SERIAL (DevProblem::serial_chain, the caller's promise): no op fetches or parks a branch frame, restarts at the root or mimics another joint -- the
-// loop body then has ONE definition of the running frames, and the compiler keeps them in the same registers from joint to joint (with the branch
-// paths in the body it copies all 14 N numbers between two sets of registers in every trip)
+// SERIAL (DevProblem::serial_chain, the caller's promise): no op fetches or parks a branch frame, restarts at the root or mimics another joint.  Where
+// moreover every tip hangs behind the LAST op (DevProblem::tips_last: the usual arm) the joints are walked by a loop that holds nothing else, two per trip:
+// a joint's new rotation needs all four numbers of the old one, so new and old frame cannot share registers, and a loop of one joint per trip ends every
+// trip by copying the 14 N numbers of the new frames onto the old ones.  With two joints per trip joint k takes the frames from f to g and joint k + 1 from g
+// back to f: each half writes what the other one reads and nothing is copied (but the position behind a joint at its parent's origin, BIOIK_POS_ZERO,
+// which has to change sets like the rest).  The last joint (of an even number the last two) and the tips are left to the loop of one joint per
+// trip behind it, which is also the whole walk of a chain with a tip in its middle.
+// One joint of a serial chain for N individuals: f = a o (op k at the children's values), a and f as for revolute_apply; returns the op's tips in t0, t1.
+template <int N, class PB, class XA>
+BIOIK_DEV void serial_joint_n(PB pb, int k, const XA (&x)[N], const F7 (&a)[N], F7 (&f)[N], double* slots, int slot_set_stride, int nth, int& t0, int& t1) {
+    // every scalar of the joint is requested here, in one burst of scalar loads that is waited for once (fk_walk_n)
+    const int type = pb->ops[k].type;
+    const int pk = pb->ops[k].pos_kind, rk = pb->ops[k].rot_kind;
+    t0 = pb->ops[k].tip_first, t1 = t0 + pb->ops[k].tip_count;
+    const double ca0 = pb->ops[k].ca[0], ca1 = pb->ops[k].ca[1], ca2 = pb->ops[k].ca[2], ca3 = pb->ops[k].ca[3];
+    const double cb0 = pb->ops[k].cb[0], cb1 = pb->ops[k].cb[1], cb2 = pb->ops[k].cb[2], cb3 = pb->ops[k].cb[3];
+    const double cp0 = pb->ops[k].cpos[0], cp1 = pb->ops[k].cpos[1], cp2 = pb->ops[k].cpos[2];
+    double xv[N];
+    if constexpr (accessor_takes_op_numbers<XA>::value) {
+        // (children computed where they are read: what their accessor reads of the op comes with the burst above)
+        const int gene = pb->ops[k].gene;
+        const double span = pb->ops[k].span, cmin = pb->ops[k].clip_min, cmax = pb->ops[k].clip_max;
+#pragma unroll
+        for (int j = 0; j < N; j++) xv[j] = x[j].at(k, gene, span, cmin, cmax);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) xv[j] = joint_value(x[j], k, -1, 1.0, 0.0);
+    }
+    if (type == BIOIK_OP_REVOLUTE) {  // (wavefront-uniform, as in fk_walk_n)
+        double sn[N], cs[N];
+#pragma unroll
+        for (int j = 0; j < N; j++) p_sincos(xv[j] * 0.5, &sn[j], &cs[j]);
+        revolute_apply<N>(a, f, sn, cs, RevConst{cp0, cp1, cp2, ca0, ca1, ca2, ca3, cb0, cb1, cb2, cb3, pk, rk});
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            const V3 lp = v3(BK_FMA(xv[j], cb0, cp0), BK_FMA(xv[j], cb1, cp1), BK_FMA(xv[j], cb2, cp2));
+            const V3 np = a[j].p + qrot(a[j].q, lp);
+            const Q4 nq = qmul(a[j].q, Q4{ca0, ca1, ca2, ca3});
+            f[j] = F7{np, nq};
+        }
+        if constexpr (pb_flavour<PB>::general)
+            if (type >= BIOIK_OP_FLOATING) {
+                const int tid = p_tid_fresh();
+#pragma unroll
+                for (int j = 0; j < N; j++) f[j] = multi_joint_fetch(f[j], slots + (size_t)j * slot_set_stride, pb->ops[k].multi_slot, nth, tid);
+            }
+    }
+}
 template <int N, bool SERIAL = false, class PB, class XA, class TipFn>
 BIOIK_DEV void fk_walk_n(PB pb, const XA (&x)[N], double* slots, int slot_set_stride, TipFn&& tip_fn, const double* prefix = nullptr) {
     const int nth = p_nthreads();
@@ -918,28 +976,51 @@ BIOIK_DEV void fk_walk_n(PB pb, const XA (&x)[N], double* slots, int slot_set_st
     }
     if constexpr (pb_flavour<PB>::general && std::is_same<XA, XV>::value)
         for (int j = 0; j < N; j++) multi_joint_prologue(pb, x[j], slots + (size_t)j * slot_set_stride);
+    if constexpr (SERIAL) {
+        int k = k_begin;
+        if (pb->tips_last) {
+            // no tip in front of the last op: nothing but joints in this loop (the last joint -- of an even number the last two -- and the tips behind it are
+            // left to the loop below)
+            F7 g[N];
+            int t0, t1;
+            for (; k + 2 < n_chain; k += 2) {
+                serial_joint_n<N>(pb, k, x, f, g, slots, slot_set_stride, nth, t0, t1);
+                serial_joint_n<N>(pb, k + 1, x, g, f, slots, slot_set_stride, nth, t0, t1);
+            }
+        }
+        for (; k < n_chain; k++) {
+            int t0, t1;
+            serial_joint_n<N>(pb, k, x, f, f, slots, slot_set_stride, nth, t0, t1);
+            for (int t = t0; t < t1; t++) {
+                F7 o[N];
+                if (pb->tips[t].has_e) {
+                    double e[7];
+                    for (int c2 = 0; c2 < 7; c2++) e[c2] = pb->tips[t].e[c2];
+#pragma unroll
+                    for (int j = 0; j < N; j++) o[j] = f7_concat(f[j], f7_load(e));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < N; j++) o[j] = f[j];
+                }
+                tip_fn(t, o);
+            }
+        }
+        return;
+    }
     for (int k = k_begin; k < n_chain; k++) {
         // every scalar of the joint is requested here, in one burst of scalar loads that is waited for once (reading
         // them where they are used costs one exposed scalar-cache round trip per branch of the loop body)
-        const int type = pb->ops[k].type, src = SERIAL ? k - 1 : pb->ops[k].src, ls = SERIAL ? -1 : pb->ops[k].load_slot, ss = SERIAL ? -1 : pb->ops[k].save_slot;
+        const int type = pb->ops[k].type, src = pb->ops[k].src, ls = pb->ops[k].load_slot, ss = pb->ops[k].save_slot;
         const int pk = pb->ops[k].pos_kind, rk = pb->ops[k].rot_kind;
         const int t0 = pb->ops[k].tip_first, t1 = t0 + pb->ops[k].tip_count;
-        const int msrc = SERIAL ? -1 : pb->ops[k].mimic_src;
-        const double mf = SERIAL ? 1.0 : pb->ops[k].mimic_factor, mo = SERIAL ? 0.0 : pb->ops[k].mimic_offset;
+        const int msrc = pb->ops[k].mimic_src;
+        const double mf = pb->ops[k].mimic_factor, mo = pb->ops[k].mimic_offset;
         const double ca0 = pb->ops[k].ca[0], ca1 = pb->ops[k].ca[1], ca2 = pb->ops[k].ca[2], ca3 = pb->ops[k].ca[3];
         const double cb0 = pb->ops[k].cb[0], cb1 = pb->ops[k].cb[1], cb2 = pb->ops[k].cb[2], cb3 = pb->ops[k].cb[3];
         const double cp0 = pb->ops[k].cpos[0], cp1 = pb->ops[k].cpos[1], cp2 = pb->ops[k].cpos[2];
         double xv[N];
-        if constexpr (SERIAL && accessor_takes_op_numbers<XA>::value) {
-            // (children computed where they are read: what their accessor reads of the op comes with the burst above)
-            const int gene = pb->ops[k].gene;
-            const double span = pb->ops[k].span, cmin = pb->ops[k].clip_min, cmax = pb->ops[k].clip_max;
 #pragma unroll
-            for (int j = 0; j < N; j++) xv[j] = x[j].at(k, gene, span, cmin, cmax);
-        } else {
-#pragma unroll
-            for (int j = 0; j < N; j++) xv[j] = joint_value(x[j], k, msrc, mf, mo);
-        }
+        for (int j = 0; j < N; j++) xv[j] = joint_value(x[j], k, msrc, mf, mo);
         if (ls >= 0) {
             const int tid = p_tid_fresh();
 #pragma unroll

@@ -110,7 +110,8 @@ struct DevProblem {
     double pose_weight_sq;   // primary[0].weight_sq
     int32_t serial_chain;    // 1: ops[0..n_chain_ops) are ONE serial chain -- every op continues the frame of the op in front of it, none fetches or parks
                              //    a branch frame, none is a mimic joint: the walk of the dense kernels then carries its frames in place
-    int32_t reserved0;
+    int32_t tips_last;       // 1: a serial chain whose tips all hang behind its LAST op (none on the root, none in the middle): the walk of the dense kernels
+                             //    then has no tip inside its joint loop (fk_walk_n)
     uint64_t active_mask;  // bit k: op k is an active gene (ops[k].gene >= 0)
     double multi_c[7];     // (unused since round 5: the constant frame in front of a floating / planar joint lies in its op's cpos / ca)
     int32_t quat_op[4];    // op index of the first of the four orientation value ops

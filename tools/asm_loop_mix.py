@@ -9,6 +9,12 @@ Every basic block is charged to the innermost loop the assembler's comments plac
 the classes (fma / mul / add = FP64; imul = 32-bit integer multiplies, 2.4 issue slots each on gfx950; mov, cnd = v_cndmask, cmp, lane =
 v_readlane / v_writelane, vint = every other VALU instruction; salu, smem, lds, wait = s_waitcnt, scratch) and the source lines
 (file, line rounded to 10) most of the loop's instructions come from.  The counts are static: weigh them with the trip counts.
+
+    python tools/asm_loop_mix.py /tmp/k.s _Z19k_solve_lean_cl64w49SolveArgs --copies [N]
+
+lists instead every loop of the kernel that holds a run of N (default 4) or more consecutive v_mov_b32 / v_mov_b64 from a VGPR to a VGPR -- values carried
+from one set of registers to another, which the `mov` class above does not tell from constants being materialised: the loop's header and depth, the block
+of the run, whether that block is the loop's latch (it branches back to the header), the run's length in instructions and in dwords, and its source line.
 """
 import collections
 import re
@@ -51,7 +57,66 @@ VALU = ("fma", "mul", "add", "mov", "cnd", "cmp", "lane", "vint", "imul")
 SHOWN = VALU + ("salu", "smem", "lds", "wait", "scratch")
 
 
+VGPR_COPY = re.compile(r"^v_mov_b(32|64)(?:_e32|_e64)?\s+v(?:\d+|\[\d+:\d+\]),\s*v(?:\d+|\[\d+:\d+\])\s*(?:;.*)?$")
+
+
+def copy_runs(lines, start, end, files, least):
+    """runs of `least` or more consecutive VGPR-to-VGPR moves inside loops: (header, depth, block, is_latch, instructions, dwords, source)"""
+    runs = []
+    header, block, loc = ("top", 0), None, None
+    run, dwords, run_loc = 0, 0, None
+    latch = {}
+
+    def close():
+        nonlocal run, dwords
+        if run >= least and header[1] > 0:
+            runs.append([header[0], header[1], block, run, dwords, run_loc])
+        run, dwords = 0, 0
+    for i in range(start, end):
+        t = lines[i]
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", t)
+        if m:
+            close()
+            comment = m.group(2) or ""
+            j = i + 1
+            while j < end and lines[j].lstrip().startswith(";"):
+                comment += lines[j]
+                j += 1
+            own = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", comment)
+            inside = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", comment)
+            block = m.group(1)[2:]
+            header = (block, int(own.group(1))) if own else ((inside.group(1), int(inside.group(2))) if inside else ("top", 0))
+            continue
+        t = t.strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            if int(m.group(2)):  # (line 0: compiler-made code, such as the copies at a latch; it keeps the line in front of it)
+                loc = "%s:%d" % (files.get(int(m.group(1))), int(m.group(2)))
+            continue
+        if not t or t[0] in ";." or t.split()[0].endswith(":"):
+            continue
+        m = VGPR_COPY.match(t)
+        if m:
+            if run == 0:
+                run_loc = loc
+            run += 1
+            dwords += 2 if m.group(1) == "64" else 1
+            continue
+        close()
+        m = re.match(r"s_c?branch\S*\s+\.L(BB\d+_\d+)", t)
+        if m and m.group(1) == header[0]:
+            latch[block] = True
+    close()
+    return [(h, d, b, bool(latch.get(b)), n, w, src) for h, d, b, n, w, src in runs]
+
+
 def main():
+    if "--copies" in sys.argv:
+        k = sys.argv.index("--copies")
+        least = int(sys.argv[k + 1]) if len(sys.argv) > k + 1 else 4
+        del sys.argv[k:k + 2]
+    else:
+        least = 0
     path = sys.argv[1]
     kernel = sys.argv[2] if len(sys.argv) > 2 else "_Z12k_solve_lean9SolveArgs"
     rows = int(sys.argv[3]) if len(sys.argv) > 3 else 25
@@ -63,6 +128,12 @@ def main():
         m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
         if m:
             files[int(m.group(1))] = (m.group(3) or m.group(2)).split("/")[-1]
+    if least:
+        found = copy_runs(lines, start, end, files, least)
+        print("kernel", kernel, "runs of %d or more VGPR-to-VGPR moves inside loops: %d" % (least, len(found)))
+        for h, d, b, is_latch, n, w, src in sorted(found, key=lambda r: (-r[1], -r[4])):
+            print("depth %d  loop %-10s block %-10s %-5s %2d moves %2d dwords  %s" % (d, h, b, "latch" if is_latch else "body", n, w, src))
+        return
     header, loc = ("top", 0), None
     count = collections.defaultdict(collections.Counter)
     source = collections.defaultdict(collections.Counter)
