@@ -800,7 +800,7 @@ BIOIK_DEV void fk_walk(PB pb, const XA& x, double* slots, double* frames_out, Ti
     if (coop) {
         const int mine = lane - coop_base, kk = mine < n_chain ? mine : n_chain - 1;
         my_xv = joint_value(x, kk, pb->ops[kk].mimic_src, pb->ops[kk].mimic_factor, pb->ops[kk].mimic_offset);
-        p_sincos(my_xv * 0.5, &my_sn, &my_cs);
+        p_sincos(my_xv * 0.5, &my_sn, &my_cs);  // (no vote: lane k holds joint k here, and one joint beyond BIOIK_SINCOS_SMALL is the rule)
     }
     for (int k = k_begin; k < n_chain; k++) {
         double xv, sn, cs;
@@ -809,7 +809,7 @@ BIOIK_DEV void fk_walk(PB pb, const XA& x, double* slots, double* frames_out, Ti
             else xv = p_shfl(my_xv, coop_base + k), sn = p_shfl(my_sn, coop_base + k), cs = p_shfl(my_cs, coop_base + k);
         } else {
             xv = joint_value(x, k, pb->ops[k].mimic_src, pb->ops[k].mimic_factor, pb->ops[k].mimic_offset);
-            p_sincos(xv * 0.5, &sn, &cs);
+            p_sincos_voted(xv * 0.5, &sn, &cs);
         }
         const int type = pb->ops[k].type, src = pb->ops[k].src, ls = pb->ops[k].load_slot, ss = pb->ops[k].save_slot;
         const int t0 = pb->ops[k].tip_first, t1 = t0 + pb->ops[k].tip_count;
@@ -925,10 +925,23 @@ BIOIK_DEV void serial_joint_n(PB pb, int k, const XA (&x)[N], const F7 (&a)[N], 
         for (int j = 0; j < N; j++) xv[j] = joint_value(x[j], k, -1, 1.0, 0.0);
     }
     if (type == BIOIK_OP_REVOLUTE) {  // (wavefront-uniform, as in fk_walk_n)
-        double sn[N], cs[N];
+        double h[N], sn[N], cs[N];
 #pragma unroll
-        for (int j = 0; j < N; j++) p_sincos(xv[j] * 0.5, &sn[j], &cs[j]);
-        revolute_apply<N>(a, f, sn, cs, RevConst{cp0, cp1, cp2, ca0, ca1, ca2, ca3, cb0, cb1, cb2, cb3, pk, rk});
+        for (int j = 0; j < N; j++) h[j] = xv[j] * 0.5;
+        const RevConst rc{cp0, cp1, cp2, ca0, ca1, ca2, ca3, cb0, cb1, cb2, cb3, pk, rk};
+        // The wavefront's vote on small half angles (p_sincos_n) with the joint's frame algebra behind EACH path: joined in front of it, the small path pays two
+        // register copies per joint for the join.  Only for two or more children per lane: with one (k_solve_lean_cl4h, a lone wavefront bound by the latency
+        // of its chain, not by issue slots) the compare, ballot and branch in front of every joint cost more time than the 14 instructions take that they
+        // save -- measured: 2.7 % fewer VALU instructions, calls of 1 ... 16 queries 1 ... 1.6 % LONGER (profiles/sincos_small_path.log).
+        if (N >= 2 && p_sincos_all_small<N>(h)) {
+#pragma unroll
+            for (int j = 0; j < N; j++) bioik_sincos_small(h[j], &sn[j], &cs[j]);
+            revolute_apply<N>(a, f, sn, cs, rc);
+        } else {
+#pragma unroll
+            for (int j = 0; j < N; j++) p_sincos(h[j], &sn[j], &cs[j]);
+            revolute_apply<N>(a, f, sn, cs, rc);
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < N; j++) {
@@ -1037,9 +1050,10 @@ BIOIK_DEV void fk_walk_n(PB pb, const XA (&x)[N], double* slots, int slot_set_st
         // branch, not a select per component; the half-angle trigonometry only where it is used,
         // and the frame applied inside each branch so that the constants stay scalar operands
         if (type == BIOIK_OP_REVOLUTE) {
-            double sn[N], cs[N];
+            double h[N], sn[N], cs[N];
 #pragma unroll
-            for (int j = 0; j < N; j++) p_sincos(xv[j] * 0.5, &sn[j], &cs[j]);
+            for (int j = 0; j < N; j++) h[j] = xv[j] * 0.5;
+            p_sincos_n<N>(h, sn, cs);
             revolute_apply<N>(f, sn, cs, RevConst{cp0, cp1, cp2, ca0, ca1, ca2, ca3, cb0, cb1, cb2, cb3, pk, rk});
         } else {
 #pragma unroll

@@ -1749,6 +1749,7 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
 }
 
 double bioik_sincos_domain(void) { return BIOIK_SINCOS_DOMAIN; }
+double bioik_sincos_small_bound(void) { return BIOIK_SINCOS_SMALL; }
 
 int bioik_stream_fitness_device(bioik_problem* p, size_t n_units, int population, const double* d_seeds, const double* d_goal_params, const double* d_genes,
                                 double* d_fitness, void* hip_stream) {

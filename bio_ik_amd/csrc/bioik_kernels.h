@@ -2359,21 +2359,27 @@ BIOIK_DEV void eval_check_body(const EvalArgs& a, uint64_t block, double* lds) {
 // mode both include is evaluated here on the device for arbitrary arguments, so that a test can hold it against an independent high-precision
 // reference (tests/test_arith_headers.py) -- bit parity between two users of one header cannot show a defect of the header itself.
 // ---------------------------------------------------------------------------------------------------------
-enum { ARITH_SINCOS = 0, ARITH_QROT = 1, ARITH_QMUL = 2, ARITH_DOT3 = 3, ARITH_DOT4 = 4, ARITH_REVOLUTE = 5, ARITH_ACOS = 6, ARITH_ATAN2 = 7 };
+enum { ARITH_SINCOS = 0, ARITH_QROT = 1, ARITH_QMUL = 2, ARITH_DOT3 = 3, ARITH_DOT4 = 4, ARITH_REVOLUTE = 5, ARITH_ACOS = 6, ARITH_ATAN2 = 7, ARITH_SINCOS_VOTED = 8, ARITH_SINCOS_SMALL = 9 };
 struct ArithArgs {
     int32_t op, pad;
     uint64_t n;
     const double* in;  // [n][arith_in(op)]
     double* out;       // [n][arith_out(op)]
 };
-BIOIK_HD int arith_in(int op) { return op == ARITH_SINCOS ? 1 : op == ARITH_QROT ? 7 : op == ARITH_QMUL ? 8 : op == ARITH_DOT3 ? 6 : op == ARITH_DOT4 ? 8 : op == ARITH_REVOLUTE ? 22 : op == ARITH_ACOS ? 1 : op == ARITH_ATAN2 ? 2 : 0; }
-BIOIK_HD int arith_out(int op) { return op == ARITH_SINCOS ? 2 : op == ARITH_QROT ? 3 : op == ARITH_QMUL ? 4 : op == ARITH_DOT3 ? 1 : op == ARITH_DOT4 ? 1 : op == ARITH_REVOLUTE ? 14 : op == ARITH_ACOS ? 1 : op == ARITH_ATAN2 ? 1 : 0; }
+BIOIK_HD int arith_in(int op) { return op == ARITH_SINCOS ? 1 : op == ARITH_QROT ? 7 : op == ARITH_QMUL ? 8 : op == ARITH_DOT3 ? 6 : op == ARITH_DOT4 ? 8 : op == ARITH_REVOLUTE ? 22 : op == ARITH_ACOS ? 1 : op == ARITH_ATAN2 ? 2 : op == ARITH_SINCOS_VOTED ? 1 : op == ARITH_SINCOS_SMALL ? 1 : 0; }
+BIOIK_HD int arith_out(int op) { return op == ARITH_SINCOS ? 2 : op == ARITH_QROT ? 3 : op == ARITH_QMUL ? 4 : op == ARITH_DOT3 ? 1 : op == ARITH_DOT4 ? 1 : op == ARITH_REVOLUTE ? 14 : op == ARITH_ACOS ? 1 : op == ARITH_ATAN2 ? 1 : op == ARITH_SINCOS_VOTED ? 2 : op == ARITH_SINCOS_SMALL ? 2 : 0; }
 BIOIK_DEV void arith_body(const ArithArgs& a, uint64_t i) {
     if (i >= a.n) return;
     const double* x = a.in + i * (uint64_t)arith_in(a.op);
     double* o = a.out + i * (uint64_t)arith_out(a.op);
     if (a.op == ARITH_SINCOS) {
         p_sincos(x[0], &o[0], &o[1]);
+    } else if (a.op == ARITH_SINCOS_VOTED) {
+        // the walks' sincos with its wavefront vote (p_sincos_n), lane = item: 64 consecutive items from a multiple of 64 on vote together, and the lanes behind
+        // the last item have left above
+        p_sincos_voted(x[0], &o[0], &o[1]);
+    } else if (a.op == ARITH_SINCOS_SMALL) {
+        bioik_sincos_small(x[0], &o[0], &o[1]);  // (the kernels alone: bioik_sincos only on |x| <= BIOIK_SINCOS_SMALL)
     } else if (a.op == ARITH_ACOS) {
         o[0] = bioik_acos(x[0]);
     } else if (a.op == ARITH_ATAN2) {

@@ -251,6 +251,41 @@ enum { PH_INIT = 0, PH_REPRODUCE = 1, PH_FITNESS = 2, PH_SELECTION = 3, PH_MEMET
 #define BIOIK_FUSED_FN BIOIK_DEV
 #include "bioik_fused.h"
 BIOIK_DEV void p_sincos(double x, double* s, double* c) { bioik_sincos(x, s, c); }
+// The half-angle sincos of the N individuals a lane walks together, voted on once per joint: where NO active lane of the wavefront holds a half angle beyond
+// BIOIK_SINCOS_SMALL, all N take bioik_sincos_small (no reduction, no quadrant: 14 instructions fewer per call), else all N take p_sincos.  One ballot of "some
+// h[j] is large" tested against zero -- inactive lanes cast no vote and so block nothing -- and one wavefront-uniform branch for all N.  A NaN fails the compare
+// and sends the wavefront down the general path.  On |h| <= BIOIK_SINCOS_SMALL both paths return the same bits, so ANY answer of the vote that is true only
+// where this lane's own values are small is correct: the host simulator, whose lanes are fibres and whose ballot is two rendezvous in the innermost loop of
+// every walk, answers with the lane's own predicate.
+#if defined(BIOIK_PLATFORM_HEADER)
+BIOIK_DEV bool p_none_of_wave(bool pred) { return !pred; }
+#else
+BIOIK_DEV bool p_none_of_wave(bool pred) { return __builtin_amdgcn_ballot_w64(pred) == 0ull; }
+#endif
+// the vote alone: true where every half angle of every active lane is small
+template <int N>
+BIOIK_DEV bool p_sincos_all_small(const double (&h)[N]) {
+    bool large = false;
+#pragma unroll
+    for (int j = 0; j < N; j++) large = large || !(__builtin_fabs(h[j]) <= BIOIK_SINCOS_SMALL);
+    return p_none_of_wave(large);
+}
+template <int N>
+BIOIK_DEV void p_sincos_n(const double (&h)[N], double (&sn)[N], double (&cs)[N]) {
+    if (p_sincos_all_small<N>(h)) {
+#pragma unroll
+        for (int j = 0; j < N; j++) bioik_sincos_small(h[j], &sn[j], &cs[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) p_sincos(h[j], &sn[j], &cs[j]);
+    }
+}
+BIOIK_DEV void p_sincos_voted(double h, double* s, double* c) {  // N = 1 with plain arguments
+    const double h1[1] = {h};
+    double s1[1], c1[1];
+    p_sincos_n<1>(h1, s1, c1);
+    *s = s1[0], *c = c1[0];
+}
 // acos / atan2 of the goal costs and of the success test: the shared bit-reproducible implementations (bioik_acos.h)
 #define BIOIK_ACOS_FN BIOIK_DEV
 #include "bioik_acos.h"

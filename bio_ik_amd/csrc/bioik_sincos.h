@@ -29,24 +29,35 @@
 #define BIOIK_SINCOS_FN inline
 #endif
 
-BIOIK_SINCOS_FN void bioik_sincos(double x, double* sn, double* cs) {
+// The three pieces of bioik_sincos, each inline in this header: the reduction (fn, r), the two fdlibm kernels on r, the quadrant step.  bioik_sincos composes
+// them; bioik_sincos_small is the kernels alone.
+BIOIK_SINCOS_FN void bioik_sincos_reduce(double x, double* fn_out, double* r_out) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
     const double invpio2 = 6.36619772367581382433e-01;
     const double P1 = 1.57079632679489655800e+00, P2 = 6.12323399573676603587e-17;
+    const double fn = __builtin_rint(x * invpio2);
+    double r = __builtin_fma(-fn, P1, x);
+    r = __builtin_fma(-fn, P2, r);
+    *fn_out = fn;
+    *r_out = r;
+}
+BIOIK_SINCOS_FN void bioik_sincos_kernels(double r, double* s_out, double* c_out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
                  S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
     const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
                  C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    const double fn = __builtin_rint(x * invpio2);
-    double r = __builtin_fma(-fn, P1, x);
-    r = __builtin_fma(-fn, P2, r);
     const double z = r * r;
     const double ps = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, S6, S5), S4), S3), S2), S1);
-    const double s = __builtin_fma(z * r, ps, r);
+    *s_out = __builtin_fma(z * r, ps, r);
     const double pc = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, C6, C5), C4), C3), C2), C1);
-    const double c = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
+    *c_out = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
+}
+BIOIK_SINCOS_FN void bioik_sincos_quadrant(double fn, double s, double c, double* sn, double* cs) {
     // The quadrant, fn mod 4: the low word of fn + 1.5 * 2^52 holds fn's low 32 bits in two's complement (|fn| < 2^51) -- ONE IEEE addition, the same
     // bits on every target for every double.  (A conversion to int is out of range from |fn| = 2^31 on, a half angle of 3.37e9: undefined in C++, INT_MIN
     // on x86-64 and a saturated value on gfx950, so the two sides parted and both were wrong.)
@@ -75,3 +86,18 @@ BIOIK_SINCOS_FN void bioik_sincos(double x, double* sn, double* cs) {
     __builtin_memcpy(cs, co, 8);
 #endif
 }
+
+BIOIK_SINCOS_FN void bioik_sincos(double x, double* sn, double* cs) {
+    double fn, r, s, c;
+    bioik_sincos_reduce(x, &fn, &r);
+    bioik_sincos_kernels(r, &s, &c);
+    bioik_sincos_quadrant(fn, s, c, sn, cs);
+}
+
+// Half angles of at most BIOIK_SINCOS_SMALL in magnitude need neither the reduction nor the quadrant.  rint is monotonic and odd, and
+// rint(BIOIK_SINCOS_SMALL * invpio2) = rint(0.4965...) == 0, so fn is (a signed) zero for every |x| <= BIOIK_SINCOS_SMALL: both reduction steps then return x itself
+// (fma(-+0, P, x) == x for every x but -0, which becomes +0: the sine kernel returns +0 for either zero, its last step being +0 + -0), the shifted sum's low
+// word is 0, and the quadrant step hands s and c through.  bioik_sincos_small is bioik_sincos without those pieces: the same bits on |x| <= BIOIK_SINCOS_SMALL
+// (tests/sincos_small_cases.py); beyond, and for NaN, it is NOT bioik_sincos.
+#define BIOIK_SINCOS_SMALL 0.78  // < pi / 4 = 0.78539...
+BIOIK_SINCOS_FN void bioik_sincos_small(double x, double* sn, double* cs) { bioik_sincos_kernels(x, sn, cs); }

@@ -453,12 +453,19 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
  *   5 revolute      frame[7] half_angle cpos[3] ca[4] cb[4] pos_kind rot_kind pad  -> frame'[7] by the general form, frame'[7] by the sparse form
  *   6 acos          x                                      -> acos x                  (reference: tf2Acos -> libm, include/bio_ik/goal_types.h:183-212, 646-712)
  *   7 atan2         y x                                    -> atan2(y, x)             (reference: KDL::Rotation::GetRot -> libm, src/problem.cpp:281-321)
+ *   8 sincos, voted x                                      -> sin x, cos x           (the chain walks' form: element i is lane i mod 64 of a wavefront that votes once on
+ *                                                                                       "every |x| <= BIOIK_SINCOS_SMALL"; the same bits as 0 for every x)
+ *   9 sincos, small x                                      -> sin x, cos x           (bioik_sincos_small: the same bits as 0 on |x| <= BIOIK_SINCOS_SMALL only)
  * Host pointers. */
 int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out);
 
 /* BIOIK_SINCOS_DOMAIN (bio_ik_amd/csrc/bioik_sincos.h), a power of two: the shared sincos gives the same bits on the host and on the device for every double and is
  * accurate for |x| below this value; a line-search candidate with a joint value of this magnitude or more is no candidate (BIOIK_CANDIDATE_BOUND). */
 double bioik_sincos_domain(void);
+
+/* BIOIK_SINCOS_SMALL (bio_ik_amd/csrc/bioik_sincos.h), below pi / 4: where no lane of a wavefront holds a half angle beyond it, the chain walks evaluate the shared
+ * sincos without its reduction and its quadrant step (the same bits). */
+double bioik_sincos_small_bound(void);
 
 /* streamed (unfused) generation: n_units (query,species) populations resident in HBM, layout
  * genes [n_units][D][population] (individual index fastest — coalesced), fitness [n_units][population].
