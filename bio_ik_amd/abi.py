@@ -65,9 +65,10 @@ class SolveParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("fk_mode", C.c_int32), ("population", C.c_int32),
                 ("islands", C.c_int32), ("max_steps", C.c_int32), ("random_seed", C.c_uint64), ("dpos", C.c_double),
                 ("drot", C.c_double), ("dtwist", C.c_double), ("no_wipeout", C.c_int32), ("schedule", C.c_int32), ("timeout", C.c_double),
-                ("island_sync", C.c_int32), ("reserved0", C.c_int32)]
+                ("island_sync", C.c_int32), ("island_migration", C.c_int32)]
 
 
+MAX_MIGRATIONS = 8  # BIOIK_MAX_MIGRATIONS: boundaries of a solve with island_migration > 0
 ISLANDS_AUTO = 0  # bioik_solve_params::islands: as many islands as the idle part of the chip carries (include/bioik_hip.h)
 
 
@@ -88,7 +89,7 @@ def default_solve_params(**kw):
     p.schedule = SCHEDULE_LATENCY
     p.timeout = 0.0
     p.island_sync = 0
-    p.reserved0 = 0
+    p.island_migration = 0  # E > 0: the islands of a query share their best every E steps (include/bioik_hip.h, ISLAND MIGRATION)
     for k, v in kw.items():
         if k == "mode" and isinstance(v, str):
             v = MODE_BY_NAME[v]

@@ -28,6 +28,7 @@ namespace bio_ik_kinematics_plugin {
 typedef std::function<void(const geometry_msgs::Pose&, const std::vector<double>&, moveit_msgs::MoveItErrorCodes&)> IKCallbackFn;
 
 struct BioIKParams : bio_ik::core::Settings {  // the kinematics.yaml keys of the reference (kinematics_plugin.cpp:243-328) + the additive gpu_* keys
+                                               // (gpu_island_migration among them: core::Settings)
     double rotation_scale = 0.5;
     bool position_only_ik = false;
     double center_joints_weight = 0, avoid_joint_limits_weight = 0, minimal_displacement_weight = 0;

@@ -61,6 +61,8 @@ struct Settings {  // IKParams (src/utils.h:64-85) as far as the device path rea
                                                                     // a batch of 2048 and more one; N > 0: exactly N
     bool gpu_island_sync = true;  // gpu_islands > 1 (and the _2 / _4 / _8 solver names): "any island succeeds => all stop", the reference's island loop
                                   // (ik_parallel.h:102, 160-178) in its deterministic form (bioik_solve_params::island_sync); false: every island to its own end
+    int gpu_island_migration = 0;  // E > 0: the islands of a pose share their best solution every E steps instead of being independent restarts
+                                   // (bioik_solve_params::island_migration: the rule, its cap, what it refuses); 0: off
     std::string gpu_fk = "exact";
     std::string gpu_schedule = "auto";     // "latency": every call as fast as it can be; "throughput": for callers that keep six or more batches in
                                            // flight (searchPositionIKBatchAsync): +30 % solves per second, an isolated call a quarter slower; "auto":
@@ -340,6 +342,7 @@ private:
         sp.dpos = settings_.dpos, sp.drot = settings_.drot, sp.dtwist = settings_.dtwist;
         sp.no_wipeout = settings_.no_wipeout ? 1 : 0;
         sp.island_sync = (settings_.gpu_island_sync && sp.islands != 1) ? 1 : 0;  // (islands 0 = BIOIK_ISLANDS_AUTO: sized per call, stopping each other)
+        sp.island_migration = settings_.gpu_island_migration;
         const size_t rows = n * K;
         tk->sol.resize(rows * V), tk->fit.resize(rows), tk->suc.resize(rows), tk->steps.resize(rows);
         // problem.timeout = t0 + timeout with t0 taken at entry (:448, :504): what the marshalling above has used is off the budget (one

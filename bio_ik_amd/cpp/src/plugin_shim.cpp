@@ -59,7 +59,8 @@ typedef struct bioik_plugin_settings {  // kinematics.yaml keys (kinematics_plug
     const int32_t* devices;
     double dpos, drot, dtwist;  // negative dpos / drot: not set (DBL_MAX)
     double rotation_scale, center_joints_weight, avoid_joint_limits_weight, minimal_displacement_weight;
-    int32_t gpu_island_sync, reserved;  // gpu_island_sync: "any island succeeds => all stop" (core::Settings)
+    int32_t gpu_island_sync, gpu_island_migration;  // gpu_island_sync: "any island succeeds => all stop"; gpu_island_migration: the islands share their best every E steps,
+                                                    // in the slot that was `reserved` (0 = off) (core::Settings)
 } bioik_plugin_settings;
 
 typedef struct bioik_plugin_goal {
@@ -89,6 +90,7 @@ static bio_ik::core::Settings coreSettings(const bioik_plugin_settings& s) {
     c.gpu_population = s.gpu_population, c.gpu_islands = s.gpu_islands, c.gpu_max_steps = s.gpu_max_steps;
     c.gpu_reproducible_calls = s.gpu_reproducible_calls != 0;
     c.gpu_island_sync = s.gpu_island_sync != 0;
+    c.gpu_island_migration = s.gpu_island_migration;
     c.devices.assign(s.devices, s.devices + s.n_devices);
     return c;
 }

@@ -711,6 +711,10 @@ DevSolveParams normalize_params(const bioik_solve_params& p, uint64_t first_quer
     o.generations = o.memetic ? 8 : 16;  // ik_evolution_2.cpp:349-351
     if (p.island_sync != 0 && p.island_sync != 1) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "island_sync must be 0 or 1");
     o.island_sync = ((p.island_sync || auto_islands) && o.islands > 1) ? 1 : 0;
+    if (p.island_migration < 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "island_migration must be >= 0");
+    if (p.island_migration > 0 && o.solver != 0)
+        throw Error(BIOIK_ERR_UNSUPPORTED, "island_migration > 0 needs a mode of the bio2 family: the gradient family (gd, gd_r, gd_c, jac) keeps no species to re-found");
+    o.island_migration = p.island_migration;
     return o;
 }
 

@@ -256,6 +256,9 @@ BIOIK_SOLVE_KERNELS(BIOIK_GLOBAL_)
 #undef BIOIK_GLOBAL_
 __global__ void k_select(SelectArgs a) { select_body(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(64) k_select_wave(SelectArgs a) { select_coop(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }  // a wavefront per query: calls of few queries with many islands
+// island migration between two launches of a solve (migrate_mark, migrate_coop): a lane per entry of the hand-over list, then a wavefront per query
+__global__ void __launch_bounds__(256) k_migrate_mark(MigrateArgs a) { migrate_mark(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ void __launch_bounds__(64) k_migrate(MigrateArgs a) { migrate_coop(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }
 // the k best distinct islands of every query, ranked (bioik_solve_batch_ranked): a wavefront per query, lane = island
 __global__ void __launch_bounds__(64) k_select_ranked(RankedArgs a) {
     extern __shared__ double lds[];
@@ -660,6 +663,7 @@ struct SolveLauncher {
     // the launches (plan_handovers)
     std::vector<int> handovers;  // the steps after which the unsolved units pass to the next launch (ascending)
     bool when_draining = false;  // ... or: whenever the chip runs empty (SolveArgs::resident), every unit from the step it is at
+    bool migrating = false;      // ... or: the boundaries of bioik_solve_params::island_migration, with k_migrate_mark and k_migrate between two launches
 
     SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, size_t n_, const double* seeds, const double* params, double* solutions, double* fitness, int32_t* success,
                   int32_t* steps, stream_t s, const SolveSwitches& w, unsigned int* err)
@@ -991,6 +995,14 @@ struct SolveLauncher {
     // BIOIK_SOLVE_TWO_PHASE=K (or K1,K2,... / init) forces hand-overs after those steps for any problem (0: never) -- the parity suites run every
     // mapping through it.
     void plan_handovers() {
+        // island migration: the boundaries E, 2E, ... < max_steps, BIOIK_MAX_MIGRATIONS at most, instead of every other plan (one island, or no boundary below max_steps: the
+        // call's plan is the one E = 0 takes)
+        if (sp.island_migration > 0 && sp.islands > 1 && sp.solver == 0 && sp.island_migration < sp.max_steps) {
+            if (be_stream_capturing(stream)) throw Error(BIOIK_ERR_UNSUPPORTED, "island_migration > 0 on a stream that is being captured into a hipGraph is not supported");
+            migrating = true;
+            for (long long k = sp.island_migration; k < (long long)sp.max_steps && handovers.size() < (size_t)BIOIK_MAX_MIGRATIONS; k += sp.island_migration) handovers.push_back((int)k);
+            return;
+        }
         if (sw.drain_test > 0 && sp.max_steps > 1 && sp.solver == 0) {
             when_draining = true;
             handovers.push_back(sp.max_steps);
@@ -1034,10 +1046,11 @@ struct SolveLauncher {
             const size_t carry_n = 9 * (size_t)(dp.n_ops > 0 ? dp.n_ops : 1) + 24;  // (solve_body: carry_n)
             const size_t list_bytes = (units * 4 + 63) / 64 * 64;
             const size_t list_off = (units * carry_n * 8 + 63) / 64 * 64, count_off = list_off + nh * list_bytes;
+            const size_t mark_off = count_off + nh * 64, mark_bytes = migrating ? list_bytes : 0;  // (migration: one word per unit, the number of the last boundary it was live at)
             void* ws_async = nullptr;
             AsyncFree ws_guard{ws_async, stream};
-            void* ws = scratch(1, count_off + nh * 64, ws_async);
-            be_zero_async((char*)ws + count_off, nh * 64, stream);
+            void* ws = scratch(1, mark_off + mark_bytes, ws_async);
+            be_zero_async((char*)ws + count_off, nh * 64 + mark_bytes, stream);  // (the counters and, behind them, the marks)
             if (!sw.handover_dump.empty())
                 if (FILE* f = std::fopen(sw.handover_dump.c_str(), "a")) {
                     std::fprintf(f, "%llu %zu %zu %llu %zu\n", (unsigned long long)(size_t)ws, list_off, count_off, (unsigned long long)units, carry_n);
@@ -1069,6 +1082,14 @@ struct SolveLauncher {
                     aj.carry_count = (unsigned int*)((char*)ws + count_off + j * 64);
                 }
                 launch(aj, lanes, lds_j);  // (always a grid of `units` workgroups: those beyond the list's length leave at once)
+                if (migrating && j < nh) {     // boundary j + 1: mark the units this launch handed over, then a wavefront per query rewrites its recipients' rows
+                    MigrateArgs m;
+                    m.islands = sp.islands, m.n_ops = dp.n_ops, m.exact = exact ? 1 : 0, m.mark = (int)j + 1, m.n = n;
+                    m.list = aj.carry_list, m.count = aj.carry_count, m.live = (int32_t*)((char*)ws + mark_off), m.rows = (double*)ws;
+                    if (sw.report) std::fprintf(stderr, "[bioik] launch: k_migrate_mark + k_migrate, boundary %d after step %d, islands %d\n", (int)j + 1, handovers[j], (int)sp.islands);
+                    LAUNCH(k_migrate_mark, migrate_mark(m, b_ * 256 + (uint64_t)p_tid()), (units + 255) / 256, 256, 0, stream, m);
+                    LAUNCH(k_migrate, migrate_coop(m, b_, p_tid()), n, 64, 0, stream, m);
+                }
             }
         }
     }
@@ -1744,6 +1765,31 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
     if (grid > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many elements for one launch");
     LAUNCH(k_eval_arith, arith_body(a, b_ * 256 + (uint64_t)p_tid()), grid, 256, 0, 0, a);
     be_d2h(out, dout.p, n * no * 8, 0);
+    be_sync(0);
+    API_END
+}
+
+int bioik_problem_carry_doubles(const bioik_problem* p) { return p ? 9 * (p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1) + 24 : BIOIK_ERR_INVALID_ARGUMENT; }
+int bioik_eval_migrate(bioik_problem* p, int32_t islands, size_t n_queries, const int32_t* live, double* rows) {
+    API_BEGIN
+    if (!p || islands < 1 || (n_queries && (!live || !rows))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n_queries == 0) return BIOIK_OK;
+    const uint64_t units = (uint64_t)n_queries * (uint64_t)islands;
+    if (units > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many (query, island) rows for one launch");
+    std::lock_guard<std::mutex> lock(p->mtx);
+    DeviceGuard on_device(p->model->device);
+    const size_t R = (size_t)bioik_problem_carry_doubles(p);
+    std::vector<int32_t> marks(units);  // (the solve's marks hold the boundary's number: here 1 for a live island)
+    for (uint64_t u = 0; u < units; u++) marks[u] = live[u] != 0 ? 1 : 0;
+    DevBuf dlive(units * 4), drows(units * R * 8);
+    be_h2d(dlive.p, marks.data(), units * 4, 0);
+    be_h2d(drows.p, rows, units * R * 8, 0);
+    MigrateArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.islands = islands, m.n_ops = p->host.dev.n_ops, m.exact = 1, m.mark = 1, m.n = n_queries;
+    m.live = dlive.as<int32_t>(), m.rows = drows.as<double>();
+    LAUNCH(k_migrate, migrate_coop(m, b_, p_tid()), n_queries, 64, 0, 0, m);
+    be_d2h(rows, drows.p, units * R * 8, 0);
     be_sync(0);
     API_END
 }

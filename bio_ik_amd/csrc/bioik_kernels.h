@@ -475,6 +475,67 @@ BIOIK_DEV void select_coop(const SelectArgs& a, uint64_t q, int lane) {
     }
 }
 
+// Island migration (bioik_solve_params::island_migration, include/bioik_hip.h): between two launches of a solve that is cut at the steps E, 2E, ... the islands of a
+// query that are still running share the best solution among them.  What an island is between two launches is its carry row (solve_epilogue writes it, solve_init
+// reads it), so the rule is an edit of rows: two small kernels per boundary, the launches around them the only synchronisation.
+//   migrate_mark  one lane per entry of the boundary's hand-over list: live[unit] = mark (the boundary's number, 1, 2, ...; the array is zeroed once per call, so
+//                 what earlier boundaries wrote is smaller and never taken for this one's).  The list's ORDER is the order the islands finished in; the marks have none.
+//   migrate_coop  ONE WAVEFRONT per query (all 64 lanes call it), lanes over the islands i, i + 64, ...: the donor is the live island with the least solution fitness
+//                 (word 20 of its bookkeeping), equal values the LOWER island; every live island whose own figure is strictly greater is a recipient, and its species
+//                 of rank 1 is re-founded as a wipe-out re-founds it (solve_species_and_checks) with the donor's solution for the uniform draws -- both elites the
+//                 donor's solution, both gradients zero, exact FK: both elites' fitness words the donor's figure.  Lanes over ops for the rows.
+struct MigrateArgs {
+    int islands, n_ops;
+    int exact, mark;
+    uint64_t n;                        // queries
+    const int32_t* list;               // migrate_mark: the hand-over list of the boundary ...
+    const unsigned int* count;         // ... and its length
+    int32_t* live;                     // [n * islands]
+    double* rows;                      // [n * islands][9 M + 24]: SolveArgs::carry
+};
+BIOIK_DEV void migrate_mark(const MigrateArgs& a, uint64_t i) {
+    if (i >= (uint64_t)p_atomic_load(a.count) || i >= a.n * (uint64_t)a.islands) return;
+    const int32_t unit = p_load_device(a.list + i);
+    if (unit >= 0 && (uint64_t)unit < a.n * (uint64_t)a.islands) p_store_device(a.live + unit, (int32_t)a.mark);
+}
+BIOIK_DEV void migrate_coop(const MigrateArgs& a, uint64_t q, int lane) {
+    const int M = a.n_ops > 0 ? a.n_ops : 1, BF = 4 * M;
+    const uint64_t R = (uint64_t)(2 * BF + M + 24), u0 = q * (uint64_t)a.islands;
+    const int st = 2 * BF + M;  // the bookkeeping block of a row
+    double df = P_INF;          // the donor: the least solution fitness of this lane's live islands, then of the wavefront's
+    int di = 0x7fffffff;
+    for (int i = lane; i < a.islands; i += 64) {
+        if (p_load_device(a.live + u0 + i) != a.mark) continue;
+        const double f = p_load_device(a.rows + (u0 + i) * R + st + 20);
+        if (f < df || (f == df && i < di)) df = f, di = i;
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double of = p_shfl_xor(df, m);
+        const int oi = p_shfl_xor(di, m);
+        if (of < df || (of == df && oi < di)) df = of, di = oi;
+    }
+    if (di == 0x7fffffff) return;  // no live island (wavefront-uniform)
+    const double* const donor = a.rows + (u0 + (uint64_t)di) * R;
+    for (int base = 0; base < a.islands; base += 64) {
+        const int i = base + lane;
+        bool rec = false;
+        if (i < a.islands && p_load_device(a.live + u0 + i) == a.mark) rec = p_load_device(a.rows + (u0 + i) * R + st + 20) > df;
+        unsigned long long todo = p_ballot(rec);
+        while (todo != 0ull) {  // (wavefront-uniform)
+            const int j = base + __builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            double* const c = a.rows + (u0 + (uint64_t)j) * R;
+            double* const cb = c + BF;  // the species of rank 1
+            for (int k = lane; k < a.n_ops; k += 64) {
+                const double v = p_load_device(donor + 2 * BF + k);
+                p_store_device(cb + k, v), p_store_device(cb + M + k, 0.0);
+                p_store_device(cb + 2 * M + k, v), p_store_device(cb + 3 * M + k, 0.0);
+            }
+            if (lane == 0 && a.exact) p_store_device(c + st + 9, df), p_store_device(c + st + 10, df);
+        }
+    }
+}
+
 // The k best DISTINCT islands of every query, ranked (bioik_solve_batch_ranked): ONE WAVEFRONT per query, lane = island (islands <= 64), over the per-island
 // arrays a solve without the fused reduction leaves behind.
 //   order     ik_parallel.h:220-269 read as a total order: the islands that passed by ascending isl_fitness (which holds the secondary term of a success, as

@@ -153,4 +153,5 @@ struct DevSolveParams {
     int32_t schedule;           // BIOIK_SCHEDULE_* (host side only: what the launcher optimises for)
     int32_t child_pairs;        // 1: a lane reproduces and scores its children two at a time (two independent dependency chains per lane)
     int32_t island_sync;        // 1: the islands of a query stop once one of them has passed the success test (bioik_solve_params::island_sync)
+    int32_t island_migration;   // E > 0: the islands of a query share their best every E steps (host side only: SolveLauncher::plan_handovers; the solve kernels never read it)
 };

@@ -31,7 +31,7 @@ class _Settings(C.Structure):  # bioik_plugin_settings (cpp/src/plugin_shim.cpp)
                 ("gpu_reproducible_calls", C.c_int32), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32)),
                 ("dpos", C.c_double), ("drot", C.c_double), ("dtwist", C.c_double), ("rotation_scale", C.c_double),
                 ("center_joints_weight", C.c_double), ("avoid_joint_limits_weight", C.c_double), ("minimal_displacement_weight", C.c_double),
-                ("gpu_island_sync", C.c_int32), ("reserved", C.c_int32)]
+                ("gpu_island_sync", C.c_int32), ("gpu_island_migration", C.c_int32)]
 
 
 class _WireGoal(C.Structure):  # bioik_plugin_goal
@@ -100,6 +100,7 @@ DEFAULT_PARAMS = {
     # additive keys of the GPU build
     "gpu_population": 128, "gpu_fk": "exact", "gpu_islands": 0, "gpu_max_steps": 64, "gpu_devices": None, "gpu_reproducible_calls": False, "gpu_schedule": "auto",
     "gpu_island_sync": True,  # islands stop each other (the reference's island loop); False: every island to its own end
+    "gpu_island_migration": 0,  # E > 0: the islands of a pose share their best solution every E steps (bioik_solve_params::island_migration); 0: independent islands
     "gpu_solutions": 8, "gpu_solution_distance": 0.1,  # searchPositionIKRanked: solutions per pose and how far apart (max over the joints, rad / m)
 }
 
@@ -136,7 +137,8 @@ class BioIKKinematicsPlugin:
                       gpu_reproducible_calls=int(bool(p["gpu_reproducible_calls"])), n_devices=len(devices), devices=abi.iptr(devices),
                       dpos=float(p["dpos"]), drot=float(p["drot"]), dtwist=float(p["dtwist"]), rotation_scale=float(p["rotation_scale"]),
                       center_joints_weight=float(p["center_joints_weight"]), avoid_joint_limits_weight=float(p["avoid_joint_limits_weight"]),
-                      minimal_displacement_weight=float(p["minimal_displacement_weight"]), gpu_island_sync=int(bool(p["gpu_island_sync"])))
+                      minimal_displacement_weight=float(p["minimal_displacement_weight"]), gpu_island_sync=int(bool(p["gpu_island_sync"])),
+                      gpu_island_migration=int(p["gpu_island_migration"]))
         return s, devices
 
     def _push_params(self):

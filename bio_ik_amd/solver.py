@@ -29,6 +29,7 @@ EXPORTS = [
     "bioik_solve_batch_device", "bioik_eval_fk", "bioik_eval_fitness", "bioik_eval_approximator", "bioik_eval_reproduce",
     "bioik_eval_check", "bioik_stream_fitness_device", "bioik_solve_batch_submit", "bioik_solve_batch_wait", "bioik_debug_reload_switches", "bioik_eval_arith",
     "bioik_resolve_islands", "bioik_solve_batch_ranked", "bioik_solve_batch_ranked_device", "bioik_sincos_domain", "bioik_sincos_small_bound",
+    "bioik_problem_carry_doubles", "bioik_eval_migrate",
 ]
 
 
@@ -67,6 +68,8 @@ def _declare(L):
     if hasattr(L, "bioik_eval_arith"):
         L.bioik_eval_arith.argtypes = [C.c_int, C.c_int, C.c_size_t, _pd, _pd]
     L.bioik_stream_fitness_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bioik_problem_carry_doubles.argtypes = [C.c_void_p]
+    L.bioik_eval_migrate.argtypes = [C.c_void_p, C.c_int32, C.c_size_t, _pi, _pd]
     L.bioik_resolve_islands.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, _pi, _pi]
     L.bioik_solve_batch_ranked.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, _pd, _pd, _pd, _pd, _pi, _pi, _pi]
     L.bioik_solve_batch_ranked_device.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
@@ -351,6 +354,18 @@ class HipSolver:
         grads = np.zeros((population, self.D))
         self._chk(self.L.bioik_eval_reproduce(self.problem, int(population), int(rng_key), int(species), int(generation), _d(par), _d(genes), _d(grads)))
         return genes, grads
+
+    def carry_doubles(self):
+        """bioik_problem_carry_doubles: doubles of an island's row between two launches (include/bioik_hip.h, bioik_eval_migrate: the layout)"""
+        return int(self.L.bioik_problem_carry_doubles(self.problem))
+
+    def migrate(self, live, rows):
+        """bioik_eval_migrate: the island-migration rule of a boundary on rows [n][islands][carry_doubles] with live [n][islands] -> the rows after it"""
+        lv = np.ascontiguousarray(live, dtype=np.int32)
+        n, islands = lv.shape
+        out = np.array(_f64(rows).reshape(n, islands, self.carry_doubles()), copy=True, order="C")
+        self._chk(self.L.bioik_eval_migrate(self.problem, islands, n, _i(lv), _d(out)))
+        return out
 
     def check(self, params, seed, goal_params, genes):
         g = _f64(genes).reshape(-1, self.D)

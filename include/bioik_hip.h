@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_batch_ranked, bioik_solve_batch_ranked_device (the k best distinct islands of every query).
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_params::island_migration in the slot of `reserved0` (0, what every caller of 6 wrote there, is off),
+                               BIOIK_MAX_MIGRATIONS, bioik_eval_migrate, bioik_problem_carry_doubles (the islands of a query share their best every E steps).
+                               6, additions that break no caller of 6: bioik_solve_batch_ranked, bioik_solve_batch_ranked_device (the k best distinct islands of every query).
                                6 (round 6): bioik_resolve_islands (the island count BIOIK_ISLANDS_AUTO gives a call of n queries, for callers that shard a request themselves);
                                a rendezvous time-out inside a workgroup is BIOIK_ERR_HIP for its call; a line-search candidate with a joint value of magnitude >= bioik_sincos_domain()
                                (2^47; 1e300 until the shared sincos had a stated domain) is no candidate: no solve returns such a value for a variable without bounds.  A joint's half angle
@@ -259,8 +261,27 @@ typedef struct bioik_solve_params {
                                 step, `steps` is that step's number.  (On the device an island leaves as soon as it sees that another one has passed at
                                 an earlier or the same step -- its own result can no longer be chosen -- so WHEN it leaves depends on timing, WHAT is
                                 returned does not.)  New key "gpu_island_sync". */
-    int32_t reserved0;
+    int32_t island_migration; /* E (the slot of `reserved0`; 0 = off, the default; < 0: BIOIK_ERR_INVALID_ARGUMENT): the islands of a query share their best solution
+                                every E steps -- ISLAND MIGRATION below.  New key "gpu_island_migration". */
 } bioik_solve_params;
+
+/* ISLAND MIGRATION (bioik_solve_params::island_migration = E > 0, more than one island once BIOIK_ISLANDS_AUTO is resolved, a mode of the bio2 family).  Without
+ * it the islands of a query are independent restarts; with it the solve is cut at the steps E, 2E, 3E, ... < max_steps -- at most BIOIK_MAX_MIGRATIONS of them,
+ * behind the last one the islands run independently to the end -- and at every such BOUNDARY, per query:
+ *   live       the islands handed over at the boundary: neither solved, nor out of time, nor overtaken (island_sync) after the boundary's step.
+ *   donor      the live island with the least solution fitness, equal values: the lower island index.  A query with fewer than two live islands is left alone.
+ *   recipient  every other live island whose own solution fitness is STRICTLY greater than the donor's.  Its species of rank 1 (the worse of the two after the step's
+ *              ranking) is re-founded exactly as a wipe-out re-founds it (ik_evolution_2.cpp:617-645), with the donor's solution in place of the uniform draws: both
+ *              elites take the donor's solution for every op, both gradients are zeroed, and under BIOIK_FK_EXACT the two elites' fitness words take the donor's
+ *              solution fitness (under BIOIK_FK_LINEAR every generation re-evaluates them, as after a wipe-out).  Every other word of the recipient -- its rank-0
+ *              species, its own solution, the rest of its bookkeeping -- stays; the donor is only read.
+ * The result is a function of (seed, query, islands, parameters): a boundary is a kernel boundary, the order in which islands reach it takes no part.  The cap is part of
+ * that contract (the host queues every launch of a call up front; once every island has finished the remaining launches are empty grids, each a launch latency on the
+ * one-pose calls this is for).  The migration plan replaces the launcher's other plans (its hand-overs, BIOIK_SOLVE_TWO_PHASE); the mapping switches keep working; the
+ * islands are reduced by k_select / k_select_ranked behind the last launch.  island_sync, timeout, ranked calls (row 0 stays the plain call's answer for the same
+ * parameters) work unchanged.  E > 0 with one island or E >= max_steps is the call E = 0 is: the same launches.  Refused with BIOIK_ERR_UNSUPPORTED: E > 0 with a mode
+ * of the gradient family (gd, gd_r, gd_c, jac), and E > 0 on a stream that is being captured into a hipGraph. */
+#define BIOIK_MAX_MIGRATIONS 8
 
 /* defaults: bio2_memetic, exact FK, population 128, 1 island, 64 steps, no timeout, seed 0, dpos=drot=off, dtwist=1e-5 */
 void bioik_default_solve_params(bioik_solve_params* p);
@@ -385,7 +406,7 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
  * share a buffer must not overlap: launch them on one stream, or wait for one before launching the next (or capture from different streams).
  * The one eager call before a capture must take the same plan as the captured call -- the same queries, islands, mode, population and steps,
  * under the same BIOIK_SOLVE_* switches: a call in one launch sizes other scratch than one with hand-overs.  Destroy the graphs before the
- * handle. */
+ * handle.  A call with island_migration > 0 that would migrate (more than one island, E < max_steps) is NOT capturable: BIOIK_ERR_UNSUPPORTED on a capturing stream. */
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds,
                              const double* d_goal_params, double* d_solutions, double* d_fitness,
                              int32_t* d_success, int32_t* d_steps, void* hip_stream);
@@ -442,6 +463,20 @@ int bioik_eval_reproduce(bioik_problem* p, int population, uint32_t rng_key, int
 /* Problem::checkSolutionActiveVariables (problem.cpp:259-341) on the exact-FK pose of n genotypes. */
 int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seed,
                      const double* goal_params, const double* genes, int32_t* ok);
+
+/* The migration rule of bioik_solve_params::island_migration on rows the caller supplies: exactly the kernel a solve runs at a boundary (k_migrate), under
+ * BIOIK_FK_EXACT.  rows [n_queries][islands][bioik_problem_carry_doubles(p)], rewritten in place; live [n_queries][islands], non-zero = the island is live.
+ * A ROW is what an unsolved island is between two steps, R = 9 M + 24 doubles with M = max(ops of the problem, 1):
+ *   [0, 4M)       the species of rank 0: elite 0's genes [M], its gradient [M], elite 1's genes [M], its gradient [M]  (one value per op; untouched)
+ *   [4M, 8M)      the species of rank 1, the same four blocks                                                        (WRITTEN in a recipient)
+ *   [8M, 9M)      the island's solution, one value per op                                                            (READ in the donor)
+ *   [9M, 9M + 24) bookkeeping: words 0-7 the species of rank 0 and 8-15 the species of rank 1 as (fitness, fitness of elite 0, of elite 1, id, slot, buffer,
+ *                 improved, ok) -- words 9 and 10 are WRITTEN in a recipient --, 16 the step count, 17-19 scratch, 20 the solution's fitness (READ in every live
+ *                 island: what donor and recipients are chosen by), 21 its success flag, 22-23 the deadline.
+ * Every word not marked WRITTEN comes back unchanged, and so does every row of an island that is no recipient.  Host pointers. */
+int bioik_problem_carry_doubles(const bioik_problem* p);
+int bioik_eval_migrate(bioik_problem* p, int32_t islands, size_t n_queries, const int32_t* live /*[n_queries][islands]*/,
+                       double* rows /*[n_queries][islands][carry_doubles], in place*/);
 
 /* The shared arithmetic of both sides of the boundary, one function at a time on the device (bio_ik_amd/csrc/bioik_sincos.h, bioik_fused.h, bioik_acos.h -- the
  * headers the kernels and the test-suite's CPU checker both include): so that a test can hold them against an INDEPENDENT high-precision
