@@ -315,6 +315,15 @@ static void launch_kernel(SolveKernel kind, const SolveArgs& args, uint64_t grid
     }
 }
 
+// The arrays of one solve call as an entry point was given them, host or device pointers alike: a parameter bundle and nothing more
+struct SolveArrays {
+    size_t n;  // queries
+    const double *seeds, *goal_params;
+    double *solutions, *fitness;
+    int32_t *success, *steps;
+    int32_t* count;  // ranked calls (bioik_solve_batch_ranked): the distinct solutions returned per query; null otherwise
+};
+
 // ------------------------------------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------------------------------------
@@ -344,10 +353,9 @@ struct bioik_problem {
         // the solve in flight on this slot, if any: where its results go when it completes
         bool pending = false;
         uint64_t ticket = 0;
-        size_t n = 0, o_sol = 0, o_fit = 0, o_suc = 0, o_steps = 0, o_cnt = 0;
+        size_t o_sol = 0, o_fit = 0, o_suc = 0, o_steps = 0, o_cnt = 0;
         size_t rows = 1;  // result rows per query (a ranked solve: k)
-        double *solutions = nullptr, *fitness = nullptr;
-        int32_t *success = nullptr, *steps = nullptr, *count = nullptr;  // (count: ranked solves only)
+        SolveArrays caller{};  // (its inputs were copied at the submission: only n and the result arrays are used)
         // a solve of this slot that ended in a device error: remembered for ITS ticket's wait (the slot itself is free again)
         uint64_t failed_ticket = 0;
         int failed_code = 0;
@@ -469,40 +477,40 @@ struct SolveSwitches {
     bool manual() const { return threads > 0 || store_children >= 0 || child_pairs >= 0 || species_parallel >= 0 || columnless >= 0; }
 };
 static SolveSwitches parse_switches() {
-    SolveSwitches w;
+    SolveSwitches w;  // (every default is written once, above: a switch that is not set keeps its field)
     auto geti = [](const char* name, int unset) {
         const char* e = std::getenv(name);
         return e ? std::atoi(e) : unset;
     };
-    w.threads = geti("BIOIK_SOLVE_THREADS", 0);
+    w.threads = geti("BIOIK_SOLVE_THREADS", w.threads);
     if (std::getenv("BIOIK_SOLVE_THREADS") && w.threads <= 0) w.threads = 64;
-    w.store_children = geti("BIOIK_SOLVE_STORE_CHILDREN", -1);
-    w.child_pairs = geti("BIOIK_SOLVE_CHILD_PAIRS", -1);
-    w.species_parallel = geti("BIOIK_SOLVE_SPECIES_PARALLEL", -1);
-    w.columnless = geti("BIOIK_SOLVE_COLUMNLESS", -1);
+    w.store_children = geti("BIOIK_SOLVE_STORE_CHILDREN", w.store_children);
+    w.child_pairs = geti("BIOIK_SOLVE_CHILD_PAIRS", w.child_pairs);
+    w.species_parallel = geti("BIOIK_SOLVE_SPECIES_PARALLEL", w.species_parallel);
+    w.columnless = geti("BIOIK_SOLVE_COLUMNLESS", w.columnless);
     if (const char* e = std::getenv("BIOIK_SOLVE_GENERAL")) w.general_set = true, w.general = std::atoi(e) != 0;
     w.report = std::getenv("BIOIK_SOLVE_REPORT") != nullptr;
     w.three_waves = std::getenv("BIOIK_SOLVE_THREE_WAVES") != nullptr;
     w.four_waves = std::getenv("BIOIK_SOLVE_FOUR_WAVES") != nullptr;
     w.no_joint = std::getenv("BIOIK_SOLVE_NO_JOINT") != nullptr;
-    w.dense_handover = geti("BIOIK_SOLVE_DENSE_HANDOVER", 0);
-    w.drain_below = geti("BIOIK_SOLVE_DRAIN_BELOW", 1024);
-    w.drain_throughput = geti("BIOIK_SOLVE_DRAIN_THROUGHPUT", 1) != 0;
-    w.drain_below_throughput = geti("BIOIK_SOLVE_DRAIN_BELOW_THROUGHPUT", 512);
-    w.drain_min_units = geti("BIOIK_SOLVE_DRAIN_MIN_UNITS", 1025);
-    w.drain_min_steps = geti("BIOIK_SOLVE_DRAIN_MIN_STEPS", 4);
-    w.drain_test = geti("BIOIK_SOLVE_DRAIN_TEST", 0);
-    w.sort_key_drop = geti("BIOIK_SOLVE_SORT_KEY_DROP", 10);
-    w.preselect = geti("BIOIK_SOLVE_PRESELECT", 1) != 0 ? 1 : 0;
-    w.tie_test_bits = geti("BIOIK_SOLVE_TIE_TEST_BITS", 0);
+    w.dense_handover = geti("BIOIK_SOLVE_DENSE_HANDOVER", w.dense_handover);
+    w.drain_below = geti("BIOIK_SOLVE_DRAIN_BELOW", w.drain_below);
+    w.drain_throughput = geti("BIOIK_SOLVE_DRAIN_THROUGHPUT", w.drain_throughput) != 0;
+    w.drain_below_throughput = geti("BIOIK_SOLVE_DRAIN_BELOW_THROUGHPUT", w.drain_below_throughput);
+    w.drain_min_units = geti("BIOIK_SOLVE_DRAIN_MIN_UNITS", w.drain_min_units);
+    w.drain_min_steps = geti("BIOIK_SOLVE_DRAIN_MIN_STEPS", w.drain_min_steps);
+    w.drain_test = geti("BIOIK_SOLVE_DRAIN_TEST", w.drain_test);
+    w.sort_key_drop = geti("BIOIK_SOLVE_SORT_KEY_DROP", w.sort_key_drop);
+    w.preselect = geti("BIOIK_SOLVE_PRESELECT", w.preselect) != 0 ? 1 : 0;
+    w.tie_test_bits = geti("BIOIK_SOLVE_TIE_TEST_BITS", w.tie_test_bits);
     if (w.tie_test_bits < 0 || w.tie_test_bits > 52) w.tie_test_bits = 0;
-    w.capture_one_launch = geti("BIOIK_SOLVE_CAPTURE_ONE_LAUNCH", 0) != 0;
-    w.memset_nodes = geti("BIOIK_SOLVE_MEMSET_NODES", 0) != 0;
-    w.autotune = geti("BIOIK_SOLVE_AUTOTUNE", 1);
-    w.helped = geti("BIOIK_SOLVE_HELPED", 1024);
-    w.debug_flags = geti("BIOIK_SOLVE_DEBUG_FLAGS", 0);
-    w.fused_select = geti("BIOIK_SOLVE_FUSED_SELECT", 1);
-    if (w.sort_key_drop < 10 || w.sort_key_drop > 52) w.sort_key_drop = 10;
+    w.capture_one_launch = geti("BIOIK_SOLVE_CAPTURE_ONE_LAUNCH", w.capture_one_launch) != 0;
+    w.memset_nodes = geti("BIOIK_SOLVE_MEMSET_NODES", w.memset_nodes) != 0;
+    w.autotune = geti("BIOIK_SOLVE_AUTOTUNE", w.autotune);
+    w.helped = geti("BIOIK_SOLVE_HELPED", w.helped);
+    w.debug_flags = geti("BIOIK_SOLVE_DEBUG_FLAGS", w.debug_flags);
+    w.fused_select = geti("BIOIK_SOLVE_FUSED_SELECT", w.fused_select);
+    if (w.sort_key_drop < 10 || w.sort_key_drop > 52) w.sort_key_drop = SolveSwitches().sort_key_drop;
     if (const char* e = std::getenv("BIOIK_SOLVE_TWO_PHASE")) {
         w.two_phase_set = true;
         w.two_phase_init = std::strcmp(e, "init") == 0;
@@ -580,9 +588,21 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
-static size_t lds_bytes(const bioik_problem* p, int nthreads, int lambda, int child_cols = 1, int groups = 1, int slot_sets = 1, bool exact = false, bool fit_park = false, bool helped = false) {
+// The two lane mappings with a kernel compiled for exactly them, both with the children computed where they are read and walked in pairs:
+static constexpr LaneMapping kWavePerSpecies{128, 1, 1, 1, 1};  // 128 lanes, a wavefront per species (k_solve_lean_cl4 and its helped build)
+static constexpr LaneMapping kHalves{64, 1, 1, 1, 1};           // 64 lanes, the species on the halves of one wavefront (k_solve_lean_cl64w4, k_solve_lean_clj4)
+static LaneMapping mapping_of(const DevSolveParams& sp, int lanes) { return LaneMapping{lanes, sp.species_parallel, sp.child_cols, sp.child_pairs, sp.columnless}; }
+static void set_mapping(DevSolveParams& sp, int& lanes, const LaneMapping& m) {
+    lanes = m.lanes, sp.species_parallel = m.species_parallel, sp.child_cols = m.child_cols, sp.child_pairs = m.child_pairs, sp.columnless = m.columnless;
+}
+// the LDS layout of a solve's workgroup under a lane mapping: solve_layout (bioik_kernels.h), the function solve_setup takes its own layout from
+static LdsLayout solve_layout(const DevProblem& d, int lambda, bool exact, const LaneMapping& m, bool helped = false) {
+    return solve_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, d.n_secondary > 0, lambda, exact, m, helped);
+}
+// the dynamic LDS of a function-level kernel of `nth` lanes, in bytes: the layout the eval_*_body / stream_fitness_body functions index (bioik_kernels.h)
+static size_t eval_lds_bytes(const bioik_problem* p, int nth) {
     const DevProblem& d = p->host.dev;
-    return (size_t)make_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, nthreads, lambda, d.n_secondary > 0 ? (exact ? 2 : 1) : 0, child_cols, groups, slot_sets, fit_park ? 1 : 0, lambda > 0 ? 1 : 0, helped ? 1 : 0).total * 8;  // (lambda > 0: a solve's layout; the function-level kernels keep their own)
+    return (size_t)make_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, nth, 0, 0).total * 8;
 }
 // The dynamic LDS of a function-level launch (a kernel of BIOIK_WIDE_LDS_KERNELS): a problem whose need is beyond a CU's LDS is refused before anything is
 // allocated or launched, a need above 64 KiB is allowed for the kernel.  (Every problem bioik_problem_create accepts runs or is refused here: 64 tips x 64 ops
@@ -638,13 +658,8 @@ static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t st
 struct SolveLauncher {
     bioik_problem* p;
     DevSolveParams sp;
+    const SolveArrays call;  // (device pointers, or the page-locked arena of a host-pointer call)
     const size_t n;
-    const double* d_seeds;
-    const double* d_params;
-    double* d_solutions;
-    double* d_fitness;
-    int32_t* d_success;
-    int32_t* d_steps;
     stream_t stream;
     const SolveSwitches& sw;
     unsigned int* error_word;
@@ -659,16 +674,14 @@ struct SolveLauncher {
     int nth = 0, groups = 1;
     size_t lds = 0;
     bool exact = false, quat = false, manual = false, can_columnless = false, prefer_cl4 = false, small_sec_cl4 = false, small_linear = false, throughput = false, dense_ok = false,
-         capturing = false, latency_drain = false, dense = false, lean = false, halves_ok = false;
+         capturing = false, latency_drain = false, dense = false, lean = false, halves_ok = false, halves_shape = false, dense_shape = false;
     // the launches (plan_handovers)
     std::vector<int> handovers;  // the steps after which the unsolved units pass to the next launch (ascending)
     bool when_draining = false;  // ... or: whenever the chip runs empty (SolveArgs::resident), every unit from the step it is at
     bool migrating = false;      // ... or: the boundaries of bioik_solve_params::island_migration, with k_migrate_mark and k_migrate between two launches
 
-    SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, size_t n_, const double* seeds, const double* params, double* solutions, double* fitness, int32_t* success,
-                  int32_t* steps, stream_t s, const SolveSwitches& w, unsigned int* err)
-        : p(p_), sp(sp_in), n(n_), d_seeds(seeds), d_params(params), d_solutions(solutions), d_fitness(fitness), d_success(success), d_steps(steps), stream(s), sw(w),
-          error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus) {
+    SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t s, const SolveSwitches& w, unsigned int* err)
+        : p(p_), sp(sp_in), call(arrays), n(arrays.n), stream(s), sw(w), error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus) {
         if (dp.n_secondary > 0 && sp.lambda < 2) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "population must be >= 2 when secondary goals are present");
         units = (uint64_t)n * sp.islands;
         if (units > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many (query, island) units for one launch: split the batch");
@@ -683,12 +696,14 @@ struct SolveLauncher {
 
     // scratch of this solve: the handle's persistent buffer for (stream, purpose), or -- while the stream is being captured and the buffer would have to
     // grow, or for the sixty-fifth stream of a handle -- a stream-ordered allocation released on every path out (null: nothing to release)
-    void* scratch(int purpose, size_t bytes, void*& async_owned) {
+    // (*entry: the handle's record of (stream, purpose), if it holds one -- whether or not the pointer returned is that record's buffer)
+    void* scratch(int purpose, size_t bytes, void*& async_owned, bioik_problem::Scratch** entry = nullptr) {
         const auto key = std::make_pair(stream, purpose);
         auto it = p->scratch.find(key);
         if (it == p->scratch.end() && p->scratch.size() < 128) it = p->scratch.emplace(key, bioik_problem::Scratch{}).first;
         if (it != p->scratch.end()) {
             bioik_problem::Scratch& sc = it->second;
+            if (entry) *entry = &sc;
             if (be_stream_capturing(stream)) {
                 for (const auto& r : p->retired_scratch)
                     if (r.stream == stream && r.purpose == purpose && r.capacity >= bytes) return r.base;  // (pinned by an earlier capture on this stream)
@@ -717,7 +732,7 @@ struct SolveLauncher {
     // itself (`fused`: SolveArgs::island_done; one launch in all) or by k_select behind the solve's launches (select_islands)
     void result_arrays(SolveArgs& args, bool fused) {
         if (sp.islands == 1) {
-            args.solutions = d_solutions, args.fitness = d_fitness, args.success = d_success, args.steps = d_steps;
+            args.solutions = call.solutions, args.fitness = call.fitness, args.success = call.success, args.steps = call.steps;
             return;
         }
         const size_t per = (size_t)dp.V * 8 + 8 + 4 + 4;
@@ -731,12 +746,9 @@ struct SolveLauncher {
             auto it = p->scratch.find(std::make_pair(stream, 0));
             if (it != p->scratch.end() && !it->second.pinned && it->second.ctl_base == it->second.base) prior = it->second.ctl_n;
         }
-        char* w = (char*)scratch(0, ctl_bytes(std::max(prior, ctl_n)) + units * per + 64 + n * 4, island_ws);
         bioik_problem::Scratch* sc = nullptr;
-        {
-            auto it = p->scratch.find(std::make_pair(stream, 0));
-            if (it != p->scratch.end() && it->second.base == (void*)w) sc = &it->second;
-        }
+        char* w = (char*)scratch(0, ctl_bytes(std::max(prior, ctl_n)) + units * per + 64 + n * 4, island_ws, &sc);
+        if (sc && sc->base != (void*)w) sc = nullptr;  // (a retired buffer: pinned, no eager call's)
         if (fused) {
             size_t have = !capturing_now && sc && sc->ctl_base == (void*)w ? sc->ctl_n : 0;
             if (have < n) {  // a new buffer, a larger call, a call of the other kind in between, or a capture: set the words up (the kernels keep them from then on)
@@ -748,7 +760,7 @@ struct SolveLauncher {
             if (sw.report) std::fprintf(stderr, "[bioik] islands: reduced by the last island in the launch (control words of %zu queries)\n", have);
             if (sp.island_sync) args.first_success = (unsigned int*)w;
             args.island_done = (unsigned int*)(w + have * 4);
-            args.final_solutions = d_solutions, args.final_fitness = d_fitness, args.final_success = d_success, args.final_steps = d_steps;
+            args.final_solutions = call.solutions, args.final_fitness = call.fitness, args.final_success = call.success, args.final_steps = call.steps;
             w += ctl_bytes(have);
             fused_select = true;
         } else if (sc) {
@@ -766,7 +778,7 @@ struct SolveLauncher {
     void select_islands(const SolveArgs& args) {  // ik_parallel.h:220-269: the best island of every query
         if (ranked) {  // ... or its k best distinct ones, in that order (islands = 1: the solve wrote the row itself, the kernel adds the count)
             RankedArgs r = *ranked;
-            r.pb = p->pb(), r.islands = sp.islands, r.V = dp.V, r.D = dp.D, r.n = n, r.seeds = d_seeds;
+            r.pb = p->pb(), r.islands = sp.islands, r.V = dp.V, r.D = dp.D, r.n = n, r.seeds = call.seeds;
             r.isl_solutions = args.solutions, r.isl_fitness = args.fitness, r.isl_success = args.success, r.isl_steps = args.steps;
             const size_t lds_r = r.min_distance >= 0.0 && sp.islands > 1 ? (size_t)dp.D * 64 * 8 : 0;  // (at most 63 x 64 doubles: 31.5 KiB)
             if (sw.report) std::fprintf(stderr, "[bioik] launch: k_select_ranked, islands %d, k %d, %zu B of LDS\n", (int)sp.islands, (int)r.k, lds_r);
@@ -778,7 +790,7 @@ struct SolveLauncher {
         s.islands = sp.islands, s.V = dp.V, s.n = n;
         s.sync = sp.island_sync, s.pad = 0;
         s.isl_solutions = args.solutions, s.isl_fitness = args.fitness, s.isl_success = args.success, s.isl_steps = args.steps;
-        s.solutions = d_solutions, s.fitness = d_fitness, s.success = d_success, s.steps = d_steps;
+        s.solutions = call.solutions, s.fitness = call.fitness, s.success = call.success, s.steps = call.steps;
         const bool wave = sp.islands >= 8 && n <= 4096 && sw.fused_select >= 0;
         if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, islands %d\n", wave ? "k_select_wave" : "k_select", (int)sp.islands);
         if (wave) LAUNCH(k_select_wave, select_coop(s, b_, p_tid()), n, 64, 0, stream, s);
@@ -789,7 +801,7 @@ struct SolveLauncher {
         const size_t lds_point = (size_t)make_point_layout(dp.n_ops, dp.V, dp.P, dp.T, dp.n_slots, dp.D, 64).total * 8;
         if (lds_point > 64 * 1024) throw Error(BIOIK_ERR_UNSUPPORTED, "problem too large for the gd / jac kernels (more than 64 KiB of LDS per query)");
         SolveArgs pa;
-        pa.pb = p->pb(), pa.sp = sp, pa.seeds = d_seeds, pa.params = d_params;
+        pa.pb = p->pb(), pa.sp = sp, pa.seeds = call.seeds, pa.params = call.goal_params;
         result_arrays(pa, false);
         pa.phase_cycles = nullptr;
         set_deadline(p, sp, stream, pa);
@@ -797,6 +809,7 @@ struct SolveLauncher {
         launch_kernel(SolveKernel::k_solve_point, pa, units, 64, lds_point, stream);
         select_islands(pa);
     }
+    size_t lds_need(const LaneMapping& m, bool helped = false) const { return (size_t)solve_layout(dp, sp.lambda, exact, m, helped).total * 8; }  // bytes of LDS per workgroup
     void choose_mapping() {
         // Mapping of a (query, island) onto lanes.  Candidates: 128 lanes (one wavefront per species) with every child kept in LDS
         // and evaluated in pairs / kept / re-derived from the RNG, or 64 lanes (one wavefront, the species one after the other).  A CU
@@ -805,19 +818,24 @@ struct SolveLauncher {
         // what limits residency (C3, C4: measured +7 % and +26 % for 64 lanes, tools/mapping_sweep.py).
         nth = solve_threads(sp, units, sw, kCus);
         exact = sp.fk_mode == BIOIK_FK_EXACT;  // (the LDS layout of exact-FK solves is smaller, make_layout)
-        if (sw.threads <= 0 && nth == 256 && lds_bytes(p, 256, sp.lambda, 1, 2, 1, exact) > 48 * 1024) nth = 128;  // LDS-heavy problem
+        if (sw.threads <= 0 && nth == 256 && lds_need(LaneMapping{256, 1, 1, 0, 0}) > 48 * 1024) nth = 128;  // LDS-heavy problem
         quat = dp.n_quat > 0;  // winners re-derived: their momentum is taken before the quaternion genes are renormalised
         manual = sw.manual();
         // children computed where they are read (no genotype columns in LDS): the lean flavour can, whenever it is chosen below
         can_columnless = lean_capable(dp) && !sw.general_set;
         sp.columnless = 0;
+        // the problems the mapping with both species on the halves of one wavefront exists for (kHalves: the first launch of a solve in two, plan_handovers), and those
+        // among them the dense kernel is compiled for (the throughput schedule's whole solve, the latency schedule's chip-filling start: `throughput`, `dense_ok` below)
+        halves_shape = can_columnless && exact && sp.lambda >= 128 && dp.D < 32;
+        dense_shape = halves_shape && sp.lambda <= 256 && dp.n_secondary == 0;
         // k_solve_lean_cl4's mapping first -- 128 lanes, a wavefront per species, children computed where they are read and walked in pairs, the kernel compiled
         // for exactly that under the budget of four wavefronts per SIMD (no register spills since round 4): for problems without a secondary goal whose
         // lanes get at least one pair of children per generation and whose LDS footprint lets sixteen wavefronts share a CU it beats the kernel with the
         // children kept in columns on every count (C2: lone step 94 -> 91 us, fixed work at 4096 queries +30 %, three solves in flight +26 %, an isolated
         // call +16 %: profiles/r04_ab_latency_schedule_kernel.log)
-        const bool cl4_eligible = !manual && !sw.three_waves && can_columnless && exact && dp.serial_chain != 0 && !(dp.n_quat > 0) && dp.n_secondary == 0 &&
-                                  sp.lambda >= 128 && lds_bytes(p, 128, sp.lambda, 0, 2, 2, exact, exact) * 8 <= kLds;
+        const bool cl4_shape = !manual && !sw.three_waves && can_columnless && exact && dp.serial_chain != 0 && !(dp.n_quat > 0) && sp.lambda >= 128 &&
+                               lds_need(kWavePerSpecies) * 8 <= kLds;  // (what the rule above and the one below ask of a problem alike)
+        const bool cl4_eligible = cl4_shape && dp.n_secondary == 0;
         // (... also for the launches that cannot fill the chip, where solve_threads asks for a lane per child: one query 0.928 against 0.942 ms, 256 queries 5.49 against
         // 5.74 ms, profiles/r04_small_batches.log)
         if (cl4_eligible && nth == 256) nth = 128;
@@ -825,52 +843,40 @@ struct SolveLauncher {
         // ... and, for launches small enough for its helped build (k_solve_lean_cl4h), the same mapping for serial chains WITH secondary goals (a 7-joint arm with a
         // MinimalDisplacementGoal, the 31-joint chain with AvoidJointLimitsGoal: the usual MoveIt configurations of bio_ik): the kernel pre-selects, the helper takes
         // half of the survivors' walks.  Chip-filling batches of such problems keep the mappings chosen below (the joint walk, the 128-register build by residency).
-        small_sec_cl4 = !manual && !sw.three_waves && can_columnless && exact && dp.serial_chain != 0 && !(dp.n_quat > 0) && dp.n_secondary > 0 && sp.lambda >= 128 &&
-                                   sw.helped > 0 && units <= (uint64_t)sw.helped && lds_bytes(p, 128, sp.lambda, 0, 2, 2, exact, exact) * 8 <= kLds;
-        if (small_sec_cl4) nth = 128;
+        small_sec_cl4 = cl4_shape && dp.n_secondary > 0 && sw.helped > 0 && units <= (uint64_t)sw.helped;
         if (prefer_cl4 || small_sec_cl4) {
-            sp.species_parallel = 1, sp.child_cols = 1, sp.child_pairs = 1, sp.columnless = 1;
+            set_mapping(sp, nth, kWavePerSpecies);
         } else if (!manual && nth == 128) {
-            struct Cand {
-                int nth, store, pairs, columnless;
-            };
-            // richest first: children kept in LDS and scored in pairs / kept / computed where they are read / one reusable column per lane
-            const Cand cands[] = {{128, 1, 1, 0}, {128, 1, 0, 0}, {128, 0, 1, 1}, {128, 0, 0, 1}, {128, 0, 0, 0}, {64, 0, 1, 1}, {64, 0, 0, 1}, {64, 0, 0, 0}};
+            // richest first: children kept in LDS and scored in pairs / kept / computed where they are read / one reusable column per lane.  (128 lanes: a wavefront
+            // per species; 64: the species one after the other.  Either way a species has 64 lanes: `all` columns keep every child of a generation)
+            const int all = (sp.lambda + 63) / 64;
+            const LaneMapping cands[] = {{128, 1, all, 1, 0}, {128, 1, all, 0, 0}, {128, 1, 1, 1, 1}, {128, 1, 1, 0, 1}, {128, 1, 1, 0, 0}, {64, 0, 1, 1, 1}, {64, 0, 1, 0, 1}, {64, 0, 1, 0, 0}};
             const int kCuWaves = 4 * BIOIK_SOLVE_WAVES_PER_SIMD;  // wavefronts a CU holds at this kernel's register budget
             int best = -1, best_waves = -1;
             for (int i = 0; i < 8; i++) {
-                const Cand& c = cands[i];
-                if ((c.store || c.pairs) && quat) continue;
+                const LaneMapping& c = cands[i];
+                if ((c.child_cols > 1 || c.child_pairs) && quat) continue;  // (child_cols > 1: the children kept)
                 if (c.columnless && !can_columnless) continue;
-                if (c.pairs && sp.fk_mode != BIOIK_FK_EXACT) continue;
-                const int groups_c = c.nth % 128 == 0 ? 2 : 1, G_c = c.nth / groups_c;
-                const int cols = c.store ? (sp.lambda + G_c - 1) / G_c : (c.columnless ? 0 : 1);
-                if (c.pairs && !c.columnless && cols < 2) continue;
+                if (c.child_pairs && !exact) continue;
+                if (c.child_pairs && !c.columnless && c.child_cols < 2) continue;
                 // (computed children in pairs: measured +1.5 % with eight children per lane and generation (C4), -4 % with two (C3))
-                if (c.pairs && c.columnless && sp.lambda < 4 * G_c) continue;
-                const size_t bytes = lds_bytes(p, c.nth, sp.lambda, cols, groups_c, c.pairs ? 2 : 1, exact, c.columnless && exact);
+                if (c.child_pairs && c.columnless && sp.lambda < 4 * 64) continue;
+                const size_t bytes = lds_need(c);
                 if (bytes > kLds) continue;
-                int waves = (int)(kLds / bytes) * (c.nth / 64);
+                int waves = (int)(kLds / bytes) * (c.lanes / 64);
                 if (waves > kCuWaves) waves = kCuWaves;
                 // full CU: first (richest) candidate wins; LDS-limited: a later (leaner) candidate wins ties
                 if (waves > best_waves || (waves == best_waves && waves < kCuWaves)) best = i, best_waves = waves;
             }
             if (best < 0) throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs more LDS per workgroup than a CU has");
-            nth = cands[best].nth;
-            sp.species_parallel = nth % 128 == 0 ? 1 : 0;
-            const int G_b = nth / (sp.species_parallel ? 2 : 1);
-            sp.child_cols = cands[best].store ? (sp.lambda + G_b - 1) / G_b : 1;
-            sp.child_pairs = cands[best].pairs;
-            sp.columnless = cands[best].columnless;
+            set_mapping(sp, nth, cands[best]);
             // Problems with secondary goals score only a random prefix of the pre-selected children, so the phases besides the chain walk (the
             // pre-selection itself, selection, the memetic phase) weigh more; with both species of a query on the halves of ONE wavefront those
             // run once for the two.  Measured: C3 (128 children per species) +14 %, C4 (512: sixteen children per lane) -22 % (tools/c34_mapping_probe.sh).
-            if (sp.columnless && dp.n_secondary > 0 && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 &&
-                lds_bytes(p, 64, sp.lambda, 0, 2, 2, exact, exact) * kCuWaves <= kLds) {
-                nth = 64, sp.species_parallel = 1, sp.child_cols = 1, sp.child_pairs = 1;
-            }
+            if (sp.columnless && dp.n_secondary > 0 && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 && lds_need(kHalves) * kCuWaves <= kLds)
+                set_mapping(sp, nth, kHalves);
         } else {
-            while (nth > 64 && lds_bytes(p, nth, sp.lambda, 1, 2, 1, exact) > 64 * 1024) nth -= 64;  // genotype columns scale with the lane count
+            while (nth > 64 && lds_need(LaneMapping{nth, 1, 1, 0, 0}) > 64 * 1024) nth -= 64;  // genotype columns scale with the lane count
             // two lane groups, one species each: whole wavefronts (128 / 256 lanes), or the two halves of one wavefront (64 lanes)
             // (small populations, <= 32 children per species: +65..80 % measured, tools/halfwave_sweep.sh; at 64 and more children
             // per species the sequential single wavefront or the two-wavefront mapping is as good or better)
@@ -882,12 +888,12 @@ struct SolveLauncher {
                 sp.child_cols = 1;
             } else if (sw.store_children >= 0) {
                 if (sw.store_children == 0) sp.child_cols = 1;
-            } else if (lds_bytes(p, nth, sp.lambda, sp.child_cols, groups_m, 1, exact) > 48 * 1024) {
+            } else if (lds_need(LaneMapping{nth, sp.species_parallel, sp.child_cols, 0, 0}) > 48 * 1024) {
                 sp.child_cols = 1;
             }
             // children two at a time per lane (two independent dependency chains): needs both columns of the pair and, for branching
             // trees, a second set of parked frames
-            sp.child_pairs = (sp.child_cols >= 2 && sp.fk_mode == BIOIK_FK_EXACT && lds_bytes(p, nth, sp.lambda, sp.child_cols, groups_m, 2, exact) <= 64 * 1024) ? 1 : 0;
+            sp.child_pairs = (sp.child_cols >= 2 && exact && lds_need(LaneMapping{nth, sp.species_parallel, sp.child_cols, 1, 0}) <= 64 * 1024) ? 1 : 0;
             if (sw.child_pairs == 0) sp.child_pairs = 0;
         }
         // small populations, linearised phenotypes (the reference's own parameters), both species on the halves of one wavefront: children computed where
@@ -897,8 +903,7 @@ struct SolveLauncher {
         // BIOIK_SCHEDULE_THROUGHPUT: the whole solve under the mapping that retires most steps per ms on a full chip -- both species of a query on the
         // halves of one wavefront, children computed where they are read and scored in pairs (the first launch's mapping of the two-launch solve
         // below) -- for callers that keep six or more batches in flight (include/bioik_hip.h; profiles/r03_inflight_and_schedule.log)
-        throughput = sp.schedule == BIOIK_SCHEDULE_THROUGHPUT && !manual && can_columnless && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 &&
-                                dp.n_secondary == 0;
+        throughput = sp.schedule == BIOIK_SCHEDULE_THROUGHPUT && !manual && dense_shape;
         // (nth / sp keep the LATENCY mapping: a throughput solve may hand its stragglers over to it, sw.dense_handover; its own launch takes the
         // dense mapping where it is made, `halves` below)
         // k_solve_lean_cl64w4 (solve_body<.., DENSE>): the 128-register build of that mapping, four wavefronts per SIMD
@@ -906,8 +911,7 @@ struct SolveLauncher {
         // resident from the start, most steps retired per ms while the chip is full -- and, when the chip runs empty, the stragglers on to k_solve_lean_cl4 whose lone
         // step is a third shorter (SolveArgs::resident).  An isolated 4096-query call: 9.2 -> 8.5 ms (profiles/r04_drain_handover.log).  Streams of solves keep the
         // chip full, never see the hand-over and pay for its bookkeeping: the throughput schedule does without (BIOIK_SOLVE_DRAIN_THROUGHPUT=1: with).
-        dense_ok = !manual && can_columnless && exact && sp.lambda >= 128 && sp.lambda <= 256 && dp.D < 32 && dp.n_secondary == 0 && !sw.three_waves &&
-                              dp.serial_chain != 0;  // (can_columnless: a lean-capable problem)
+        dense_ok = !manual && dense_shape && !sw.three_waves && dp.serial_chain != 0;  // (can_columnless: a lean-capable problem)
         // (BIOIK_SOLVE_CAPTURE_ONE_LAUNCH=1: round 4's rule -- a call on a stream that is being captured gets a one-launch mapping.  The replay defect it worked around
         // was the runtime's memset NODE in front of the kernels, not the hand-over; the library fills its words with a kernel of its own now
         // and captured calls take the same mapping as eager ones)
@@ -920,14 +924,13 @@ struct SolveLauncher {
             sp.child_pairs = (sw.columnless == 2 && sp.fk_mode == BIOIK_FK_EXACT) ? 1 : 0;  // 2: children scored two at a time
         }
         groups = sp.species_parallel ? 2 : 1;
-        lds = lds_bytes(p, nth, sp.lambda, sp.columnless ? 0 : sp.child_cols, groups, sp.child_pairs ? 2 : 1, exact, sp.columnless && exact);
+        lds = lds_need(mapping_of(sp, nth));
         if (lds > kLds) throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs more LDS per workgroup than a CU has");
         lean = lean_capable(dp) && !(sw.general_set && sw.general);
-        halves_ok = lean && can_columnless && exact && sp.lambda >= 128 && dp.D < 32;  // the first launch's mapping exists for this problem
+        halves_ok = lean && halves_shape;  // the first launch's mapping exists for this problem
     }
     void report_mapping() const {  // diagnostics: the lane mapping and the residency it gives
-        const LdsLayout L = make_layout(dp.n_ops, dp.V, dp.P, dp.T, dp.n_slots, nth, sp.lambda, dp.n_secondary > 0 ? (exact ? 2 : 1) : 0, sp.columnless ? 0 : sp.child_cols,
-                                        groups, sp.child_pairs ? 2 : 1, (sp.columnless && exact) ? 1 : 0, 1);
+        const LdsLayout L = solve_layout(dp, sp.lambda, exact, mapping_of(sp, nth));
         int n_rev = 0, n_pos = 0, n_rot = 0;  // revolute ops and how many of them the walk takes through a sparse form
         for (int k = 0; k < dp.n_chain_ops; k++)
             if (dp.ops[k].type == BIOIK_OP_REVOLUTE) n_rev++, n_pos += dp.ops[k].pos_kind != BIOIK_POS_GENERAL, n_rot += dp.ops[k].rot_kind != BIOIK_ROT_GENERAL;
@@ -978,7 +981,7 @@ struct SolveLauncher {
         const SolveKernel kind = choose_kernel(args, lanes, lds_b);
         const bool helped = kind == SolveKernel::k_solve_lean_cl4h;
         if (helped) {
-            lanes = 256, lds_b += 64;  // (make_layout: the sixteen words of the hand-overs)
+            lds_b = lds_need(mapping_of(args.sp, lanes), true), lanes = 256;  // (the layout with the sixteen words of the hand-overs; two helper wavefronts beside the mapping's two)
             if (lds_b > 64 * 1024) be_allow_lds(lds_b);
         }
         if (sw.report)
@@ -1017,7 +1020,7 @@ struct SolveLauncher {
                 when_draining = true, handovers.push_back(sp.max_steps);
         } else if (latency_drain) {
             when_draining = true, handovers.push_back(sp.max_steps);
-        } else if (halves_ok && !manual && !prefer_cl4 && sp.lambda <= 256 && dp.n_secondary == 0 && units >= 8 * kCus && sp.max_steps >= 24 && !capturing) {
+        } else if (lean && dense_shape && !manual && !prefer_cl4 && units >= 8 * kCus && sp.max_steps >= 24 && !capturing) {
             // (not under k_solve_lean_cl4's mapping: there one launch is faster -- three in flight 9.9e5 against 9.3e5, an isolated call 8.9 against 9.3 ms,
             // profiles/r04_ab_latency_schedule_kernel.log)
             handovers.push_back(1);
@@ -1026,9 +1029,8 @@ struct SolveLauncher {
     // the mapping with both species of a query on the halves of ONE wavefront, children computed where they are read and walked in pairs: the
     // first launch of a solve in several launches, and the whole of a throughput solve
     void halves(SolveArgs& aj, int& lanes, size_t& lds_j) {
-        lanes = 64;
-        aj.sp.species_parallel = 1, aj.sp.columnless = 1, aj.sp.child_cols = 1, aj.sp.child_pairs = 1;
-        lds_j = lds_bytes(p, 64, sp.lambda, 0, 2, 2, exact, exact);
+        set_mapping(aj.sp, lanes, kHalves);
+        lds_j = lds_need(kHalves);
         if (lds_j > 64 * 1024) be_allow_lds(lds_j);
     }
     // the launch(es) of a solve whose arguments `a` are complete
@@ -1043,7 +1045,7 @@ struct SolveLauncher {
             launch(a, nth, lds);
         } else {
             const size_t nh = handovers.size();
-            const size_t carry_n = 9 * (size_t)(dp.n_ops > 0 ? dp.n_ops : 1) + 24;  // (solve_body: carry_n)
+            const size_t carry_n = (size_t)carry_doubles(dp.n_ops);
             const size_t list_bytes = (units * 4 + 63) / 64 * 64;
             const size_t list_off = (units * carry_n * 8 + 63) / 64 * 64, count_off = list_off + nh * list_bytes;
             const size_t mark_off = count_off + nh * 64, mark_bytes = migrating ? list_bytes : 0;  // (migration: one word per unit, the number of the last boundary it was live at)
@@ -1095,11 +1097,10 @@ struct SolveLauncher {
     }
 };
 
-static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, size_t n, const double* d_seeds, const double* d_params, double* d_solutions,
-                         double* d_fitness, int32_t* d_success, int32_t* d_steps, stream_t stream, const SolveSwitches& sw, unsigned int* error_word,
+static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t stream, const SolveSwitches& sw, unsigned int* error_word,
                          const RankedArgs* ranked = nullptr) {
-    if (n == 0) return;
-    SolveLauncher s(p, sp_in, n, d_seeds, d_params, d_solutions, d_fitness, d_success, d_steps, stream, sw, error_word);
+    if (arrays.n == 0) return;
+    SolveLauncher s(p, sp_in, arrays, stream, sw, error_word);
     s.ranked = ranked;
     if (s.sp.solver != 0) return s.solve_point();
     s.choose_mapping();
@@ -1108,8 +1109,8 @@ static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, size_t n
     SolveArgs a;
     a.pb = p->pb();
     a.sp = s.sp;
-    a.seeds = d_seeds;
-    a.params = d_params;
+    a.seeds = arrays.seeds;
+    a.params = arrays.goal_params;
     a.phase_cycles = nullptr;
     a.sort_key_drop = sw.sort_key_drop;
     a.preselect = sw.preselect | (sw.tie_test_bits << 8);
@@ -1164,11 +1165,10 @@ static SolveSwitches preset_switches(const SolveSwitches& base, int i) {
     if (i == 4) w.threads = 128, w.columnless = 1;
     return w;
 }
-static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, size_t n, const double* d_seeds, const double* d_params, double* d_solutions, double* d_fitness,
-                           int32_t* d_success, int32_t* d_steps, stream_t stream, bool may_wait, unsigned int* error_word) {
+static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, const SolveArrays& arrays, stream_t stream, bool may_wait, unsigned int* error_word) {
     const SolveSwitches sw = switches();  // (the diagnostic switches as last parsed: no environment access on the launch path)
-    auto run = [&](const SolveSwitches& w) { launch_solve(p, sp, n, d_seeds, d_params, d_solutions, d_fitness, d_success, d_steps, stream, w, error_word); };
-    const uint64_t units = (uint64_t)n * (uint64_t)sp.islands;
+    auto run = [&](const SolveSwitches& w) { launch_solve(p, sp, arrays, stream, w, error_word); };
+    const uint64_t units = (uint64_t)arrays.n * (uint64_t)sp.islands;
     const bool kind_ok = sw.autotune > 0 && !sw.manual() && !sw.general_set && !sw.two_phase_set && sw.drain_test == 0 && sw.dense_handover == 0 && sp.solver == 0 &&
                          sp.schedule != BIOIK_SCHEDULE_THROUGHPUT && sp.timeout_ticks == 0 && units >= 8 * (uint64_t)p->model->dev.cus && sp.max_steps >= 8;
     if (!kind_ok || be_stream_capturing(stream)) {
@@ -1212,6 +1212,22 @@ static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, size_t n,
             else std::fprintf(stderr, "[bioik]     %-90s   not eligible\n", preset_name(i));
     }
     // (the caller's arrays hold the last eligible run's results: every mapping's are the same bits, nothing to redo)
+}
+
+// what every solve entry point asks of its arrays (goal parameters only where the problem has some)
+static void check_arrays(const bioik_problem* p, const SolveArrays& a) {
+    if (a.n && (!a.seeds || !a.solutions || !a.fitness || !a.success || !a.steps || (p->host.dev.P > 0 && !a.goal_params))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+}
+// The device-pointer entries do not wait for their solves: a rendezvous time-out of an EARLIER solve through one of them is reported by the handle's next call
+static void report_stale_error(bioik_problem* p) {
+    unsigned int& err = p->h_error[bioik_problem::kIoSlots];
+    if (err == 0u) return;
+    err = 0u;
+    throw Error(BIOIK_ERR_HIP, "an earlier solve of this handle through a device-pointer entry timed out at a rendezvous between its wavefronts (k_solve_lean_cl4h): its results are not valid");
+}
+// a solve that broke off may have left the control words of the handle's scratch buffers anywhere: every buffer sets them up again (bioik_problem::Scratch)
+static void reset_control_words(bioik_problem* p) {
+    for (auto& kv : p->scratch) kv.second.ctl_base = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1344,17 +1360,13 @@ int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params,
                              double* d_solutions, double* d_fitness, int32_t* d_success, int32_t* d_steps, void* hip_stream) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    if (n && (!d_seeds || !d_solutions || !d_fitness || !d_success || !d_steps || (p->host.dev.P > 0 && !d_goal_params)))
-        throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    const SolveArrays arrays{n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, nullptr};
+    check_arrays(p, arrays);
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     DevSolveParams sp = bioik::normalize_params(*params, p->first_query, n, 8 * (size_t)p->model->dev.cus);
-    // (this entry does not wait for its solve: a rendezvous time-out of an EARLIER solve through it is reported here)
-    if (p->h_error[bioik_problem::kIoSlots] != 0u) {
-        p->h_error[bioik_problem::kIoSlots] = 0u;
-        throw Error(BIOIK_ERR_HIP, "an earlier solve of this handle through bioik_solve_batch_device timed out at a rendezvous between its wavefronts (k_solve_lean_cl4h): its results are not valid");
-    }
-    solve_dispatch(p, sp, n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, (stream_t)hip_stream, false, p->h_error + bioik_problem::kIoSlots);
+    report_stale_error(p);
+    solve_dispatch(p, sp, arrays, (stream_t)hip_stream, false, p->h_error + bioik_problem::kIoSlots);
     API_END
 }
 
@@ -1373,18 +1385,17 @@ static DevSolveParams ranked_params(bioik_problem* p, const bioik_solve_params& 
     if (k > sp.islands) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_ranked: k = " + std::to_string(k) + " is more than the call's " + std::to_string(sp.islands) + " islands");
     return sp;
 }
-static RankedArgs ranked_args(int32_t k, double min_distance, double* solutions, double* fitness, int32_t* success, int32_t* steps, int32_t* count) {
+static RankedArgs ranked_args(int32_t k, double min_distance, const SolveArrays& out) {
     RankedArgs r;
     std::memset(&r, 0, sizeof(r));
     r.k = k, r.min_distance = min_distance;
-    r.solutions = solutions, r.fitness = fitness, r.success = success, r.steps = steps, r.count = count;
+    r.solutions = out.solutions, r.fitness = out.fitness, r.success = out.success, r.steps = out.steps, r.count = out.count;
     return r;
 }
-struct RankedCall {  // a ranked solve through the host-pointer path (io_begin): its checked parameters, k, the distance, where the counts go
+struct RankedCall {  // a ranked solve through the host-pointer path (io_begin): its checked parameters, k, the distance
     DevSolveParams sp;
     int32_t k;
     double min_distance;
-    int32_t* count;
 };
 
 // host arrays in, host arrays out: staged through a slot's page-locked arena, one DMA each way, on the slot's own stream.
@@ -1399,35 +1410,35 @@ static void io_finish(bioik_problem* p, bioik_problem::IoSlot& sl) {
         // stay untouched, and the slot is free again
         sl.failed_ticket = sl.ticket, sl.failed_code = e.code, sl.failed_message = e.what();
         sl.pending = false;
-        for (auto& kv : p->scratch) kv.second.ctl_base = nullptr;  // (a solve that broke off may have left its control words anywhere: set up again)
+        reset_control_words(p);
         return;
     }
     sl.pending = false;
     unsigned int& err = p->h_error[&sl - p->io];
     if (err != 0u) {  // (SolveArgs::error: a wavefront of this solve gave up waiting for its partner and went on unsynchronised)
         err = 0u;
-        for (auto& kv : p->scratch) kv.second.ctl_base = nullptr;
+        reset_control_words(p);
         sl.failed_ticket = sl.ticket, sl.failed_code = BIOIK_ERR_HIP;
         sl.failed_message = "a rendezvous between the wavefronts of a workgroup timed out (k_solve_lean_cl4h): the results of this solve are not valid";
         return;
     }
     const size_t V = p->host.dev.V;
     const char* hd = (const char*)sl.host;
-    const size_t rows = sl.n * sl.rows;
-    std::memcpy(sl.solutions, hd + sl.o_sol, rows * V * 8);
-    std::memcpy(sl.fitness, hd + sl.o_fit, rows * 8);
-    std::memcpy(sl.success, hd + sl.o_suc, rows * 4);
-    std::memcpy(sl.steps, hd + sl.o_steps, rows * 4);
-    if (sl.count) std::memcpy(sl.count, hd + sl.o_cnt, sl.n * 4);
+    const SolveArrays& to = sl.caller;
+    const size_t rows = to.n * sl.rows;
+    std::memcpy(to.solutions, hd + sl.o_sol, rows * V * 8);
+    std::memcpy(to.fitness, hd + sl.o_fit, rows * 8);
+    std::memcpy(to.success, hd + sl.o_suc, rows * 4);
+    std::memcpy(to.steps, hd + sl.o_steps, rows * 4);
+    if (to.count) std::memcpy(to.count, hd + sl.o_cnt, to.n * 4);
 }
 // io_begin: copy in, enqueue the transfer in, the solve and the transfer out on the slot's stream; returns without waiting.
 // A solve still pending on the slot is completed first (its results reach its caller's arrays).  Called with p->mtx held.
-static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticket, const bioik_solve_params& params, uint64_t first_query, size_t n,
-                     const double* seeds, const double* goal_params, double* solutions, double* fitness, int32_t* success, int32_t* steps,
+static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticket, const bioik_solve_params& params, uint64_t first_query, const SolveArrays& caller,
                      const RankedCall* ranked = nullptr) {
     io_finish(p, sl);
     DeviceGuard on_device(p->model->device);
-    const size_t V = p->host.dev.V, P = p->host.dev.P;
+    const size_t V = p->host.dev.V, P = p->host.dev.P, n = caller.n;
     // arena layout: [seeds | goal_params] in, [solutions | fitness | success | steps] out, every block 64-byte aligned
     auto up = [](size_t b) { return (b + 63) / 64 * 64; };
     const size_t o_seeds = 0, o_par = o_seeds + up(n * V * 8), in_bytes = o_par + up(n * P * 8);
@@ -1447,8 +1458,8 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     char* dd = (char*)sl.dev;
     if (!sl.stream_made) sl.stream = be_stream_create(), sl.stream_made = true;
     const stream_t st = sl.stream;
-    std::memcpy(hd + o_seeds, seeds, n * V * 8);
-    if (P) std::memcpy(hd + o_par, goal_params, n * P * 8);
+    std::memcpy(hd + o_seeds, caller.seeds, n * V * 8);
+    if (P) std::memcpy(hd + o_par, caller.goal_params, n * P * 8);
     // (a call of a few queries -- MoveIt's one pose per call -- reads its inputs where they lie: the page-locked arena is mapped into the device's address space, and a
     // few hundred bytes per workgroup over the bus cost less than a DMA transfer in front of the launch)
     const bool direct_inputs = n <= 16;
@@ -1459,20 +1470,19 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     // written once per query).  A transfer out enqueued behind the solve would sit at the head of a DMA queue until the solve is over -- 12 ms
     // for a one-launch solve -- with the transfers in of the handle's next solves behind it: nothing would overlap
     // (profiles/r03_inflight_and_schedule.log, host pipeline).
+    const SolveArrays arena{n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
+                            (int32_t*)(hd + o_steps), ranked ? (int32_t*)(hd + o_cnt) : nullptr};
     if (ranked) {  // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
-        const RankedArgs r = ranked_args(ranked->k, ranked->min_distance, (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc), (int32_t*)(hd + o_steps), (int32_t*)(hd + o_cnt));
-        launch_solve(p, sp, n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), r.solutions, r.fitness, r.success, r.steps, st, switches(), p->h_error + (&sl - p->io), &r);
+        const RankedArgs r = ranked_args(ranked->k, ranked->min_distance, arena);
+        launch_solve(p, sp, arena, st, switches(), p->h_error + (&sl - p->io), &r);
     } else {
-        solve_dispatch(p, sp, n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
-                       (int32_t*)(hd + o_steps), st, true, p->h_error + (&sl - p->io));
+        solve_dispatch(p, sp, arena, st, true, p->h_error + (&sl - p->io));
     }
-    sl.pending = true, sl.ticket = ticket, sl.n = n, sl.rows = K;
+    sl.pending = true, sl.ticket = ticket, sl.rows = K, sl.caller = caller;
     sl.o_sol = o_sol, sl.o_fit = o_fit, sl.o_suc = o_suc, sl.o_steps = o_steps, sl.o_cnt = o_cnt;
-    sl.solutions = solutions, sl.fitness = fitness, sl.success = success, sl.steps = steps, sl.count = ranked ? ranked->count : nullptr;
 }
-static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint64_t first_query, size_t n, const double* seeds, const double* goal_params,
-                       double* solutions, double* fitness, int32_t* success, int32_t* steps, const RankedCall* ranked = nullptr) {
-    if (n == 0) return;
+static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint64_t first_query, const SolveArrays& caller, const RankedCall* ranked = nullptr) {
+    if (caller.n == 0) return;
     std::lock_guard<std::mutex> lock(p->mtx);
     const uint64_t ticket = p->next_ticket++;
     // (a synchronous call needs no slot of its own: an idle one whose stream and arenas exist already, so that a loop of searchPositionIK calls does not pay for
@@ -1484,7 +1494,7 @@ static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint6
             break;
         }
     bioik_problem::IoSlot& sl = p->io[pick];
-    io_begin(p, sl, ticket, params, first_query, n, seeds, goal_params, solutions, fitness, success, steps, ranked);
+    io_begin(p, sl, ticket, params, first_query, caller, ranked);
     io_finish(p, sl);
     if (sl.failed_ticket == ticket) throw Error(sl.failed_code, "the solve failed on the device: " + sl.failed_message);  // (the synchronous call is its own ticket's wait)
 }
@@ -1493,9 +1503,9 @@ int bioik_solve_batch(bioik_problem* p, const bioik_solve_params* params, size_t
                       double* fitness, int32_t* success, int32_t* steps) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    if (n && (!seeds || !solutions || !fitness || !success || !steps || (p->host.dev.P > 0 && !goal_params)))
-        throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
-    solve_host(p, *params, p->first_query, n, seeds, goal_params, solutions, fitness, success, steps);
+    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr};
+    check_arrays(p, arrays);
+    solve_host(p, *params, p->first_query, arrays);
     API_END
 }
 
@@ -1504,28 +1514,26 @@ int bioik_solve_batch_ranked_device(bioik_problem* p, const bioik_solve_params* 
                                     void* hip_stream) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    if (n && (!d_seeds || !d_solutions || !d_fitness || !d_success || !d_steps || (p->host.dev.P > 0 && !d_goal_params)))
-        throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    const SolveArrays arrays{n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, d_count};
+    check_arrays(p, arrays);
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     const DevSolveParams sp = ranked_params(p, *params, p->first_query, n, k, d_count);
-    if (p->h_error[bioik_problem::kIoSlots] != 0u) {
-        p->h_error[bioik_problem::kIoSlots] = 0u;
-        throw Error(BIOIK_ERR_HIP, "an earlier solve of this handle through a device-pointer entry timed out at a rendezvous between its wavefronts (k_solve_lean_cl4h): its results are not valid");
-    }
-    const RankedArgs r = ranked_args(k, min_distance, d_solutions, d_fitness, d_success, d_steps, d_count);
+    report_stale_error(p);
+    const RankedArgs r = ranked_args(k, min_distance, arrays);
     // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
-    launch_solve(p, sp, n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, (stream_t)hip_stream, switches(), p->h_error + bioik_problem::kIoSlots, &r);
+    launch_solve(p, sp, arrays, (stream_t)hip_stream, switches(), p->h_error + bioik_problem::kIoSlots, &r);
     API_END
 }
 int bioik_solve_batch_ranked(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* seeds,
                              const double* goal_params, double* solutions, double* fitness, int32_t* success, int32_t* steps, int32_t* count) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    if (n && (!seeds || !solutions || !fitness || !success || !steps || (p->host.dev.P > 0 && !goal_params))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, count};
+    check_arrays(p, arrays);
     const uint64_t first_query = p->first_query;
-    const RankedCall call{ranked_params(p, *params, first_query, n, k, count), k, min_distance, count};
-    solve_host(p, *params, first_query, n, seeds, goal_params, solutions, fitness, success, steps, &call);  // (the handle's arena, lock and slots, as bioik_solve_batch)
+    const RankedCall call{ranked_params(p, *params, first_query, n, k, count), k, min_distance};
+    solve_host(p, *params, first_query, arrays, &call);  // (the handle's arena, lock and slots, as bioik_solve_batch)
     API_END
 }
 
@@ -1534,8 +1542,8 @@ int bioik_solve_batch_submit(bioik_problem* p, const bioik_solve_params* params,
                              double* fitness, int32_t* success, int32_t* steps, uint64_t* ticket) {
     API_BEGIN
     if (!p || !params || !ticket) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    if (n && (!seeds || !solutions || !fitness || !success || !steps || (p->host.dev.P > 0 && !goal_params)))
-        throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr};
+    check_arrays(p, arrays);
     std::lock_guard<std::mutex> lock(p->mtx);
     const uint64_t t = p->next_ticket++;
     *ticket = t;
@@ -1546,7 +1554,7 @@ int bioik_solve_batch_submit(bioik_problem* p, const bioik_solve_params* params,
         for (auto& sl : p->io) in_flight += (sl.pending && &sl != &p->io[t % bioik_problem::kIoSlots]) ? 1 : 0;
         sp.schedule = in_flight >= 2 ? BIOIK_SCHEDULE_THROUGHPUT : BIOIK_SCHEDULE_LATENCY;
     }
-    io_begin(p, p->io[t % bioik_problem::kIoSlots], t, sp, p->first_query, n, seeds, goal_params, solutions, fitness, success, steps);
+    io_begin(p, p->io[t % bioik_problem::kIoSlots], t, sp, p->first_query, arrays);
     API_END
 }
 int bioik_solve_batch_wait(bioik_problem* p, uint64_t ticket) {
@@ -1590,7 +1598,7 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
             if (problems[q] == problems[r]) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_multi: the same handle twice");
     }
     const size_t V = problems[0]->host.dev.V, P = problems[0]->host.dev.P;
-    if (n && (!seeds || !solutions || !fitness || !success || !steps || (P > 0 && !goal_params))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
+    check_arrays(problems[0], SolveArrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr});
     const uint64_t first = problems[0]->first_query;
     const size_t W = (size_t)n_problems;
     // BIOIK_ISLANDS_AUTO: one island count for the whole batch, sized to the largest shard (what one device gets), so that every shard runs the same solve
@@ -1607,8 +1615,7 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
         if (a == b) continue;
         workers.emplace_back([&, r, a, b]() {
             try {
-                solve_host(problems[r], shard_params, first + a, b - a, seeds + a * V, P ? goal_params + a * P : nullptr, solutions + a * V, fitness + a,
-                           success + a, steps + a);
+                solve_host(problems[r], shard_params, first + a, SolveArrays{b - a, seeds + a * V, P ? goal_params + a * P : nullptr, solutions + a * V, fitness + a, success + a, steps + a, nullptr});
             } catch (const Error& e) {
                 status[r] = e.code, message[r] = e.what();
             } catch (const std::exception& e) {
@@ -1638,7 +1645,7 @@ int bioik_eval_fk(bioik_problem* p, size_t n, const double* seed, const double* 
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     const int nth = 64;
-    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
+    const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
     DevBuf dseed(V * 8), dgenes(n * D * 8), dout(n * T * 7 * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1662,7 +1669,7 @@ int bioik_eval_fitness(bioik_problem* p, int fk_mode, size_t n, const double* se
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     const int nth = 64;
-    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
+    const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
     DevBuf dseed(V * 8), dpar(P * 8), dbase(D * 8), dgenes(n * D * 8), d0(n * 8), d1(n * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1685,7 +1692,7 @@ int bioik_eval_approximator(bioik_problem* p, const double* seed, const double* 
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     const int nth = 64;
-    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
+    const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
     DevBuf dseed(V * 8), dbase(D * 8), d0(T * 7 * 8), d1(T * D * 7 * 8);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1732,7 +1739,7 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
     DeviceGuard on_device(p->model->device);
     DevSolveParams sp = bioik::normalize_params(*params, 0);
     const int nth = 64;
-    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
+    const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
     DevBuf dseed(V * 8), dpar(P * 8), dgenes(n * D * 8), dok(n * 4);
     be_h2d(dseed.p, seed, V * 8, 0);
@@ -1769,7 +1776,7 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
     API_END
 }
 
-int bioik_problem_carry_doubles(const bioik_problem* p) { return p ? 9 * (p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1) + 24 : BIOIK_ERR_INVALID_ARGUMENT; }
+int bioik_problem_carry_doubles(const bioik_problem* p) { return p ? carry_doubles(p->host.dev.n_ops) : BIOIK_ERR_INVALID_ARGUMENT; }
 int bioik_eval_migrate(bioik_problem* p, int32_t islands, size_t n_queries, const int32_t* live, double* rows) {
     API_BEGIN
     if (!p || islands < 1 || (n_queries && (!live || !rows))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bad argument");
@@ -1808,8 +1815,8 @@ int bioik_stream_fitness_device(bioik_problem* p, size_t n_units, int population
     int nth = population >= 256 ? 256 : (population + 63) / 64 * 64;
     // (a lane per individual: the genotype columns and parked frames grow with the lanes -- fewer lanes per workgroup where a CU would not hold them; the
     // lanes score their individuals independently, so the result does not change)
-    while (nth > 64 && lds_bytes(p, nth, 0) > p->model->dev.lds_cu) nth -= 64;
-    const size_t lds = eval_lds(p, lds_bytes(p, nth, 0));
+    while (nth > 64 && eval_lds_bytes(p, nth) > p->model->dev.lds_cu) nth -= 64;
+    const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     StreamArgs a;
     a.pb = p->pb();
     a.n_units = n_units;

@@ -95,6 +95,23 @@ BIOIK_HD LdsLayout make_layout(int n_ops, int V, int P, int T, int n_slots, int 
     L.total = o;
     return L;
 }
+// How a (query, island) lies on the lanes of its workgroup, and THE place where such a mapping becomes a solve's LDS layout: the launcher (SolveLauncher,
+// bioik_hip.hip) takes the bytes of every mapping it weighs or launches from here.  It states what solve_setup derives from its template parameters and
+// SolveArgs::sp -- kept there in its own words, because called through this function k_solve's prologue compiles to other code -- and the two must agree.
+struct LaneMapping {
+    int lanes;             // of the workgroup's species groups together (the helped kernel's two helper wavefronts do not count: `helped` below)
+    int species_parallel;  // the species on two lane groups, concurrently
+    int child_cols;        // genotype columns per lane (where children are kept at all)
+    int child_pairs;       // a lane walks its children two at a time: a second set of parked frames
+    int columnless;        // children computed where they are read: no genotype columns, and under exact FK a generation's fitness values parked in LDS
+};
+BIOIK_HD LdsLayout solve_layout(int n_ops, int V, int P, int T, int n_slots, bool has_secondary, int lambda, bool exact, const LaneMapping& m, bool helped) {
+    return make_layout(n_ops, V, P, T, n_slots, m.lanes, lambda, has_secondary ? (exact ? 2 : 1) : 0, m.columnless ? 0 : (m.child_cols > 0 ? m.child_cols : 1),
+                       m.species_parallel ? 2 : 1, m.child_pairs ? 2 : 1, (m.columnless && exact) ? 1 : 0, 1, helped ? 1 : 0);
+}
+// doubles of a unit's state between two launches of a solve (a hand-over row): per species (in ranking order) the elite buffer in use -- two individuals, genes and
+// momentum: 4 m each --, the solution, the bookkeeping block (the other elite buffer is written before it is read: it does not travel)
+BIOIK_HD int carry_doubles(int n_ops) { return 9 * (n_ops > 0 ? n_ops : 1) + 24; }
 
 struct Cand {
     double f;
@@ -882,9 +899,7 @@ struct SolveFrame {
     const int M = n_ops > 0 ? n_ops : 1;                                                                                                                              \
     const int SP = 2 * 2 * 2 * M; /* doubles per species in s_pop */                                                                                                  \
     const int BF = 4 * M;         /* doubles per buffer: [ind0 genes][ind0 momentum][ind1 genes][ind1 momentum] */                                                    \
-    /* doubles of a unit's state between two steps: per species (in ranking order) the elite buffer in use -- two individuals, genes and momentum --, the solution, */  \
-    /* the bookkeeping block (the other elite buffer is written before it is read: it does not travel) */                                                             \
-    const int carry_n = 2 * BF + M + 24;                                                                                                                              \
+    const int carry_n = carry_doubles(n_ops); /* doubles of a unit's state between two steps */                                                                       \
     const LdsLayout& L = (F).L;                                                                                                                                       \
     double* const s_seed = (F).s_seed;                                                                                                                                \
     double* const s_par = (F).s_par;                                                                                                                                  \
@@ -936,6 +951,7 @@ BIOIK_DEV bool solve_setup(Frame& F, uint64_t unit_in) {
     const int groups = FIXED ? 2 : (sp.species_parallel ? 2 : 1);
     const int G = HALVES ? 32 : (WAVE2 ? 64 : nth / groups);        // lanes per species group (a multiple of 64, or half a wavefront)
     const int g_shift = HALVES ? 5 : (WAVE2 ? 6 : ((G & (G - 1)) == 0 ? 31 - __builtin_clz((unsigned)G) : -1));  // the group sizes the launcher produces are powers of two: no integer division
+    // (solve_layout, by which the launcher sizes the LDS of every workgroup, must agree with this call)
     const LdsLayout L = make_layout(n_ops, V, P, T, pb->n_slots, nth, lambda, has_sec ? (exact ? 2 : 1) : 0, columnless ? 0 : n_cols, groups, child_pairs ? 2 : 1, (CL && exact) ? 1 : 0, 1, HELPED ? 1 : 0);
     double* s_seed = lds + L.seed;
     double* s_par = lds + L.par;
