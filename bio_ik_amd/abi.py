@@ -68,6 +68,7 @@ class SolveParams(C.Structure):
                 ("island_sync", C.c_int32), ("island_migration", C.c_int32)]
 
 
+BOUNDS_COLUMNS = ("vmin", "vmax", "span", "clip_min", "clip_max", "unbounded")  # bioik_eval_bounds: the six numbers per op
 MAX_MIGRATIONS = 8  # BIOIK_MAX_MIGRATIONS: boundaries of a solve with island_migration > 0
 ISLANDS_AUTO = 0  # bioik_solve_params::islands: as many islands as the idle part of the chip carries (include/bioik_hip.h)
 

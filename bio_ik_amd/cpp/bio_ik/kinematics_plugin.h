@@ -28,7 +28,7 @@ namespace bio_ik_kinematics_plugin {
 typedef std::function<void(const geometry_msgs::Pose&, const std::vector<double>&, moveit_msgs::MoveItErrorCodes&)> IKCallbackFn;
 
 struct BioIKParams : bio_ik::core::Settings {  // the kinematics.yaml keys of the reference (kinematics_plugin.cpp:243-328) + the additive gpu_* keys
-                                               // (gpu_island_migration among them: core::Settings)
+                                               // (gpu_island_migration and gpu_consistency_limits among them: core::Settings)
     double rotation_scale = 0.5;
     bool position_only_ik = false;
     double center_joints_weight = 0, avoid_joint_limits_weight = 0, minimal_displacement_weight = 0;
@@ -48,7 +48,9 @@ class BioIKKinematicsPlugin {
     int gpu_solutions_ = 8;
     double gpu_solution_distance_ = 0.1;
     void buildRequest(bio_ik::core::Request& rq, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states,
-                      const bio_ik::KinematicsQueryOptions& options, const std::vector<double>* context_state, double timeout) const {
+                      const bio_ik::KinematicsQueryOptions& options, const std::vector<double>* context_state, double timeout,
+                      const std::vector<std::vector<double>>* consistency_limits = nullptr) const {
+        rq.consistency_limits = consistency_limits;
         auto* bio = bio_ik::toBioIKKinematicsQueryOptions(&options);  // recognised by address, as the reference does (:75-101)
         const bool replace = bio && bio->replace;
         if (!replace)
@@ -95,6 +97,7 @@ public:
         }
         mv.var_bounded = rm.var_bounded, mv.var_min = rm.var_min, mv.var_max = rm.var_max;
         mv.var_max_velocity = rm.var_max_velocity;
+        mv.var_names = rm.variable_names;
         mv.var_prismatic.assign(mv.n_variables, 0);
         for (size_t l = 0; l < rm.joint_type.size(); l++)
             if (rm.joint_type[l] == BIOIK_JOINT_PRISMATIC) mv.var_prismatic[rm.joint_first_variable[l]] = 1;
@@ -135,11 +138,14 @@ public:
     // The batched entry point without waiting: n independent queries sharing one goal structure are marshalled and enqueued; finish
     // with searchPositionIKBatchWait.  ik_poses [n][tips] (ignored with options.replace), ik_seed_states [n][group variables]
     // (referenced until the wait, like `options`, whose solution_fitness the wait writes).  Up to six batches per device may be in flight.
+    // consistency_limits: [n][group variables] or one shared row (core::Request::consistency_limits: the windows, the seam at +-pi, what is refused -- a refused
+    // argument throws core::ConsistencyLimitsError before anything is launched); honoured whenever given, whatever the key gpu_consistency_limits says.
     Pending searchPositionIKBatchAsync(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states,
                                        const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions(),
-                                       const std::vector<double>* context_state = nullptr, double timeout = 0.0) const {
+                                       const std::vector<double>* context_state = nullptr, double timeout = 0.0,
+                                       const std::vector<std::vector<double>>* consistency_limits = nullptr) const {
         bio_ik::core::Request rq;
-        buildRequest(rq, ik_poses, ik_seed_states, options, context_state, timeout);
+        buildRequest(rq, ik_poses, ik_seed_states, options, context_state, timeout, consistency_limits);
         return Pending{engine.submit(rq)};
     }
     // Up to k distinct solutions per pose, best first (core::Engine::solveRanked): solutions [n][<= k][group variables]; rows that did not pass only with
@@ -188,19 +194,32 @@ public:
     bool searchPositionIKBatch(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states,
                                std::vector<std::vector<double>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
                                const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions(),
-                               const std::vector<double>* context_state = nullptr, double timeout = 0.0) const {
-        Pending p = searchPositionIKBatchAsync(ik_poses, ik_seed_states, options, context_state, timeout);
+                               const std::vector<double>* context_state = nullptr, double timeout = 0.0,
+                               const std::vector<std::vector<double>>* consistency_limits = nullptr) const {
+        Pending p = searchPositionIKBatchAsync(ik_poses, ik_seed_states, options, context_state, timeout, consistency_limits);
         return searchPositionIKBatchWait(p, solutions, error_codes);
     }
 
     // kinematics_plugin.cpp:437-655 (the multi-pose overload every other overload forwards to)
+    // consistency_limits: ignored unless the key gpu_consistency_limits is set (the reference ignores it: :392-440 only hand it on); with the key and a non-empty
+    // vector every group variable of the answer stays within its limit of the seed (core::Request::consistency_limits); limits that are refused -- negative, of the
+    // wrong length, an empty window -- give NO_IK_SOLUTION before anything is launched.
     bool searchPositionIK(const std::vector<geometry_msgs::Pose>& ik_poses, const std::vector<double>& ik_seed_state, double timeout,
-                          const std::vector<double>& /*consistency_limits*/, std::vector<double>& solution, const IKCallbackFn& solution_callback,
+                          const std::vector<double>& consistency_limits, std::vector<double>& solution, const IKCallbackFn& solution_callback,
                           moveit_msgs::MoveItErrorCodes& error_code, const bio_ik::KinematicsQueryOptions& options = bio_ik::KinematicsQueryOptions(),
                           const std::vector<double>* context_state = nullptr) const {
         std::vector<std::vector<double>> sols;
         std::vector<moveit_msgs::MoveItErrorCodes> codes;
-        bool ok = searchPositionIKBatch({ik_poses}, {ik_seed_state}, sols, codes, options, context_state, timeout);
+        const std::vector<std::vector<double>> limits{consistency_limits};
+        const bool limited = engine.settings().gpu_consistency_limits && !consistency_limits.empty();
+        bool ok = false;
+        try {
+            ok = searchPositionIKBatch({ik_poses}, {ik_seed_state}, sols, codes, options, context_state, timeout, limited ? &limits : nullptr);
+        } catch (const bio_ik::core::ConsistencyLimitsError&) {
+            solution = ik_seed_state;
+            error_code.val = moveit_msgs::MoveItErrorCodes::NO_IK_SOLUTION;
+            return false;
+        }
         solution = sols.empty() || sols[0].empty() ? ik_seed_state : sols[0];
         if (!ok) {
             error_code.val = moveit_msgs::MoveItErrorCodes::NO_IK_SOLUTION;

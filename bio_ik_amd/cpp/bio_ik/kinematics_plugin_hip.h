@@ -26,7 +26,10 @@ bool searchPositionIKBatch(const kinematics::KinematicsBase& solver, const std::
                            const std::vector<std::vector<double>>& ik_seed_states, double timeout, std::vector<std::vector<double>>& solutions,
                            std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
                            const kinematics::KinematicsQueryOptions& options = kinematics::KinematicsQueryOptions(),
-                           const moveit::core::RobotState* context_state = nullptr);
+                           const moveit::core::RobotState* context_state = nullptr,
+                           const std::vector<std::vector<double>>* consistency_limits = nullptr);  // [n][group variables] or one shared row: how far every group variable
+                                                                                                    // may move from its seed (plugin_core.h: Request::consistency_limits);
+                                                                                                    // honoured whenever given; a refused argument throws before any launch
 
 // The same without waiting: the batch is marshalled and enqueued (transfers and kernels on one of the solver handle's SIX streams per
 // device), and the call returns a ticket; searchPositionIKBatchWait blocks until that batch is complete and post-processed.  A caller
@@ -46,7 +49,8 @@ struct BatchTicket {
 BatchTicket searchPositionIKBatchAsync(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                                        const std::vector<std::vector<double>>& ik_seed_states, double timeout,
                                        const kinematics::KinematicsQueryOptions& options = kinematics::KinematicsQueryOptions(),
-                                       const moveit::core::RobotState* context_state = nullptr);
+                                       const moveit::core::RobotState* context_state = nullptr,
+                                       const std::vector<std::vector<double>>* consistency_limits = nullptr);  // (as searchPositionIKBatch)
 bool searchPositionIKBatchWait(const kinematics::KinematicsBase& solver, BatchTicket& ticket, std::vector<std::vector<double>>& solutions,
                                std::vector<moveit_msgs::MoveItErrorCodes>& error_codes);
 

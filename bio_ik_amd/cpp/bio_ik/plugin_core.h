@@ -49,6 +49,7 @@ struct ModelView {
     std::function<void(const std::string& link, const double* positions, double* frame7)> link_frame;  // global frame of a link at a full variable vector
     std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal on the host); may be empty
     std::function<const std::vector<double>*(const std::string& link)> link_disks;   // collision disks cx cy cz r ax ay az 0 of a link (likewise)
+    std::vector<std::string> var_names;  // optional: the variables' names, for messages (consistency limits that are refused name their variable)
 };
 
 struct Settings {  // IKParams (src/utils.h:64-85) as far as the device path reads them, + the additive gpu_* keys
@@ -71,6 +72,9 @@ struct Settings {  // IKParams (src/utils.h:64-85) as far as the device path rea
                                           // call returns the same answer; false (default): the streams advance from call to call like the
                                           // reference's generator state, and a retry of a failed query explores differently
     std::vector<int> devices = {0};  // a batch is sharded over them (contiguous shards, no exchange)
+    bool gpu_consistency_limits = false;  // true: the MoveIt-signature searchPositionIK honours a non-empty `consistency_limits` argument (Request::consistency_limits);
+                                          // false (default): it ignores the argument, as the reference does (src/kinematics_plugin.cpp:392-440 only hands it on).  Read by
+                                          // the faces: the batched entry points honour their own argument whenever it is given
     int gpu_host_goal_candidates = 4;  // solves whose goal list holds goals without a device implementation: candidates per query (independent random
                                        // streams of the device search over the device-capable goals) that the host then scores with ALL goals
 };
@@ -129,6 +133,11 @@ inline void makeDefaultGoals(const std::vector<std::string>& tip_frames, double 
     if (minimal_displacement_weight > 0) out.emplace_back(new MinimalDisplacementGoal(minimal_displacement_weight));
 }
 
+// consistency limits that are refused (Request::consistency_limits): the batched faces let it through, the MoveIt-signature searchPositionIK answers NO_IK_SOLUTION
+struct ConsistencyLimitsError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
 // One batch of queries that share a goal structure, as every face hands it over.
 struct Request {
     std::vector<const Goal*> goals;         // all goals: the plugin's defaults first (unless `replace`), then the caller's (:550-556)
@@ -141,6 +150,13 @@ struct Request {
     double timeout = 0.0;                   // the caller's timeout [s], counted from the moment submit() is entered (:504)
     bool return_approximate_solution = false;
     const BioIKKinematicsQueryOptions* bio = nullptr;  // receives solution_fitness (:632-634)
+    // CONSISTENCY LIMITS (KinematicsBase::searchPositionIK's consistency_limits): [n][group variables], or ONE row shared by every query; null or empty: none.
+    // Query k may move group variable i at most c = limits[k][i] from its seed: the solve gets the window [seed - c, seed + c] as per-query variable bounds
+    // (bioik_solve_batch_bounded_submit), each end cut to the model's var_min / var_max wherever those are finite -- continuous revolute variables included, whose
+    // model range is [-pi, pi]: A WINDOW DOES NOT CROSS THE SEAM at +-pi (a joint seeded at 3.1 with c = 0.2 stays in [2.9, pi]), so that enforcePositionBounds
+    // cannot carry an answer out of it.  Refused before any launch (std::runtime_error naming the variable): a limit that is negative or no number, a row of the
+    // wrong length, a window that comes out empty (a seed farther than c outside the model's limits).  c = 0 pins the variable to its seed.
+    const std::vector<std::vector<double>>* consistency_limits = nullptr;
 };
 
 class Engine {
@@ -214,6 +230,7 @@ public:
         std::vector<bioik_problem*> handles;
         std::vector<uint64_t> tickets;   // one per device shard (0: an empty shard)
         std::vector<double> seeds, params, sol, fit;
+        std::vector<double> lo, hi;  // the windows of a request with consistency limits, [rows][variables] (NaN: no window); empty: none.  Read by the device until the wait
         std::vector<int32_t> suc, steps, active;
         bool approximate = false, failed = false, waited = false;
         const BioIKKinematicsQueryOptions* bio = nullptr;  // receives solution_fitness in wait(): the caller's options object must outlive the wait
@@ -312,6 +329,7 @@ private:
             for (size_t i = 0; i < mv_.group_vars.size(); i++) row[mv_.group_vars[i]] = seed.at(i);
             for (size_t j = 1; j < K; j++) std::copy(row, row + V, row + j * V);
         }
+        if (rq.consistency_limits && !rq.consistency_limits->empty()) windows(rq, *tk, n, K);  // (refusals throw here: nothing has been launched)
         // per-query goal numbers: the default pose goals move into the model frame (:487-502, :540-546), then every goal writes its own
         tk->params.resize(n * K * P);
         std::vector<double> row;
@@ -354,6 +372,38 @@ private:
         return tk;
     }
 
+    std::string variableName(int v) const { return (size_t)v < mv_.var_names.size() ? "'" + mv_.var_names[v] + "'" : "#" + std::to_string(v); }
+    // Request::consistency_limits into the ticket's windows (the candidates of the hybrid path share their query's)
+    void windows(const Request& rq, Ticket& tk, size_t n, size_t K) const {
+        const std::vector<std::vector<double>>& lim = *rq.consistency_limits;
+        const size_t V = mv_.n_variables, G = mv_.group_vars.size();
+        if (lim.size() != 1 && lim.size() != n)
+            throw ConsistencyLimitsError("bio_ik (MI355X): consistency_limits holds " + std::to_string(lim.size()) + " rows: one shared row or one per query (" + std::to_string(n) + ") expected");
+        tk.lo.assign(n * K * V, std::nan("")), tk.hi.assign(n * K * V, std::nan(""));
+        for (size_t k = 0; k < n; k++) {
+            const std::vector<double>& c = lim[lim.size() == 1 ? 0 : k];
+            if (c.size() != G)
+                throw ConsistencyLimitsError("bio_ik (MI355X): consistency_limits has " + std::to_string(c.size()) + " entries, the group has " + std::to_string(G) + " variables");
+            const double* seed = &tk.seeds[k * K * V];
+            double *lo = &tk.lo[k * K * V], *hi = &tk.hi[k * K * V];
+            for (size_t i = 0; i < G; i++) {
+                const int v = mv_.group_vars[i];
+                if (!(c[i] >= 0.0 && c[i] <= DBL_MAX))
+                    throw ConsistencyLimitsError("bio_ik (MI355X): the consistency limit of variable " + variableName(v) + " is negative or not a finite number");
+                double a = seed[v] - c[i], b = seed[v] + c[i];
+                // (the ends as rounded may lie an ulp farther from the seed than c: one step in, so that |answer - seed| <= c holds as the caller computes it)
+                if (seed[v] - a > c[i]) a = std::nextafter(a, DBL_MAX);
+                if (b - seed[v] > c[i]) b = std::nextafter(b, -DBL_MAX);
+                if (std::isfinite(mv_.var_min[v])) a = std::max(a, mv_.var_min[v]);
+                if (std::isfinite(mv_.var_max[v])) b = std::min(b, mv_.var_max[v]);
+                if (!(a <= b))
+                    throw ConsistencyLimitsError("bio_ik (MI355X): the consistency window of variable " + variableName(v) + " is empty: its seed lies farther outside the model's limits than its limit");
+                lo[v] = a, hi[v] = b;
+            }
+            for (size_t j = 1; j < K; j++) std::copy(lo, lo + V, lo + j * V), std::copy(hi, hi + V, hi + j * V);
+        }
+    }
+
 public:
     std::shared_ptr<Ticket> submit(const Request& rq) {
         bioik_solve_params sp;
@@ -376,8 +426,10 @@ public:
             const size_t a = r * rows / W, b = (r + 1) * rows / W;
             if (a == b) continue;
             bioik_problem_set_first_query(tk->handles[r], first + a);
-            if (bioik_solve_batch_submit(tk->handles[r], &sp, b - a, &tk->seeds[a * V], P ? &tk->params[a * P] : nullptr, &tk->sol[a * V], &tk->fit[a], &tk->suc[a],
-                                         &tk->steps[a], &tk->tickets[r]) != BIOIK_OK)
+            // (a request with consistency limits: its windows shard with its queries; without: both arrays null, the plain call)
+            const bool limited = !tk->lo.empty();
+            if (bioik_solve_batch_bounded_submit(tk->handles[r], &sp, b - a, &tk->seeds[a * V], P ? &tk->params[a * P] : nullptr, limited ? &tk->lo[a * V] : nullptr,
+                                                 limited ? &tk->hi[a * V] : nullptr, &tk->sol[a * V], &tk->fit[a], &tk->suc[a], &tk->steps[a], &tk->tickets[r]) != BIOIK_OK)
                 tk->failed = true;  // device errors never abort the caller: every query of the batch reports NO_IK_SOLUTION
         }
         return tk;
@@ -477,7 +529,7 @@ public:
                 for (size_t j = 0; j < K; j++) {
                     const size_t r = k * K + j;
                     double* st = &tk.sol[r * V];
-                    postprocess(st, &tk.seeds[r * V], tk.active);
+                    postprocess(st, &tk.seeds[r * V], tk.active, tk.lo.empty() ? nullptr : &tk.lo[r * V], tk.lo.empty() ? nullptr : &tk.hi[r * V]);
                     positions.assign(st, st + V);
                     const std::vector<double> e = host->evaluateGoals(positions);
                     double prim = 0.0, sec = 0.0;
@@ -508,7 +560,7 @@ public:
                     if ((pass && !best_ok) || (pass == best_ok && total < best_fit)) best = r, best_fit = total, best_ok = pass;
                 }
             } else {
-                postprocess(&tk.sol[best * V], &tk.seeds[best * V], tk.active);
+                postprocess(&tk.sol[best * V], &tk.seeds[best * V], tk.active, tk.lo.empty() ? nullptr : &tk.lo[best * V], tk.lo.empty() ? nullptr : &tk.hi[best * V]);
             }
             const double* st = &tk.sol[best * V];
             for (int gv : mv_.group_vars) solutions[k].push_back(st[gv]);  // map the result to the group's variables (:619-629)
@@ -521,8 +573,12 @@ public:
 
     // What the reference does to the solver's answer before it hands it out (:580-616), on ONE full variable vector `st` solved from `seed`:
     // the angle wrap of the active revolute variables, then RobotModel::enforcePositionBounds.
-    void postprocess(double* st, const double* seed, const std::vector<int32_t>& active) const {
+    // lo / hi (a request with consistency limits: the query's windows, NaN where a variable has none): a limited variable is left inside its window -- where the angle
+    // wrap or the clamp would carry it out, the device's value, which lies inside, is kept.
+    void postprocess(double* st, const double* seed, const std::vector<int32_t>& active, const double* lo = nullptr, const double* hi = nullptr) const {
         const size_t V = mv_.n_variables;
+        std::vector<double> device;
+        if (lo && hi) device.assign(st, st + V);
         {
             {
             if (!mv_.has_mimic)
@@ -554,6 +610,9 @@ public:
             }
             }
         }
+        if (lo && hi)
+            for (int ivar : active)
+                if (lo[ivar] <= hi[ivar] && !(st[ivar] >= lo[ivar] && st[ivar] <= hi[ivar])) st[ivar] = device[ivar];
     }
     // the settings a caller may change between calls (budgets, thresholds, seed); the devices stay as initialised
     void updateSettings(const Settings& s) {

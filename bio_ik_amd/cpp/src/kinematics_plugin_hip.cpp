@@ -255,6 +255,7 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
         lookupParam("gpu_islands", p.gpu_islands, 0);  // 0: as many as the idle part of the chip carries (BIOIK_ISLANDS_AUTO)
         lookupParam("gpu_island_sync", p.gpu_island_sync, true);  // islands stop once one of them has a solution, as the reference's solver threads do
         lookupParam("gpu_island_migration", p.gpu_island_migration, 0);  // E > 0: the islands of a pose share their best solution every E steps (0: independent islands)
+        lookupParam("gpu_consistency_limits", p.gpu_consistency_limits, false);  // true: searchPositionIK honours its consistency_limits argument (false: ignored, as the reference does)
         lookupParam("gpu_host_goal_candidates", p.gpu_host_goal_candidates, 4);  // candidates per query that the host scores when the goal list holds callback goals
         lookupParam("gpu_max_steps", p.gpu_max_steps, 4096);    // safety cap; the caller's timeout is what normally ends a query
         lookupParam("gpu_fk", p.gpu_fk, std::string("exact"));  // "exact" | "linear" (the reference's linearised phenotypes)
@@ -290,6 +291,7 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
             mv.var_max_velocity.push_back(b.max_velocity_);
             mv.var_prismatic.push_back(jm->getType() == moveit::core::JointModel::PRISMATIC ? 1 : 0);
         }
+        mv.var_names = rm->getVariableNames();
         // goals that are evaluated on the host (JointFunctionGoal, LinkFunctionGoal, user subclasses: bio_ik/plugin_core.h, the hybrid path) read link
         // frames through MoveIt's own forward kinematics
         host_state.reset(new moveit::core::RobotState(robot_model));
@@ -390,10 +392,12 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
     double gpu_solution_distance = 0.1;
     std::shared_ptr<bio_ik::core::Engine::Ticket> submitBatch(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                                                               const std::vector<std::vector<double>>& ik_seed_states, double timeout,
-                                                              const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state) const {
+                                                              const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state,
+                                                              const std::vector<std::vector<double>>* consistency_limits = nullptr) const {
         std::lock_guard<std::mutex> lock(mutex);
         bio_ik::core::Request rq;
         buildRequest(rq, ik_poses, ik_seed_states, timeout, options, context_state);
+        rq.consistency_limits = consistency_limits;  // (core::Request::consistency_limits: [n][group variables] or one shared row; a refused argument throws before any launch)
         return engine.submit(rq);
     }
     // Up to k distinct solutions per pose, best first (core::Engine::solveRanked): solutions [n][<= k][group variables]; a query without a row: NO_IK_SOLUTION
@@ -484,19 +488,30 @@ struct BioIKKinematicsPlugin : kinematics::KinematicsBase {
     }
     bool solveBatch(const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses, const std::vector<std::vector<double>>& ik_seed_states, double timeout,
                     std::vector<std::vector<double>>& solutions, std::vector<moveit_msgs::MoveItErrorCodes>& error_codes,
-                    const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state) const {
-        auto ticket = submitBatch(ik_poses, ik_seed_states, timeout, options, context_state);
+                    const kinematics::KinematicsQueryOptions& options, const moveit::core::RobotState* context_state,
+                    const std::vector<std::vector<double>>* consistency_limits = nullptr) const {
+        auto ticket = submitBatch(ik_poses, ik_seed_states, timeout, options, context_state, consistency_limits);
         return finishBatch(*ticket, solutions, error_codes);
     }
 
     // :437-655, the overload every other one forwards to
+    // consistency_limits: honoured only with the key gpu_consistency_limits (default off: ignored, as the reference does); then every group variable of the answer
+    // stays within its limit of the seed (core::Request::consistency_limits: the windows, the seam at +-pi); limits that are refused give NO_IK_SOLUTION
     bool searchPositionIK(const std::vector<geometry_msgs::Pose>& ik_poses, const std::vector<double>& ik_seed_state, double timeout,
-                          const std::vector<double>& /*consistency_limits*/, std::vector<double>& solution, const IKCallbackFn& solution_callback,
+                          const std::vector<double>& consistency_limits, std::vector<double>& solution, const IKCallbackFn& solution_callback,
                           moveit_msgs::MoveItErrorCodes& error_code, const kinematics::KinematicsQueryOptions& options = kinematics::KinematicsQueryOptions(),
                           const moveit::core::RobotState* context_state = nullptr) const override {
         std::vector<std::vector<double>> sols;
         std::vector<moveit_msgs::MoveItErrorCodes> codes;
-        const bool ok = solveBatch({ik_poses}, {ik_seed_state}, timeout, sols, codes, options, context_state);
+        const std::vector<std::vector<double>> limits{consistency_limits};
+        const bool limited = settings.gpu_consistency_limits && !consistency_limits.empty();
+        bool ok = false;
+        try {
+            ok = solveBatch({ik_poses}, {ik_seed_state}, timeout, sols, codes, options, context_state, limited ? &limits : nullptr);
+        } catch (const bio_ik::core::ConsistencyLimitsError&) {
+            error_code.val = error_code.NO_IK_SOLUTION;
+            return false;
+        }
         if (!sols.empty() && !sols[0].empty()) solution = sols[0];
         if (!ok) {  // no accurate solution and no approximate one requested (:638-641)
             error_code.val = error_code.NO_IK_SOLUTION;
@@ -522,8 +537,8 @@ static const BioIKKinematicsPlugin& pluginOf(const kinematics::KinematicsBase& s
 bool searchPositionIKBatch(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                            const std::vector<std::vector<double>>& ik_seed_states, double timeout, std::vector<std::vector<double>>& solutions,
                            std::vector<moveit_msgs::MoveItErrorCodes>& error_codes, const kinematics::KinematicsQueryOptions& options,
-                           const moveit::core::RobotState* context_state) {
-    return pluginOf(solver, "searchPositionIKBatch").solveBatch(ik_poses, ik_seed_states, timeout, solutions, error_codes, options, context_state);
+                           const moveit::core::RobotState* context_state, const std::vector<std::vector<double>>* consistency_limits) {
+    return pluginOf(solver, "searchPositionIKBatch").solveBatch(ik_poses, ik_seed_states, timeout, solutions, error_codes, options, context_state, consistency_limits);
 }
 
 
@@ -545,9 +560,9 @@ BatchTicket::BatchTicket(BatchTicket&&) = default;
 BatchTicket& BatchTicket::operator=(BatchTicket&&) = default;
 BatchTicket searchPositionIKBatchAsync(const kinematics::KinematicsBase& solver, const std::vector<std::vector<geometry_msgs::Pose>>& ik_poses,
                                        const std::vector<std::vector<double>>& ik_seed_states, double timeout, const kinematics::KinematicsQueryOptions& options,
-                                       const moveit::core::RobotState* context_state) {
+                                       const moveit::core::RobotState* context_state, const std::vector<std::vector<double>>* consistency_limits) {
     BatchTicket t;
-    t.impl.reset(new BatchTicket::Impl{pluginOf(solver, "searchPositionIKBatchAsync").submitBatch(ik_poses, ik_seed_states, timeout, options, context_state)});
+    t.impl.reset(new BatchTicket::Impl{pluginOf(solver, "searchPositionIKBatchAsync").submitBatch(ik_poses, ik_seed_states, timeout, options, context_state, consistency_limits)});
     return t;
 }
 bool searchPositionIKBatchWait(const kinematics::KinematicsBase& solver, BatchTicket& ticket, std::vector<std::vector<double>>& solutions,

@@ -30,6 +30,7 @@ struct InFlight {
     std::shared_ptr<bio_ik::core::Engine::Ticket> ticket;
     std::vector<std::vector<double>> seed_states;
     std::vector<std::unique_ptr<bio_ik::Goal>> caller_goals;
+    std::vector<std::vector<double>> limits;  // consistency limits (bioik_plugin_submit_limited)
 };
 
 thread_local std::string g_error;
@@ -61,6 +62,7 @@ typedef struct bioik_plugin_settings {  // kinematics.yaml keys (kinematics_plug
     double rotation_scale, center_joints_weight, avoid_joint_limits_weight, minimal_displacement_weight;
     int32_t gpu_island_sync, gpu_island_migration;  // gpu_island_sync: "any island succeeds => all stop"; gpu_island_migration: the islands share their best every E steps,
                                                     // in the slot that was `reserved` (0 = off) (core::Settings)
+    int32_t gpu_consistency_limits, reserved1;      // gpu_consistency_limits: the MoveIt-signature searchPositionIK honours its consistency_limits argument (core::Settings)
 } bioik_plugin_settings;
 
 typedef struct bioik_plugin_goal {
@@ -91,6 +93,7 @@ static bio_ik::core::Settings coreSettings(const bioik_plugin_settings& s) {
     c.gpu_reproducible_calls = s.gpu_reproducible_calls != 0;
     c.gpu_island_sync = s.gpu_island_sync != 0;
     c.gpu_island_migration = s.gpu_island_migration;
+    c.gpu_consistency_limits = s.gpu_consistency_limits != 0;
     c.devices.assign(s.devices, s.devices + s.n_devices);
     return c;
 }
@@ -121,6 +124,7 @@ int bioik_plugin_create(const bioik_model_desc* md, const char* const* link_name
         }
         mv.var_bounded.assign(md->var_bounded, md->var_bounded + md->n_variables);
         mv.var_min.assign(md->var_min, md->var_min + md->n_variables), mv.var_max.assign(md->var_max, md->var_max + md->n_variables);
+        mv.var_names = p->variable_names;
         for (uint32_t i = 0; i < n_group_joints; i++) {
             const int j = group_joints[i], t = md->joint_type[j];
             const int nv = t == BIOIK_JOINT_FLOATING ? 7 : (t == BIOIK_JOINT_PLANAR ? 3 : 1);
@@ -173,6 +177,26 @@ int bioik_plugin_submit(bioik_plugin* p, uint64_t n, const double* seeds, const 
         InFlight f;
         bio_ik::core::Request rq;
         buildRequest(p, f, rq, n, seeds, tip_poses, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints, timeout, return_approximate_solution);
+        f.ticket = p->engine.submit(rq);
+        *ticket = p->next_ticket++;
+        p->in_flight.emplace(*ticket, std::move(f));
+    });
+}
+
+// bioik_plugin_submit with CONSISTENCY LIMITS (core::Request::consistency_limits): limits [n_limit_rows][group variables], n_limit_rows = n, or 1 (one row shared by
+// every query), or 0 (none: bioik_plugin_submit).  Limits that are refused -- negative or no number, another number of rows, an empty window -- fail the call before
+// anything is launched (bioik_plugin_last_error names the variable).  limit_row_length: the entries per row the caller holds (must be the group's variable count).
+int bioik_plugin_submit_limited(bioik_plugin* p, uint64_t n, const double* seeds, const double* tip_poses, const double* base_frame, const double* context,
+                                uint32_t n_goals, const bioik_plugin_goal* goals, int32_t replace, uint32_t n_fixed, const char* const* fixed_joints, double timeout,
+                                int32_t return_approximate_solution, uint64_t n_limit_rows, uint32_t limit_row_length, const double* limits, uint64_t* ticket) {
+    return guarded([&] {
+        if (n_limit_rows && !limits) throw std::runtime_error("bio_ik (MI355X): bioik_plugin_submit_limited: limits is null");
+        std::lock_guard<std::mutex> lock(p->mutex);
+        InFlight f;
+        bio_ik::core::Request rq;
+        buildRequest(p, f, rq, n, seeds, tip_poses, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints, timeout, return_approximate_solution);
+        for (uint64_t r = 0; r < n_limit_rows; r++) f.limits.emplace_back(limits + r * limit_row_length, limits + (r + 1) * limit_row_length);
+        if (n_limit_rows) rq.consistency_limits = &f.limits;
         f.ticket = p->engine.submit(rq);
         *ticket = p->next_ticket++;
         p->in_flight.emplace(*ticket, std::move(f));
@@ -276,6 +300,30 @@ int bioik_plugin_search_each(bioik_plugin* p, uint64_t n, const double* seeds, c
         uint64_t ticket = 0;
         int rc = bioik_plugin_submit(p, 1, seeds + k * G, T ? tip_poses + k * T * 7 : nullptr, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints, timeout,
                                      return_approximate_solution, &ticket);
+        if (rc == 0) rc = bioik_plugin_wait(p, ticket, solutions + k * G, ok + k, fitness + k);
+        if (rc != 0) return rc;
+        seconds[k] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return 0;
+}
+
+// bioik_plugin_search_each with consistency limits: limits [n_limit_rows][group variables], n_limit_rows = n or 1 (shared) or 0 (none); call k gets its own row
+int bioik_plugin_search_each_limited(bioik_plugin* p, uint64_t n, const double* seeds, const double* tip_poses, const double* base_frame, const double* context,
+                                     uint32_t n_goals, const bioik_plugin_goal* goals, int32_t replace, uint32_t n_fixed, const char* const* fixed_joints, double timeout,
+                                     int32_t return_approximate_solution, uint64_t n_limit_rows, uint32_t limit_row_length, const double* limits, double* solutions,
+                                     uint8_t* ok, double* fitness, double* seconds) {
+    if (n_limit_rows != 0 && n_limit_rows != 1 && n_limit_rows != n) {
+        g_error = "bio_ik (MI355X): consistency_limits holds " + std::to_string(n_limit_rows) + " rows: one shared row or one per query expected";
+        return 1;
+    }
+    const size_t G = p->engine.modelView().group_vars.size();
+    const size_t T = replace ? 0 : p->tip_frames.size();
+    for (uint64_t k = 0; k < n; k++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t ticket = 0;
+        int rc = bioik_plugin_submit_limited(p, 1, seeds + k * G, T ? tip_poses + k * T * 7 : nullptr, base_frame, context, n_goals, goals, replace, n_fixed, fixed_joints,
+                                             timeout, return_approximate_solution, n_limit_rows ? 1 : 0, limit_row_length,
+                                             n_limit_rows ? limits + (n_limit_rows == 1 ? 0 : k) * limit_row_length : nullptr, &ticket);
         if (rc == 0) rc = bioik_plugin_wait(p, ticket, solutions + k * G, ok + k, fitness + k);
         if (rc != 0) return rc;
         seconds[k] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

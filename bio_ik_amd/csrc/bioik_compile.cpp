@@ -506,6 +506,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         const HostModel::Var& vi = m->vars[op.var];
         op.clip_min = vi.clip_min, op.clip_max = vi.clip_max, op.span = vi.span, op.vmin = vi.vmin, op.vmax = vi.vmax;
         op.unbounded = vi.clip_max == DBL_MAX;
+        op.var_revolute = (vi.joint >= 0 && m->links[vi.joint].type == BIOIK_JOINT_REVOLUTE) ? 1 : 0;
         op.vw = op.gene >= 0 ? vw[op.gene] : 0.0;
         if (op.gene >= 0) dev.op_of_gene[op.gene] = (int)k;
     }

@@ -356,11 +356,46 @@ BIOIK_CALL double goal_eval_link_rare(int type, const lds_f64* P, F7 fb) {
     }
     return 0.0;
 }
+// Per-query variable bounds (bioik_solve_batch_bounded): THE rule, in one place.  For op k of a query whose rows of bounds are lo_row / hi_row ([V], indexed by
+// robot variable): if the op's variable is an ACTIVE variable of the problem and lo, hi are both finite with lo <= hi, the six numbers the host-side problem
+// compiler would have put into the op had the model been created with var_min = lo, var_max = hi, var_bounded = 1 (bioik_compile.cpp, HostModel: RobotInfo,
+// robot_info.h:70-106) -- a revolute variable whose range reaches 2 pi 0.9999 loses its clip, span = hi - lo with the "not in [0, FLT_MAX) -> 1" rule,
+// unbounded = clip_max == DBL_MAX.  Otherwise (a NaN, an infinity, lo > hi, a variable that is no gene, null rows) the op's own numbers from the problem block.
+struct OpBounds {
+    double clip_min, clip_max, span, vmin, vmax;
+    int unbounded;
+};
+BIOIK_DEV OpBounds stage_op_bounds(ProbPtr pb, int k, const double* lo_row, const double* hi_row) {
+    BIOIK_FP_STRICT
+    OpBounds b{pb->ops[k].clip_min, pb->ops[k].clip_max, pb->ops[k].span, pb->ops[k].vmin, pb->ops[k].vmax, pb->ops[k].unbounded};
+    if (pb->ops[k].gene < 0 || !lo_row || !hi_row) return b;
+    const double lo = lo_row[pb->ops[k].var], hi = hi_row[pb->ops[k].var];
+    if (!(__builtin_fabs(lo) <= BIOIK_DBL_MAX && __builtin_fabs(hi) <= BIOIK_DBL_MAX && lo <= hi)) return b;
+    bool bounded = true;
+    if (pb->ops[k].var_revolute && hi - lo >= 2 * BIOIK_PI * 0.9999) bounded = false;
+    b.vmin = lo, b.vmax = hi;
+    b.clip_min = bounded ? lo : -BIOIK_DBL_MAX;
+    b.clip_max = bounded ? hi : BIOIK_DBL_MAX;
+    b.span = hi - lo;
+    if (!(b.span >= 0 && b.span < 3.4028234663852886e38)) b.span = 1;  // (FLT_MAX)
+    b.unbounded = b.clip_max == BIOIK_DBL_MAX ? 1 : 0;
+    return b;
+}
+// the ops of a query into its table of bounds ([LIM_N][m], LDS): lanes stride over the ops
+BIOIK_DEV void stage_bounds(ProbPtr pb, const double* lo_row, const double* hi_row, double* lim, int m, int tid, int nth) {
+    const int n_ops = pb->n_ops;
+    for (int k = tid; k < n_ops; k += nth) {
+        const OpBounds b = stage_op_bounds(pb, k, lo_row, hi_row);
+        lim[LIM_CLIP_MIN * m + k] = b.clip_min, lim[LIM_CLIP_MAX * m + k] = b.clip_max, lim[LIM_SPAN * m + k] = b.span;
+        lim[LIM_VMIN * m + k] = b.vmin, lim[LIM_VMAX * m + k] = b.vmax, lim[LIM_UNBOUNDED * m + k] = b.unbounded ? 1.0 : 0.0;
+    }
+}
+
 // The goals over the joint values (goal_types.h:387-498): one out-of-line copy; x and the seed are LDS pointers that cross the
 // call with their address space spelled out.
 // x: any "one value per op" accessor (an LDS vector / column, or a child computed where it is read)
-template <class XA>
-BIOIK_DEV double goal_eval_joint_set_x(ProbPtr pb, int type, int var_op, int var_seed, double p0, const XA& x, const lds_f64* seed) {
+template <class XA, class PB>
+BIOIK_DEV double goal_eval_joint_set_x(PB pb, int type, int var_op, int var_seed, double p0, const XA& x, const lds_f64* seed) {
     // The reference's sums run over the ACTIVE VARIABLES -- the genes in their order.  That is the order of the ops wherever the ops meet the genes in it
     // (DevProblem::genes_follow_ops: every problem whose goals name no variable of their own); a JointVariableGoal puts its variable in front of the
     // chains' (problem.cpp:139-162), and the terms are then added in that order: the same terms, another rounding.
@@ -371,9 +406,9 @@ BIOIK_DEV double goal_eval_joint_set_x(ProbPtr pb, int type, int var_op, int var
             double sum = 0.0;
             for (int i = 0; i < cnt; i++) {
                 const int k = by_op ? i : pb->op_of_gene[i];
-                if (pb->ops[k].gene >= 0 && !pb->ops[k].unbounded) {
-                    double d = x(k) - (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5;
-                    d = fmax(0.0, fabs(d) * 2.0 - pb->ops[k].span * 0.5);
+                if (pb->ops[k].gene >= 0 && !op_unbounded(pb, k)) {
+                    double d = x(k) - (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5;
+                    d = fmax(0.0, fabs(d) * 2.0 - op_limit<LIM_SPAN>(pb, k) * 0.5);
                     d *= pb->ops[k].vw;
                     sum += d * d;
                 }
@@ -384,8 +419,8 @@ BIOIK_DEV double goal_eval_joint_set_x(ProbPtr pb, int type, int var_op, int var
             double sum = 0.0;
             for (int i = 0; i < cnt; i++) {
                 const int k = by_op ? i : pb->op_of_gene[i];
-                if (pb->ops[k].gene >= 0 && !pb->ops[k].unbounded) {
-                    double d = x(k) - (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5;
+                if (pb->ops[k].gene >= 0 && !op_unbounded(pb, k)) {
+                    double d = x(k) - (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5;
                     d *= pb->ops[k].vw;
                     sum += d * d;
                 }
@@ -433,15 +468,15 @@ BIOIK_DEV double joint_set_term(PB pb, int type, int k, double xv, const double*
     if (pb->ops[k].gene < 0) return 0.0;
     switch (type) {
         case G_AVOID_JOINT_LIMITS: {
-            if (pb->ops[k].unbounded) return 0.0;
-            double d = xv - (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5;
-            d = fmax(0.0, fabs(d) * 2.0 - pb->ops[k].span * 0.5);
+            if (op_unbounded(pb, k)) return 0.0;
+            double d = xv - (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5;
+            d = fmax(0.0, fabs(d) * 2.0 - op_limit<LIM_SPAN>(pb, k) * 0.5);
             d *= pb->ops[k].vw;
             return d * d;
         }
         case G_CENTER_JOINTS: {
-            if (pb->ops[k].unbounded) return 0.0;
-            double d = xv - (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5;
+            if (op_unbounded(pb, k)) return 0.0;
+            double d = xv - (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5;
             d *= pb->ops[k].vw;
             return d * d;
         }
@@ -464,8 +499,8 @@ BIOIK_DEV double joint_set_term(PB pb, int type, int k, double xv, const double*
 // inside_mask (wavefront-uniform; AvoidJointLimitsGoal only): bit k = op k of EVERY individual in x lies strictly inside the half of its range that
 // costs nothing (avoid_limits_surely_free) -- its term is `sum += 0`, which leaves a non-negative sum as it is, so the op is passed over without its
 // value being computed at all
-template <int N, class XA>
-BIOIK_DEV void goal_eval_joint_set_xn(ProbPtr pb, int type, int var_op, int var_seed, double p0, const XA (&x)[N], const lds_f64* seed, double (&out)[N],
+template <int N, class XA, class PB>
+BIOIK_DEV void goal_eval_joint_set_xn(PB pb, int type, int var_op, int var_seed, double p0, const XA (&x)[N], const lds_f64* seed, double (&out)[N],
                                       uint64_t inside_mask = 0ull) {
     const int n_ops = pb->n_ops;
     double sum[N];
@@ -474,8 +509,8 @@ BIOIK_DEV void goal_eval_joint_set_xn(ProbPtr pb, int type, int var_op, int var_
     switch (type) {
         case G_AVOID_JOINT_LIMITS:
             for (int k = 0; k < n_ops; k++)
-                if (pb->ops[k].gene >= 0 && !pb->ops[k].unbounded && !((inside_mask >> k) & 1ull)) {
-                    const double mid = (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5, half_span = pb->ops[k].span * 0.5, vw = pb->ops[k].vw;
+                if (pb->ops[k].gene >= 0 && !op_unbounded(pb, k) && !((inside_mask >> k) & 1ull)) {
+                    const double mid = (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5, half_span = op_limit<LIM_SPAN>(pb, k) * 0.5, vw = pb->ops[k].vw;
 #pragma unroll
                     for (int j = 0; j < N; j++) {
                         double d = x[j](k) - mid;
@@ -487,8 +522,8 @@ BIOIK_DEV void goal_eval_joint_set_xn(ProbPtr pb, int type, int var_op, int var_
             break;
         case G_CENTER_JOINTS:
             for (int k = 0; k < n_ops; k++)
-                if (pb->ops[k].gene >= 0 && !pb->ops[k].unbounded) {
-                    const double mid = (pb->ops[k].vmin + pb->ops[k].vmax) * 0.5, vw = pb->ops[k].vw;
+                if (pb->ops[k].gene >= 0 && !op_unbounded(pb, k)) {
+                    const double mid = (op_limit<LIM_VMIN>(pb, k) + op_limit<LIM_VMAX>(pb, k)) * 0.5, vw = pb->ops[k].vw;
 #pragma unroll
                     for (int j = 0; j < N; j++) {
                         double d = x[j](k) - mid;
@@ -538,7 +573,8 @@ struct LdsX {  // an op-indexed vector in LDS with its address space spelled out
     int s;
     BIOIK_DEV double operator()(int k) const { return p[(size_t)k * s]; }
 };
-BIOIK_DEV double goal_eval_joint_set_inl(ProbPtr pb, int type, int var_op, int var_seed, double p0, const lds_f64* xp, int xs, const lds_f64* seed) {
+template <class PB>
+BIOIK_DEV double goal_eval_joint_set_inl(PB pb, int type, int var_op, int var_seed, double p0, const lds_f64* xp, int xs, const lds_f64* seed) {
     return goal_eval_joint_set_x(pb, type, var_op, var_seed, p0, LdsX{xp, xs}, seed);
 }
 BIOIK_CALL double goal_eval_joint_set(ProbPtr pb, int type, int var_op, int var_seed, double p0, const lds_f64* xp, int xs, const lds_f64* seed) {
@@ -575,7 +611,7 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
             if constexpr (!std::is_same<XA, XV>::value) {  // a computed accessor cannot cross a call: inline
                 return goal_eval_joint_set_x(pb, type, var_op, var_seed, type == G_JOINT_VARIABLE ? P[0] : 0.0, x, (const lds_f64*)qc.seed);
             } else {
-                if (JS_INLINE)
+                if (JS_INLINE || pb_bounded<PB>::value)  // (the bounded flavour's pointer carries an LDS pointer: it crosses no call)
                     return goal_eval_joint_set_inl(pb, type, var_op, var_seed, type == G_JOINT_VARIABLE ? P[0] : 0.0, (const lds_f64*)x.p, x.s, (const lds_f64*)qc.seed);
                 return goal_eval_joint_set(pb, type, var_op, var_seed, type == G_JOINT_VARIABLE ? P[0] : 0.0, (const lds_f64*)x.p, x.s, (const lds_f64*)qc.seed);
             }
@@ -917,7 +953,7 @@ BIOIK_DEV void serial_joint_n(PB pb, int k, const XA (&x)[N], const F7 (&a)[N], 
     if constexpr (accessor_takes_op_numbers<XA>::value) {
         // (children computed where they are read: what their accessor reads of the op comes with the burst above)
         const int gene = pb->ops[k].gene;
-        const double span = pb->ops[k].span, cmin = pb->ops[k].clip_min, cmax = pb->ops[k].clip_max;
+        const double span = op_limit<LIM_SPAN>(pb, k), cmin = op_limit<LIM_CLIP_MIN>(pb, k), cmax = op_limit<LIM_CLIP_MAX>(pb, k);
 #pragma unroll
         for (int j = 0; j < N; j++) xv[j] = x[j].at(k, gene, span, cmin, cmax);
     } else {
@@ -1425,7 +1461,7 @@ BIOIK_DEV void reproduce_children(PB pb, uint32_t key, uint32_t ctr1, const uint
                 const int g = w0 + w - 1 < 0 ? 0 : (w0 + w - 1 < D ? w0 + w - 1 : D - 1);
                 const int k = pb->op_of_gene[g];
                 kk[j] = k;
-                const double span = pb->ops[k].span, cmin = pb->ops[k].clip_min, cmax = pb->ops[k].clip_max;
+                const double span = op_limit<LIM_SPAN>(pb, k), cmin = op_limit<LIM_CLIP_MIN>(pb, k), cmax = op_limit<LIM_CLIP_MAX>(pb, k);
                 const double parent_gene = p0g[k], d0 = p0d[k], d1 = p1d[k];
 #pragma unroll
                 for (int i = 0; i < N; i++) {
@@ -1479,7 +1515,7 @@ struct ChildX {
     // (p_clamp_uniform); false where lane k asks for op k (the winners' re-derivation): the same two instructions on vector operands
     template <bool UNIFORM = true>
     BIOIK_DEV double value(int k) const {
-        return at<UNIFORM>(k, pb->ops[k].gene, pb->ops[k].span, pb->ops[k].clip_min, pb->ops[k].clip_max);
+        return at<UNIFORM>(k, pb->ops[k].gene, op_limit<LIM_SPAN>(pb, k), op_limit<LIM_CLIP_MIN>(pb, k), op_limit<LIM_CLIP_MAX>(pb, k));
     }
     // the same with the op's numbers handed in: the chain walk asks for them in ONE burst of scalar loads with the joint's constants (fk_walk_n), and the
     // parents' entries are read from LDS before anything waits -- a lone wavefront (one pose per call, the stragglers of a batch) otherwise waits four times per joint
@@ -1533,7 +1569,7 @@ struct ChildT {
     const double *p0g, *pgrow;  // LDS, op-indexed: genes of parent 0; the row of the table for this child's parity
     uint32_t base;
     double mutation_rate, gradient_factor;
-    BIOIK_DEV double operator()(int k) const { return at(k, pb->ops[k].gene, pb->ops[k].span, pb->ops[k].clip_min, pb->ops[k].clip_max); }
+    BIOIK_DEV double operator()(int k) const { return at(k, pb->ops[k].gene, op_limit<LIM_SPAN>(pb, k), op_limit<LIM_CLIP_MIN>(pb, k), op_limit<LIM_CLIP_MAX>(pb, k)); }
     static constexpr bool takes_op_numbers = true;  // (ChildX::at)
     BIOIK_DEV double at(int k, int g, double span, double cmin, double cmax) const {
         BIOIK_FP_STRICT

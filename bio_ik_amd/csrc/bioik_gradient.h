@@ -12,9 +12,9 @@
 #include "bioik_kernels.h"
 
 struct PointLayout {  // offsets in doubles
-    int seed, par, prefix, sol, best, grad, gg, ex, xcol, slots, frames, tips, jac, A, Vm, sig, b, x, total;
+    int seed, par, prefix, sol, best, grad, gg, ex, xcol, slots, frames, tips, jac, A, Vm, sig, b, x, lim, total;
 };
-BIOIK_HD PointLayout make_point_layout(int n_ops, int V, int P, int T, int n_slots, int D, int nthreads) {
+BIOIK_HD PointLayout make_point_layout(int n_ops, int V, int P, int T, int n_slots, int D, int nthreads, int bounded = 0) {
     PointLayout L;
     const int m = n_ops > 0 ? n_ops : 1, d = D > 0 ? D : 1, t6 = 6 * (T > 0 ? T : 1);
     const int q = d < t6 ? d : t6;
@@ -37,6 +37,7 @@ BIOIK_HD PointLayout make_point_layout(int n_ops, int V, int P, int T, int n_slo
     L.sig = o, o += q;
     L.b = o, o += t6;
     L.x = o, o += d;
+    L.lim = o, o += bounded ? LIM_N * m : 0;  // the bounded flavour's table of the query's variable bounds (k_solve_point_bounded)
     L.total = o;
     return L;
 }
@@ -106,13 +107,16 @@ BIOIK_DEV void pinv_solve_lds(const double* J, int rows, int cols, const double*
 // one (query, island) per workgroup of ONE wavefront; the island loop in budget / wall-clock form as in solve_body.  Island 0 is solver
 // thread 0 of the reference (started at the seed), the islands i > 0 its threads started at random configurations (the _2 / _4 / _8
 // factory names, ik_gradient.cpp:157-159, :283-285); solver 4 (gd_r) draws a new configuration after a step that did not improve.
+// BOUNDED: per-query variable bounds (k_solve_point_bounded): the random configurations and the clip read the query's table (BoundedProbPtr)
+template <bool BOUNDED = false>
 BIOIK_DEV void point_body(const SolveArgs& a, uint64_t unit, double* lds) {
-    const ProbPtr pb = a.pb;
+    typedef typename std::conditional<BOUNDED, BoundedProbPtr, ProbPtr>::type PB;
     const DevSolveParams& sp = a.sp;
     const int tid = p_tid(), nth = p_nthreads();
-    const int V = pb->V, P = pb->P, T = pb->T, n_ops = pb->n_ops, D = pb->D;
-    const uint64_t active_mask = pb->active_mask;
-    const PointLayout L = make_point_layout(n_ops, V, P, T, pb->n_slots, D, nth);
+    const int V = a.pb->V, P = a.pb->P, T = a.pb->T, n_ops = a.pb->n_ops, D = a.pb->D;
+    const uint64_t active_mask = a.pb->active_mask;
+    const PointLayout L = make_point_layout(n_ops, V, P, T, a.pb->n_slots, D, nth, BOUNDED ? 1 : 0);
+    const PB pb = pb_with_limits((PB)a.pb, lds + L.lim, n_ops > 0 ? n_ops : 1);
     double *s_seed = lds + L.seed, *s_par = lds + L.par, *s_prefix = lds + L.prefix, *s_sol = lds + L.sol, *s_best = lds + L.best;
     double *s_grad = lds + L.grad, *s_gg = lds + L.gg, *s_ex = lds + L.ex, *s_slots = lds + L.slots;
     double *s_frames = lds + L.frames, *s_tips = lds + L.tips, *s_jac = lds + L.jac;
@@ -127,10 +131,11 @@ BIOIK_DEV void point_body(const SolveArgs& a, uint64_t unit, double* lds) {
         BIOIK_FP_STRICT
         uint32_t o0, o1;
         philox2x32_10(key, rng_ctr0(0, (uint32_t)pb->ops[k].gene), rng_ctr1(count, 0u, RNG_POINT_RANDOM), o0, o1);
-        return rng_uniform(o0, o1) * (pb->ops[k].vmax - pb->ops[k].vmin) + pb->ops[k].vmin;
+        return rng_uniform(o0, o1) * (op_limit<LIM_VMAX>(pb, k) - op_limit<LIM_VMIN>(pb, k)) + op_limit<LIM_VMIN>(pb, k);
     };
     for (int i = tid; i < V; i += nth) s_seed[i] = a.seeds[q * V + i];
     for (int i = tid; i < P; i += nth) s_par[i] = a.params[q * P + i];
+    if constexpr (BOUNDED) stage_bounds(a.pb, a.var_lo + q * (uint64_t)V, a.var_hi + q * (uint64_t)V, lds + L.lim, M, tid, nth);
     p_wave_sync();
     const QueryCtx qc{s_seed, s_par};
     for (int k = tid; k < n_ops; k += nth) {  // solution = problem.initial_guess (ik_gradient.cpp:150, :281); threads > 0: a random one (:157-159, :283-285)
@@ -156,7 +161,7 @@ BIOIK_DEV void point_body(const SolveArgs& a, uint64_t unit, double* lds) {
     const int my_op = tid < D ? pb->op_of_gene[tid] : -1;
     auto fitness_of = [&](const XV& x) { return eval_exact_primary(pb, x, qc, s_slots, s_prefix); };
     auto clip_op = [&](double v, int k) {  // RobotInfo::clip, robot_info.h:109-113 (clamp2: max first, then min)
-        const double lo = pb->ops[k].clip_min, hi = pb->ops[k].clip_max;
+        const double lo = op_limit<LIM_CLIP_MIN>(pb, k), hi = op_limit<LIM_CLIP_MAX>(pb, k);
         if (v < lo) v = lo;
         if (v > hi) v = hi;
         return v;

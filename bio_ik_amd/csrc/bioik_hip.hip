@@ -65,14 +65,17 @@ static thread_local std::string g_err;
 // the register budget of four wavefronts per SIMD (FIXED = 4: fitness values parked in LDS, accessors rebuilt behind the walks).  (Its 168-register sibling
 // k_solve_lean_clj of rounds 3 - 5 served the one LDS band in which a CU holds exactly twelve queries; retired in round 6: this build runs there too.)
 // k_solve_point: the point solvers gd_c / jac (bioik_gradient.h): one wavefront per query, at most 64 KiB of LDS (SolveLauncher::solve_point)
-#ifndef BIOIK_SOLVE_WAVES_PER_SIMD
-#define BIOIK_SOLVE_WAVES_PER_SIMD 3  // register budget of k_solve: wavefronts per SIMD (its __launch_bounds__)
-#endif
+// k_solve_bounded, k_solve_point_bounded: k_solve's and k_solve_point's bodies with the third pointer flavour (BoundedProbPtr, bioik_platform.h): a call with per-query variable
+//                   bounds (bioik_solve_batch_bounded) reads every bound from its query's table in LDS instead of from the problem block.  Only such calls reach them,
+//                   and they reach no other row -- the gating by which a TouchGoal only ever reaches k_solve.  Their rows are written in bioik_bounded_rows.h and their
+//                   __global__ definitions are compiled in a translation unit of their own (bioik_bounded.hip): in one device module with them, the register allocation
+//                   of k_solve and k_solve_lean comes out differently (profiles/per_query_bounds_metadata.log), and the existing kernels are to stay as they are
+#include "bioik_bounded_rows.h"  // (BIOIK_SOLVE_WAVES_PER_SIMD: the register budget of k_solve)
 #ifndef BIOIK_DENSE_WAVES
 #define BIOIK_DENSE_WAVES 4
 #endif
 // (ROW(X, name, bounds, body...): X is handed through to the row macro, for lists whose entries are X(name))
-#define BIOIK_SOLVE_BODY_KERNELS(ROW, X)                                                                   \
+#define BIOIK_SOLVE_BODY_KERNELS_HERE(ROW, X)                                                              \
     ROW(X, k_solve, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<false>)                                  \
     ROW(X, k_solve_lean, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<true>)                              \
     ROW(X, k_solve_lean_cl, (256, BIOIK_SOLVE_WAVES_PER_SIMD), solve_body<true, true>)                     \
@@ -81,7 +84,9 @@ static thread_local std::string g_err;
     ROW(X, k_solve_lean_cl64w4, (64, BIOIK_DENSE_WAVES), solve_body<true, true, false, true, 1>)           \
     ROW(X, k_solve_lean_lin, (64, 4), solve_body<true, true, false, true, 3>)                              \
     ROW(X, k_solve_lean_clj4, (64, 4), solve_body<true, true, true, true, 4>)
-#define BIOIK_SOLVE_KERNELS(ROW) BIOIK_SOLVE_BODY_KERNELS(ROW, ) ROW(, k_solve_point, (64), point_body)
+#define BIOIK_SOLVE_KERNELS_HERE(ROW) BIOIK_SOLVE_BODY_KERNELS_HERE(ROW, ) ROW(, k_solve_point, (64), point_body)  // (defined in this translation unit)
+#define BIOIK_SOLVE_BODY_KERNELS(ROW, X) BIOIK_SOLVE_BODY_KERNELS_HERE(ROW, X) BIOIK_BOUNDED_BODY_KERNELS(ROW, X)
+#define BIOIK_SOLVE_KERNELS(ROW) BIOIK_SOLVE_KERNELS_HERE(ROW) BIOIK_BOUNDED_KERNELS(ROW)
 #define BIOIK_ENUM_(X, name, ...) name,
 enum class SolveKernel { BIOIK_SOLVE_KERNELS(BIOIK_ENUM_) };
 #undef BIOIK_ENUM_
@@ -252,8 +257,11 @@ static void be_stream_destroy(stream_t s) {
         extern __shared__ double lds[];                          \
         __VA_ARGS__(a, blockIdx.x, lds);                         \
     }
-BIOIK_SOLVE_KERNELS(BIOIK_GLOBAL_)
+BIOIK_SOLVE_KERNELS_HERE(BIOIK_GLOBAL_)
 #undef BIOIK_GLOBAL_
+#define BIOIK_GLOBAL_DECL_(X, name, bounds, ...) __global__ void name(SolveArgs a);  // (bioik_bounded.hip)
+BIOIK_BOUNDED_KERNELS(BIOIK_GLOBAL_DECL_)
+#undef BIOIK_GLOBAL_DECL_
 __global__ void k_select(SelectArgs a) { select_body(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(64) k_select_wave(SelectArgs a) { select_coop(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }  // a wavefront per query: calls of few queries with many islands
 // island migration between two launches of a solve (migrate_mark, migrate_coop): a lane per entry of the hand-over list, then a wavefront per query
@@ -284,6 +292,7 @@ __global__ void __launch_bounds__(256) k_eval_check(EvalArgs a) {
     extern __shared__ double lds[];
     eval_check_body(a, blockIdx.x, lds);
 }
+__global__ void __launch_bounds__(64) k_eval_bounds(BoundsArgs a) { eval_bounds_body(a, (uint64_t)blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(256) k_eval_arith(ArithArgs a) { arith_body(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_stream_fitness(StreamArgs a) {
     extern __shared__ double lds[];
@@ -322,6 +331,10 @@ struct SolveArrays {
     double *solutions, *fitness;
     int32_t *success, *steps;
     int32_t* count;  // ranked calls (bioik_solve_batch_ranked): the distinct solutions returned per query; null otherwise
+    // per-query variable bounds (bioik_solve_batch_bounded), [n][V] each: both set (a bounded call: k_solve_bounded / k_solve_point_bounded) or both null
+    const double* var_lo = nullptr;
+    const double* var_hi = nullptr;
+    bool bounded() const { return var_lo != nullptr; }
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -596,8 +609,8 @@ static void set_mapping(DevSolveParams& sp, int& lanes, const LaneMapping& m) {
     lanes = m.lanes, sp.species_parallel = m.species_parallel, sp.child_cols = m.child_cols, sp.child_pairs = m.child_pairs, sp.columnless = m.columnless;
 }
 // the LDS layout of a solve's workgroup under a lane mapping: solve_layout (bioik_kernels.h), the function solve_setup takes its own layout from
-static LdsLayout solve_layout(const DevProblem& d, int lambda, bool exact, const LaneMapping& m, bool helped = false) {
-    return solve_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, d.n_secondary > 0, lambda, exact, m, helped);
+static LdsLayout solve_layout(const DevProblem& d, int lambda, bool exact, const LaneMapping& m, bool helped = false, bool bounded = false) {
+    return solve_layout(d.n_ops, d.V, d.P, d.T, d.n_slots, d.n_secondary > 0, lambda, exact, m, helped, bounded);
 }
 // the dynamic LDS of a function-level kernel of `nth` lanes, in bytes: the layout the eval_*_body / stream_fitness_body functions index (bioik_kernels.h)
 static size_t eval_lds_bytes(const bioik_problem* p, int nth) {
@@ -669,6 +682,7 @@ struct SolveLauncher {
     uint64_t units = 0;
     void* island_ws = nullptr;  // (a stream-ordered fallback allocation of the per-island results, if any)
     bool fused_select = false;
+    const bool bounded;  // per-query variable bounds (SolveArrays::var_lo / var_hi): the bounded rows of the kernel table, and their LDS layout
     const RankedArgs* ranked = nullptr;  // bioik_solve_batch_ranked: the per-island arrays are ranked by k_select_ranked (k, min_distance and the outputs: here), never reduced to one
     // the mapping (choose_mapping)
     int nth = 0, groups = 1;
@@ -681,7 +695,7 @@ struct SolveLauncher {
     bool migrating = false;      // ... or: the boundaries of bioik_solve_params::island_migration, with k_migrate_mark and k_migrate between two launches
 
     SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t s, const SolveSwitches& w, unsigned int* err)
-        : p(p_), sp(sp_in), call(arrays), n(arrays.n), stream(s), sw(w), error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus) {
+        : p(p_), sp(sp_in), call(arrays), n(arrays.n), stream(s), sw(w), error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus), bounded(arrays.bounded()) {
         if (dp.n_secondary > 0 && sp.lambda < 2) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "population must be >= 2 when secondary goals are present");
         units = (uint64_t)n * sp.islands;
         if (units > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many (query, island) units for one launch: split the batch");
@@ -798,18 +812,20 @@ struct SolveLauncher {
     }
     // gd / gd_r / gd_c / jac: one wavefront per (query, island), its own (small) LDS layout
     void solve_point() {
-        const size_t lds_point = (size_t)make_point_layout(dp.n_ops, dp.V, dp.P, dp.T, dp.n_slots, dp.D, 64).total * 8;
+        const size_t lds_point = (size_t)make_point_layout(dp.n_ops, dp.V, dp.P, dp.T, dp.n_slots, dp.D, 64, bounded ? 1 : 0).total * 8;
         if (lds_point > 64 * 1024) throw Error(BIOIK_ERR_UNSUPPORTED, "problem too large for the gd / jac kernels (more than 64 KiB of LDS per query)");
         SolveArgs pa;
         pa.pb = p->pb(), pa.sp = sp, pa.seeds = call.seeds, pa.params = call.goal_params;
+        pa.var_lo = call.var_lo, pa.var_hi = call.var_hi;
         result_arrays(pa, false);
         pa.phase_cycles = nullptr;
         set_deadline(p, sp, stream, pa);
-        if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, 64 lanes, %zu B of LDS\n", kSolveKernelNames[(int)SolveKernel::k_solve_point], lds_point);
-        launch_kernel(SolveKernel::k_solve_point, pa, units, 64, lds_point, stream);
+        const SolveKernel kind = bounded ? SolveKernel::k_solve_point_bounded : SolveKernel::k_solve_point;
+        if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, 64 lanes, %zu B of LDS\n", kSolveKernelNames[(int)kind], lds_point);
+        launch_kernel(kind, pa, units, 64, lds_point, stream);
         select_islands(pa);
     }
-    size_t lds_need(const LaneMapping& m, bool helped = false) const { return (size_t)solve_layout(dp, sp.lambda, exact, m, helped).total * 8; }  // bytes of LDS per workgroup
+    size_t lds_need(const LaneMapping& m, bool helped = false) const { return (size_t)solve_layout(dp, sp.lambda, exact, m, helped, bounded).total * 8; }  // bytes of LDS per workgroup
     void choose_mapping() {
         // Mapping of a (query, island) onto lanes.  Candidates: 128 lanes (one wavefront per species) with every child kept in LDS
         // and evaluated in pairs / kept / re-derived from the RNG, or 64 lanes (one wavefront, the species one after the other).  A CU
@@ -822,7 +838,7 @@ struct SolveLauncher {
         quat = dp.n_quat > 0;  // winners re-derived: their momentum is taken before the quaternion genes are renormalised
         manual = sw.manual();
         // children computed where they are read (no genotype columns in LDS): the lean flavour can, whenever it is chosen below
-        can_columnless = lean_capable(dp) && !sw.general_set;
+        can_columnless = lean_capable(dp) && !sw.general_set && !bounded;  // (a bounded call: the general flavour's kernel with the query's table, k_solve_bounded, and no other)
         sp.columnless = 0;
         // the problems the mapping with both species on the halves of one wavefront exists for (kHalves: the first launch of a solve in two, plan_handovers), and those
         // among them the dense kernel is compiled for (the throughput schedule's whole solve, the latency schedule's chip-filling start: `throughput`, `dense_ok` below)
@@ -926,11 +942,11 @@ struct SolveLauncher {
         groups = sp.species_parallel ? 2 : 1;
         lds = lds_need(mapping_of(sp, nth));
         if (lds > kLds) throw Error(BIOIK_ERR_UNSUPPORTED, "problem needs more LDS per workgroup than a CU has");
-        lean = lean_capable(dp) && !(sw.general_set && sw.general);
+        lean = lean_capable(dp) && !(sw.general_set && sw.general) && !bounded;
         halves_ok = lean && halves_shape;  // the first launch's mapping exists for this problem
     }
     void report_mapping() const {  // diagnostics: the lane mapping and the residency it gives
-        const LdsLayout L = solve_layout(dp, sp.lambda, exact, mapping_of(sp, nth));
+        const LdsLayout L = solve_layout(dp, sp.lambda, exact, mapping_of(sp, nth), false, bounded);
         int n_rev = 0, n_pos = 0, n_rot = 0;  // revolute ops and how many of them the walk takes through a sparse form
         for (int k = 0; k < dp.n_chain_ops; k++)
             if (dp.ops[k].type == BIOIK_OP_REVOLUTE) n_rev++, n_pos += dp.ops[k].pos_kind != BIOIK_POS_GENERAL, n_rot += dp.ops[k].rot_kind != BIOIK_ROT_GENERAL;
@@ -970,6 +986,7 @@ struct SolveLauncher {
         const bool helped_launch = lean && four_waves && !manual && !sw.four_waves && args.sp.columnless && sw.helped > 0 &&
                                    (units <= (uint64_t)sw.helped || (args.unit_list != nullptr && args.resident != nullptr));
         if (helped_launch) return SolveKernel::k_solve_lean_cl4h;
+        if (bounded) return SolveKernel::k_solve_bounded;
         if (!lean) return SolveKernel::k_solve;
         if (lin_launch) return SolveKernel::k_solve_lean_lin;
         if (!args.sp.columnless) return SolveKernel::k_solve_lean;
@@ -1111,6 +1128,7 @@ static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const So
     a.sp = s.sp;
     a.seeds = arrays.seeds;
     a.params = arrays.goal_params;
+    a.var_lo = arrays.var_lo, a.var_hi = arrays.var_hi;
     a.phase_cycles = nullptr;
     a.sort_key_drop = sw.sort_key_drop;
     a.preselect = sw.preselect | (sw.tie_test_bits << 8);
@@ -1169,7 +1187,7 @@ static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, const Sol
     const SolveSwitches sw = switches();  // (the diagnostic switches as last parsed: no environment access on the launch path)
     auto run = [&](const SolveSwitches& w) { launch_solve(p, sp, arrays, stream, w, error_word); };
     const uint64_t units = (uint64_t)arrays.n * (uint64_t)sp.islands;
-    const bool kind_ok = sw.autotune > 0 && !sw.manual() && !sw.general_set && !sw.two_phase_set && sw.drain_test == 0 && sw.dense_handover == 0 && sp.solver == 0 &&
+    const bool kind_ok = !arrays.bounded() /* (a bounded call neither takes nor changes the measured choice, as the ranked entries) */ && sw.autotune > 0 && !sw.manual() && !sw.general_set && !sw.two_phase_set && sw.drain_test == 0 && sw.dense_handover == 0 && sp.solver == 0 &&
                          sp.schedule != BIOIK_SCHEDULE_THROUGHPUT && sp.timeout_ticks == 0 && units >= 8 * (uint64_t)p->model->dev.cus && sp.max_steps >= 8;
     if (!kind_ok || be_stream_capturing(stream)) {
         run(sw);
@@ -1216,6 +1234,7 @@ static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, const Sol
 
 // what every solve entry point asks of its arrays (goal parameters only where the problem has some)
 static void check_arrays(const bioik_problem* p, const SolveArrays& a) {
+    if ((a.var_lo == nullptr) != (a.var_hi == nullptr)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "var_lo and var_hi: both or neither (exactly one of them is null)");
     if (a.n && (!a.seeds || !a.solutions || !a.fitness || !a.success || !a.steps || (p->host.dev.P > 0 && !a.goal_params))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null array");
 }
 // The device-pointer entries do not wait for their solves: a rendezvous time-out of an EARLIER solve through one of them is reported by the handle's next call
@@ -1356,11 +1375,17 @@ int bioik_resolve_islands(const bioik_problem* p, const bioik_solve_params* para
     *islands = r.islands, *island_sync = r.island_sync;
     API_END
 }
+// (the plain entries are the bounded ones with both arrays of bounds null: one path, the same launches, kernels and bits)
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds, const double* d_goal_params,
                              double* d_solutions, double* d_fitness, int32_t* d_success, int32_t* d_steps, void* hip_stream) {
+    return bioik_solve_batch_bounded_device(p, params, n, d_seeds, d_goal_params, nullptr, nullptr, d_solutions, d_fitness, d_success, d_steps, hip_stream);
+}
+int bioik_solve_batch_bounded_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds, const double* d_goal_params,
+                                     const double* d_var_lo, const double* d_var_hi, double* d_solutions, double* d_fitness, int32_t* d_success, int32_t* d_steps,
+                                     void* hip_stream) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    const SolveArrays arrays{n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, nullptr};
+    const SolveArrays arrays{n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, nullptr, d_var_lo, d_var_hi};
     check_arrays(p, arrays);
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
@@ -1441,7 +1466,8 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     const size_t V = p->host.dev.V, P = p->host.dev.P, n = caller.n;
     // arena layout: [seeds | goal_params] in, [solutions | fitness | success | steps] out, every block 64-byte aligned
     auto up = [](size_t b) { return (b + 63) / 64 * 64; };
-    const size_t o_seeds = 0, o_par = o_seeds + up(n * V * 8), in_bytes = o_par + up(n * P * 8);
+    const size_t nb = caller.bounded() ? n * V * 8 : 0;  // (a bounded call: its two arrays of bounds behind the goal parameters; they stay in the arena as long as the call's launches)
+    const size_t o_seeds = 0, o_par = o_seeds + up(n * V * 8), o_lo = o_par + up(n * P * 8), o_hi = o_lo + up(nb), in_bytes = o_hi + up(nb);
     const size_t K = ranked ? (size_t)ranked->k : 1;  // result rows per query; a ranked solve adds count [n]
     const size_t o_sol = in_bytes, o_fit = o_sol + up(n * K * V * 8), o_suc = o_fit + up(n * K * 8), o_steps = o_suc + up(n * K * 4), o_cnt = o_steps + up(n * K * 4),
                  total = o_cnt + (ranked ? up(n * 4) : 0);
@@ -1460,6 +1486,7 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     const stream_t st = sl.stream;
     std::memcpy(hd + o_seeds, caller.seeds, n * V * 8);
     if (P) std::memcpy(hd + o_par, caller.goal_params, n * P * 8);
+    if (nb) std::memcpy(hd + o_lo, caller.var_lo, nb), std::memcpy(hd + o_hi, caller.var_hi, nb);
     // (a call of a few queries -- MoveIt's one pose per call -- reads its inputs where they lie: the page-locked arena is mapped into the device's address space, and a
     // few hundred bytes per workgroup over the bus cost less than a DMA transfer in front of the launch)
     const bool direct_inputs = n <= 16;
@@ -1471,7 +1498,7 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
     // for a one-launch solve -- with the transfers in of the handle's next solves behind it: nothing would overlap
     // (profiles/r03_inflight_and_schedule.log, host pipeline).
     const SolveArrays arena{n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
-                            (int32_t*)(hd + o_steps), ranked ? (int32_t*)(hd + o_cnt) : nullptr};
+                            (int32_t*)(hd + o_steps), ranked ? (int32_t*)(hd + o_cnt) : nullptr, nb ? (const double*)(in_base + o_lo) : nullptr, nb ? (const double*)(in_base + o_hi) : nullptr};
     if (ranked) {  // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
         const RankedArgs r = ranked_args(ranked->k, ranked->min_distance, arena);
         launch_solve(p, sp, arena, st, switches(), p->h_error + (&sl - p->io), &r);
@@ -1501,9 +1528,13 @@ static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint6
 
 int bioik_solve_batch(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params, double* solutions,
                       double* fitness, int32_t* success, int32_t* steps) {
+    return bioik_solve_batch_bounded(p, params, n, seeds, goal_params, nullptr, nullptr, solutions, fitness, success, steps);
+}
+int bioik_solve_batch_bounded(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params, const double* var_lo,
+                              const double* var_hi, double* solutions, double* fitness, int32_t* success, int32_t* steps) {
     API_BEGIN
     if (!p || !params) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr};
+    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr, var_lo, var_hi};
     check_arrays(p, arrays);
     solve_host(p, *params, p->first_query, arrays);
     API_END
@@ -1540,9 +1571,13 @@ int bioik_solve_batch_ranked(bioik_problem* p, const bioik_solve_params* params,
 // Asynchronous host-pointer solve: a caller with a stream of batches keeps up to kIoSlots (six) of them in flight on ONE handle.
 int bioik_solve_batch_submit(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params, double* solutions,
                              double* fitness, int32_t* success, int32_t* steps, uint64_t* ticket) {
+    return bioik_solve_batch_bounded_submit(p, params, n, seeds, goal_params, nullptr, nullptr, solutions, fitness, success, steps, ticket);
+}
+int bioik_solve_batch_bounded_submit(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params, const double* var_lo,
+                                     const double* var_hi, double* solutions, double* fitness, int32_t* success, int32_t* steps, uint64_t* ticket) {
     API_BEGIN
     if (!p || !params || !ticket) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
-    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr};
+    const SolveArrays arrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr, var_lo, var_hi};
     check_arrays(p, arrays);
     std::lock_guard<std::mutex> lock(p->mtx);
     const uint64_t t = p->next_ticket++;
@@ -1754,6 +1789,25 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
     API_END
 }
 
+int bioik_eval_bounds(bioik_problem* p, size_t n, const double* var_lo, const double* var_hi, double* out) {
+    API_BEGIN
+    if (!p || (n && (!var_lo || !var_hi || !out))) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return BIOIK_OK;
+    if (n > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many queries for one launch");
+    std::lock_guard<std::mutex> lock(p->mtx);
+    DeviceGuard on_device(p->model->device);
+    const size_t V = p->host.dev.V, M = p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1;
+    DevBuf dlo(n * V * 8), dhi(n * V * 8), dout(n * M * 6 * 8);
+    be_h2d(dlo.p, var_lo, n * V * 8, 0);
+    be_h2d(dhi.p, var_hi, n * V * 8, 0);
+    BoundsArgs a;
+    a.pb = p->pb(), a.n = n, a.var_lo = dlo.as<double>(), a.var_hi = dhi.as<double>(), a.out = dout.as<double>();
+    LAUNCH(k_eval_bounds, eval_bounds_body(a, b_, p_tid()), n, 64, 0, 0, a);
+    be_d2h(out, dout.p, n * M * 6 * 8, 0);
+    be_sync(0);
+    API_END
+}
+
 int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out) {
     API_BEGIN
     const int ni = arith_in(op), no = arith_out(op);
@@ -1776,6 +1830,12 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
     API_END
 }
 
+int bioik_problem_op_count(const bioik_problem* p) { return p ? p->host.dev.n_ops : BIOIK_ERR_INVALID_ARGUMENT; }
+int bioik_problem_op_variables(const bioik_problem* p, int32_t* variable, int32_t* gene) {
+    if (!p || !variable || !gene) return BIOIK_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < p->host.dev.n_ops; k++) variable[k] = p->host.dev.ops[k].var, gene[k] = p->host.dev.ops[k].gene;
+    return BIOIK_OK;
+}
 int bioik_problem_carry_doubles(const bioik_problem* p) { return p ? carry_doubles(p->host.dev.n_ops) : BIOIK_ERR_INVALID_ARGUMENT; }
 int bioik_eval_migrate(bioik_problem* p, int32_t islands, size_t n_queries, const int32_t* live, double* rows) {
     API_BEGIN

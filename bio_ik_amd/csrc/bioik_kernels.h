@@ -36,7 +36,7 @@ struct LdsLayout {  // offsets in doubles; "g_" regions exist once per species g
                          // a four-word mailbox per species (offsets of the parent's genes and of the momentum table, the stream's counter, the children to walk)
 };
 BIOIK_HD LdsLayout make_layout(int n_ops, int V, int P, int T, int n_slots, int nthreads, int lambda, int has_secondary, int child_cols = 1,
-                               int groups = 1, int slot_sets = 1, int fit_park = 0, int fc_in_pop = 0, int helped = 0) {
+                               int groups = 1, int slot_sets = 1, int fit_park = 0, int fc_in_pop = 0, int helped = 0, int bounded = 0) {
     LdsLayout L;
     const int m = n_ops > 0 ? n_ops : 1;
     int o = 0;
@@ -46,7 +46,7 @@ BIOIK_HD LdsLayout make_layout(int n_ops, int V, int P, int T, int n_slots, int 
     L.sol = o, o += m;
     L.prefix = o, o += 8;               // frame behind the leading non-gene joints (DevProblem::n_prefix), per query
     L.state = o, o += 2 * 8 + 4 + 4;    // species bookkeeping [2][8], workgroup broadcast slots [4], fitness / success flag of the solution [2] (+2 spare)
-    L.clip = o, o += 2 * m;             // RobotInfo clip_min | clip_max per op (robot_info.h:109-113), staged once per query
+    L.clip = o, o += (bounded ? LIM_N : 2) * m;  // RobotInfo clip_min | clip_max per op (robot_info.h:109-113), staged once per query; bounded flavour: the query's whole table of bounds, [LIM_N][m] (BoundedProbPtr)
     L.help = o, o += helped ? 8 : 0;
     L.xcol = o, o += m * nthreads * (child_cols >= 0 ? child_cols : 1);  // genotype columns: [col][op][lane]; none when children are computed where they are read
     L.slots = o, o += n_slots * 7 * nthreads * (slot_sets > 0 ? slot_sets : 1);  // parked branch frames, one set per child a lane walks at once
@@ -105,9 +105,9 @@ struct LaneMapping {
     int child_pairs;       // a lane walks its children two at a time: a second set of parked frames
     int columnless;        // children computed where they are read: no genotype columns, and under exact FK a generation's fitness values parked in LDS
 };
-BIOIK_HD LdsLayout solve_layout(int n_ops, int V, int P, int T, int n_slots, bool has_secondary, int lambda, bool exact, const LaneMapping& m, bool helped) {
+BIOIK_HD LdsLayout solve_layout(int n_ops, int V, int P, int T, int n_slots, bool has_secondary, int lambda, bool exact, const LaneMapping& m, bool helped, bool bounded = false) {
     return make_layout(n_ops, V, P, T, n_slots, m.lanes, lambda, has_secondary ? (exact ? 2 : 1) : 0, m.columnless ? 0 : (m.child_cols > 0 ? m.child_cols : 1),
-                       m.species_parallel ? 2 : 1, m.child_pairs ? 2 : 1, (m.columnless && exact) ? 1 : 0, 1, helped ? 1 : 0);
+                       m.species_parallel ? 2 : 1, m.child_pairs ? 2 : 1, (m.columnless && exact) ? 1 : 0, 1, helped ? 1 : 0, bounded ? 1 : 0);
 }
 // doubles of a unit's state between two launches of a solve (a hand-over row): per species (in ranking order) the elite buffer in use -- two individuals, genes and
 // momentum: 4 m each --, the solution, the bookkeeping block (the other elite buffer is written before it is read: it does not travel)
@@ -686,6 +686,10 @@ struct SolveArgs {
     int32_t debug_flags = 0;                       // tests: bit 0 -- the helper wavefront of species 0 never answers (the host simulator's rendezvous test)
     unsigned int* resident = nullptr;              // [16][32]: word 32 x of XCD x
     int32_t drain_below = 0, drain_min_steps = 0;  // (wavefronts per XCD)  // (drain_below < 0: test pattern -- unit u leaves after 1 + hash(u) % -drain_below steps)
+    // Per-query variable bounds (bioik_solve_batch_bounded; the bounded kernels only: k_solve_bounded, k_solve_point_bounded): [n][V] each, indexed by robot variable.
+    // Every launch of the call stages its queries' tables from them (stage_bounds), the launches that continue handed-over units too: they live as long as the call's chain.
+    const double* var_lo = nullptr;
+    const double* var_hi = nullptr;
 };
 
 struct SpeciesState {
@@ -752,7 +756,8 @@ struct SpeciesState {
 // lane and trip (k_solve_lean_lin: populations of up to 32 children per species -- the reference's own parameters);  4 = 64 lanes, halves, exact FK,
 // secondary goals, the pre-selected children of both species walked as one list (JOINT; k_solve_lean_clj4);  5 = FIXED 2 with two helper wavefronts (k_solve_lean_cl4h)
 // ---------------------------------------------------------------------------------------------------------
-template <bool LEAN_, bool CL_, bool JOINT_, bool SLIM_, int FIXED_>
+// BOUNDED: the general flavour with per-query variable bounds (BoundedProbPtr, bioik_platform.h): k_solve_bounded
+template <bool LEAN_, bool CL_, bool JOINT_, bool SLIM_, int FIXED_, bool BOUNDED_ = false>
 struct SolveFrame {
     static constexpr bool LEAN = LEAN_, CL = CL_, JOINT = JOINT_, SLIM = SLIM_;
     static constexpr int FIXED = FIXED_;
@@ -765,7 +770,8 @@ struct SolveFrame {
     static_assert(FIXED == 0 || (SLIM && CL), "the fixed mappings are builds of the computed-children kernel for the 128-register budget");
     static_assert(LEAN || !CL, "computed children: lean flavour only (quaternion genes are renormalised in place)");
     static_assert(CL || !JOINT, "the joint walk of both species' children exists for computed children only");
-    typedef typename std::conditional<LEAN, LeanProbPtr, ProbPtr>::type PB;
+    static_assert(!BOUNDED_ || (!LEAN && !CL && FIXED == 0), "per-query bounds: the general flavour's kernel only");
+    typedef typename std::conditional<BOUNDED_, BoundedProbPtr, typename std::conditional<LEAN, LeanProbPtr, ProbPtr>::type>::type PB;
     const SolveArgs& a;
     const DevSolveParams& sp;
     double* const lds;
@@ -952,7 +958,7 @@ BIOIK_DEV bool solve_setup(Frame& F, uint64_t unit_in) {
     const int G = HALVES ? 32 : (WAVE2 ? 64 : nth / groups);        // lanes per species group (a multiple of 64, or half a wavefront)
     const int g_shift = HALVES ? 5 : (WAVE2 ? 6 : ((G & (G - 1)) == 0 ? 31 - __builtin_clz((unsigned)G) : -1));  // the group sizes the launcher produces are powers of two: no integer division
     // (solve_layout, by which the launcher sizes the LDS of every workgroup, must agree with this call)
-    const LdsLayout L = make_layout(n_ops, V, P, T, pb->n_slots, nth, lambda, has_sec ? (exact ? 2 : 1) : 0, columnless ? 0 : n_cols, groups, child_pairs ? 2 : 1, (CL && exact) ? 1 : 0, 1, HELPED ? 1 : 0);
+    const LdsLayout L = make_layout(n_ops, V, P, T, pb->n_slots, nth, lambda, has_sec ? (exact ? 2 : 1) : 0, columnless ? 0 : n_cols, groups, child_pairs ? 2 : 1, (CL && exact) ? 1 : 0, 1, HELPED ? 1 : 0, pb_bounded<PB>::value ? 1 : 0);
     double* s_seed = lds + L.seed;
     double* s_par = lds + L.par;
     double* s_pop = lds + L.pop;
@@ -982,7 +988,7 @@ BIOIK_DEV bool solve_setup(Frame& F, uint64_t unit_in) {
     p_barrier();  // (the ONE hardware barrier of the helped kernel: its helper wavefronts never reach another, so from here on its two main wavefronts meet at wg_barrier's words)
     const QueryCtx qc{s_seed, s_par};
     const uint32_t key = rng_query_key(sp.random_seed, sp.first_query + q, island);
-    F.pb = pb, F.unit = unit, F.q = q, F.island = island, F.key = key, F.resume = resume;
+    F.pb = pb_with_limits(pb, s_clip, M), F.unit = unit, F.q = q, F.island = island, F.key = key, F.resume = resume;
     F.tid0 = tid0, F.nth = nth, F.V = V, F.P = P, F.T = T, F.n_ops = n_ops, F.D = D, F.lambda = lambda, F.n_cols = n_cols, F.groups = groups, F.G = G, F.g_shift = g_shift;
     F.active_mask = active_mask, F.has_sec = has_sec, F.exact = exact, F.child_pairs = child_pairs;
     F.L = L;
@@ -1054,7 +1060,11 @@ BIOIK_DEV void solve_init(Frame& F) {
             s_pop[(int)p_load_device(c + 2 * BF + M + r * 8 + 4) * SP + (i - r * BF)] = p_load_device(c + i);
         }
     }
-    for (int k = tid; k < n_ops; k += nth) s_clip[k] = pb->ops[k].clip_min, s_clip[M + k] = pb->ops[k].clip_max;
+    if constexpr (pb_bounded<PB>::value) {  // the query's table of bounds from its rows of the call's arrays (in every launch of the call: a.var_lo / a.var_hi)
+        stage_bounds(pb, a.var_lo + q * (uint64_t)V, a.var_hi + q * (uint64_t)V, s_clip, M, tid, nth);
+    } else {
+        for (int k = tid; k < n_ops; k += nth) s_clip[k] = pb->ops[k].clip_min, s_clip[M + k] = pb->ops[k].clip_max;
+    }
     wg_barrier();
     if (pb->n_prefix > 0) {  // the joints in front of the first gene see the seed in every individual: walk them once per query
         if (tid == 0) f7_store(s_prefix, fk_prefix(pb, XV{s_sol, 1}));
@@ -1799,7 +1809,7 @@ BIOIK_DEV void solve_generation(Frame& F, SpeciesState& S, double*& popS, int ra
             const double pg0 = child_parent_gradient(d0, d1, 0), pg1 = child_parent_gradient(d0, d1, 1);
             pgt[k] = pg0, pgt[M + k] = pg1;
             if constexpr (WAVE2)
-                inside = pb->ops[k].gene >= 0 && !pb->ops[k].unbounded && avoid_limits_surely_free(p0g[k], pg0, pg1, pb->ops[k].vmin, pb->ops[k].vmax, pb->ops[k].span);
+                inside = pb->ops[k].gene >= 0 && !op_unbounded(pb, k) && avoid_limits_surely_free(p0g[k], pg0, pg1, op_limit<LIM_VMIN>(pb, k), op_limit<LIM_VMAX>(pb, k), op_limit<LIM_SPAN>(pb, k));
         }
         if constexpr (WAVE2) inside_mask = has_sec ? p_ballot(inside) : 0ull;  // (a group is one wavefront and an op a lane: at most 64 ops)
         group_sync(G);
@@ -2143,7 +2153,7 @@ BIOIK_DEV bool solve_species_and_checks(Frame& F, int step) {
                 double v = cb[k];
                 if (pb->ops[k].gene >= 0) {
                     philox2x32_10(key, rng_ctr0(0, (uint32_t)pb->ops[k].gene), wc1, o0, o1);
-                    v = rng_uniform(o0, o1) * (pb->ops[k].vmax - pb->ops[k].vmin) + pb->ops[k].vmin;
+                    v = rng_uniform(o0, o1) * (op_limit<LIM_VMAX>(pb, k) - op_limit<LIM_VMIN>(pb, k)) + op_limit<LIM_VMIN>(pb, k);
                 }
                 cb[k] = v, cb[M + k] = 0.0;
                 cb[2 * M + k] = v, cb[3 * M + k] = 0.0;
@@ -2271,9 +2281,9 @@ BIOIK_DEV void solve_epilogue(Frame& F) {
     BIOIK_EPILOGUE_SCOPE_END
 }
 
-template <bool LEAN, bool CL = false, bool JOINT = false, bool SLIM = false, int FIXED = 0>
+template <bool LEAN, bool CL = false, bool JOINT = false, bool SLIM = false, int FIXED = 0, bool BOUNDED = false>
 BIOIK_DEV void solve_body(const SolveArgs& a, uint64_t unit_in, double* lds) {
-    typedef SolveFrame<LEAN, CL, JOINT, SLIM, FIXED> Frame;
+    typedef SolveFrame<LEAN, CL, JOINT, SLIM, FIXED, BOUNDED> Frame;
     Frame F(a, lds);
     if (!solve_setup(F, unit_in)) return;
     if constexpr (Frame::HELPED)
@@ -2437,6 +2447,27 @@ BIOIK_DEV void eval_check_body(const EvalArgs& a, uint64_t block, double* lds) {
 // reference (tests/test_arith_headers.py) -- bit parity between two users of one header cannot show a defect of the header itself.
 // ---------------------------------------------------------------------------------------------------------
 enum { ARITH_SINCOS = 0, ARITH_QROT = 1, ARITH_QMUL = 2, ARITH_DOT3 = 3, ARITH_DOT4 = 4, ARITH_REVOLUTE = 5, ARITH_ACOS = 6, ARITH_ATAN2 = 7, ARITH_SINCOS_VOTED = 8, ARITH_SINCOS_SMALL = 9 };
+// bioik_eval_bounds: the rule of the per-query variable bounds in isolation (stage_op_bounds): a wavefront per row of bounds, lanes stride over the ops;
+// out [n][max(n_ops, 1)][6] = vmin, vmax, span, clip_min, clip_max, unbounded
+struct BoundsArgs {
+    ProbPtr pb;
+    uint64_t n;
+    const double* var_lo;  // [n][V]
+    const double* var_hi;
+    double* out;
+};
+BIOIK_DEV void eval_bounds_body(const BoundsArgs& a, uint64_t q, int lane) {
+    if (q >= a.n) return;
+    const int n_ops = a.pb->n_ops, V = a.pb->V, M = n_ops > 0 ? n_ops : 1;
+    double* out = a.out + q * (uint64_t)M * 6;
+    if (n_ops == 0 && lane < 6) out[lane] = 0.0;
+    for (int k = lane; k < n_ops; k += 64) {
+        const OpBounds b = stage_op_bounds(a.pb, k, a.var_lo + q * (uint64_t)V, a.var_hi + q * (uint64_t)V);
+        double* o = out + k * 6;
+        o[0] = b.vmin, o[1] = b.vmax, o[2] = b.span, o[3] = b.clip_min, o[4] = b.clip_max, o[5] = b.unbounded ? 1.0 : 0.0;
+    }
+}
+
 struct ArithArgs {
     int32_t op, pad;
     uint64_t n;

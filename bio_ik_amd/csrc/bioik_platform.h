@@ -206,6 +206,52 @@ template <>
 struct pb_flavour<LeanProbPtr> {
     static constexpr bool general = false;
 };
+// The third flavour: the general one with PER-QUERY variable bounds (bioik_solve_batch_bounded; k_solve_bounded, k_solve_point_bounded).  The pointer carries, beside
+// the problem block, the query's table of bounds in LDS -- [LIM_N][m] doubles, staged once per query and launch where the clip range is staged for the other
+// flavours (LdsLayout::clip; stage_op_bounds, bioik_device.h).  Everything but the six bound fields of an op is read from the block as before (operator->).
+enum { LIM_CLIP_MIN = 0, LIM_CLIP_MAX = 1, LIM_SPAN = 2, LIM_VMIN = 3, LIM_VMAX = 4, LIM_UNBOUNDED = 5, LIM_N = 6 };
+struct BoundedProbPtr {
+    ProbPtr p;
+    const double* lim;  // LDS: [LIM_N][m]
+    int m;
+    BoundedProbPtr() = default;
+    BIOIK_DEV explicit BoundedProbPtr(ProbPtr q) : p(q), lim(nullptr), m(0) {}
+    BIOIK_DEV ProbPtr operator->() const { return p; }
+    BIOIK_DEV operator ProbPtr() const { return p; }
+};
+template <class PB>
+struct pb_bounded {
+    static constexpr bool value = false;
+};
+template <>
+struct pb_bounded<BoundedProbPtr> {
+    static constexpr bool value = true;
+};
+// THE accessor of an op's variable bounds -- op_limit<LIM_CLIP_MIN | LIM_CLIP_MAX | LIM_SPAN | LIM_VMIN | LIM_VMAX>(pb, k), and op_unbounded(pb, k) for "the variable has
+// no clip" --: every device site reads them through it.  The two flavours that take them from the problem block read exactly the fields they always read, as
+// scalar loads (the same code as the field named in place); the bounded flavour reads its query's table.
+template <int W, class PB>
+BIOIK_DEV double op_limit(PB pb, int k) {
+    static_assert(W >= LIM_CLIP_MIN && W <= LIM_VMAX, "a LIM_* column that is a number");
+    if constexpr (pb_bounded<PB>::value) return pb.lim[W * pb.m + k];
+    else if constexpr (W == LIM_CLIP_MIN) return pb->ops[k].clip_min;
+    else if constexpr (W == LIM_CLIP_MAX) return pb->ops[k].clip_max;
+    else if constexpr (W == LIM_SPAN) return pb->ops[k].span;
+    else if constexpr (W == LIM_VMIN) return pb->ops[k].vmin;
+    else return pb->ops[k].vmax;
+}
+template <class PB>
+BIOIK_DEV bool op_unbounded(PB pb, int k) {
+    if constexpr (pb_bounded<PB>::value) return pb.lim[LIM_UNBOUNDED * pb.m + k] != 0.0;
+    else return pb->ops[k].unbounded;
+}
+// the flavour's pointer with its table attached (the flavours without one: the pointer itself)
+template <class PB>
+BIOIK_DEV PB pb_with_limits(PB pb, const double*, int) { return pb; }
+BIOIK_DEV BoundedProbPtr pb_with_limits(BoundedProbPtr pb, const double* lim, int m) {
+    pb.lim = lim, pb.m = m;
+    return pb;
+}
 
 // Phase profiler (the reference's BLOCKPROFILER taxonomy, src/ik_evolution_2.cpp:330-437,605): compiled in only with
 // -DBIOIK_PHASE_TIMING; lane 0 of the workgroup accumulates shader-clock cycles per phase.

@@ -53,7 +53,7 @@ struct DevOp {
     int32_t val_first;               // FLOATING / PLANAR chain op: first of its 7 / 3 consecutive value ops (type NONE), else -1
     int32_t joint_op;                // value op of a FLOATING / PLANAR joint: the chain op it belongs to, else -1
     int32_t multi_slot;              // FLOATING / PLANAR chain op: the LDS slot its joint frame J(values) is parked in before a walk (multi_joint_prologue); else -1
-    int32_t pad_;
+    int32_t var_revolute;            // 1: `var` is the variable of a revolute joint (RobotInfo drops the clip of a range of a full turn, robot_info.h:82-84; per-query bounds: stage_op_bounds)
 };
 
 struct DevTip {

@@ -31,7 +31,7 @@ class _Settings(C.Structure):  # bioik_plugin_settings (cpp/src/plugin_shim.cpp)
                 ("gpu_reproducible_calls", C.c_int32), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32)),
                 ("dpos", C.c_double), ("drot", C.c_double), ("dtwist", C.c_double), ("rotation_scale", C.c_double),
                 ("center_joints_weight", C.c_double), ("avoid_joint_limits_weight", C.c_double), ("minimal_displacement_weight", C.c_double),
-                ("gpu_island_sync", C.c_int32), ("gpu_island_migration", C.c_int32)]
+                ("gpu_island_sync", C.c_int32), ("gpu_island_migration", C.c_int32), ("gpu_consistency_limits", C.c_int32), ("reserved1", C.c_int32)]
 
 
 class _WireGoal(C.Structure):  # bioik_plugin_goal
@@ -72,12 +72,19 @@ def load_shim(path=None):
     L.bioik_plugin_search_ranked.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, i32, C.c_double, dp, C.POINTER(C.c_uint8),
                                              C.POINTER(i32)]
     L.bioik_plugin_postprocess.argtypes = [vp, u64, dp, dp, u32, C.POINTER(i32)]
+    L.bioik_plugin_submit_limited.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, u64, u32, dp, C.POINTER(u64)]
+    L.bioik_plugin_search_each_limited.argtypes = [vp, u64, dp, dp, dp, dp, u32, C.POINTER(_WireGoal), i32, u32, strs, C.c_double, i32, u64, u32, dp, dp, C.POINTER(C.c_uint8),
+                                                   dp, dp]
     _shims[path] = L
     return L
 
 
 def _strs(names):
     return (C.c_char_p * max(len(names), 1))(*[(n or "").encode() for n in names])
+
+
+class ConsistencyLimitsError(RuntimeError):
+    """consistency limits that are refused before anything is launched: a limit that is negative or no number, a row of the wrong length, an empty window"""
 
 
 class MoveItErrorCodes:
@@ -101,6 +108,7 @@ DEFAULT_PARAMS = {
     "gpu_population": 128, "gpu_fk": "exact", "gpu_islands": 0, "gpu_max_steps": 64, "gpu_devices": None, "gpu_reproducible_calls": False, "gpu_schedule": "auto",
     "gpu_island_sync": True,  # islands stop each other (the reference's island loop); False: every island to its own end
     "gpu_island_migration": 0,  # E > 0: the islands of a pose share their best solution every E steps (bioik_solve_params::island_migration); 0: independent islands
+    "gpu_consistency_limits": False,  # True: the MoveIt-signature searchPositionIK honours its consistency_limits argument; False: ignored, as the reference does
     "gpu_solutions": 8, "gpu_solution_distance": 0.1,  # searchPositionIKRanked: solutions per pose and how far apart (max over the joints, rad / m)
 }
 
@@ -126,7 +134,8 @@ class BioIKKinematicsPlugin:
 
     def _chk(self, rc):
         if rc != 0:
-            raise RuntimeError(self._L.bioik_plugin_last_error().decode())
+            msg = self._L.bioik_plugin_last_error().decode()
+            raise (ConsistencyLimitsError if "consistency" in msg else RuntimeError)(msg)
 
     def _settings(self):
         p = self.params
@@ -138,7 +147,7 @@ class BioIKKinematicsPlugin:
                       dpos=float(p["dpos"]), drot=float(p["drot"]), dtwist=float(p["dtwist"]), rotation_scale=float(p["rotation_scale"]),
                       center_joints_weight=float(p["center_joints_weight"]), avoid_joint_limits_weight=float(p["avoid_joint_limits_weight"]),
                       minimal_displacement_weight=float(p["minimal_displacement_weight"]), gpu_island_sync=int(bool(p["gpu_island_sync"])),
-                      gpu_island_migration=int(p["gpu_island_migration"]))
+                      gpu_island_migration=int(p["gpu_island_migration"]), gpu_consistency_limits=int(bool(p["gpu_consistency_limits"])))
         return s, devices
 
     def _push_params(self):
@@ -195,15 +204,32 @@ class BioIKKinematicsPlugin:
         return True  # kinematics_plugin.cpp:657-662
 
     # ---- the batched entry point and its submit / wait form; the reference's single-query one -------------------------------
-    def searchPositionIKBatchAsync(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0):
+    def searchPositionIKBatchAsync(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0, consistency_limits=None):
         """Marshals and enqueues n independent queries sharing one goal structure, waits for nothing; finish with
         searchPositionIKBatchWait.  ik_poses [n][tips][7] in the base frame (ignored when options.replace), ik_seed_states
         [n][group variables], context_state [variables] (None: the model's default positions, :465-472).  `timeout` [s] bounds the
-        call on the device clock (ik_parallel.h:160; every query still runs one step), <= 0: only gpu_max_steps applies."""
+        call on the device clock (ik_parallel.h:160; every query still runs one step), <= 0: only gpu_max_steps applies.
+        consistency_limits: [n][group variables] or one row [group variables] shared by every query -- how far each group variable may move from its seed
+        (plugin_core.h: Request::consistency_limits: the window is cut to the model's limits and does not cross the seam at +-pi; 0 pins the variable).  Honoured
+        whenever given, whatever the key gpu_consistency_limits says.  Refused with ConsistencyLimitsError before anything is launched: a negative or non-finite
+        limit, a row of the wrong length, a window that comes out empty."""
         a, n, bio, keep = self._marshal(ik_poses, ik_seed_states, options, context_state, timeout)
         ticket = C.c_uint64()
-        self._chk(self._L.bioik_plugin_submit(self._h, *a, C.byref(ticket)))
+        if consistency_limits is None:
+            self._chk(self._L.bioik_plugin_submit(self._h, *a, C.byref(ticket)))
+        else:
+            rows, length, lim = self._limits(consistency_limits)
+            self._chk(self._L.bioik_plugin_submit_limited(self._h, *a, rows, length, abi.dptr(lim), C.byref(ticket)))
         return (ticket.value, n, bio)
+
+    @staticmethod
+    def _limits(consistency_limits):
+        """(rows, entries per row, the numbers) of a consistency_limits argument: one row or one per query; the library checks the counts"""
+        lim = np.ascontiguousarray(np.asarray(consistency_limits, dtype=np.float64))
+        if lim.ndim < 2:
+            lim = lim.reshape(1, -1)
+        lim = np.ascontiguousarray(lim.reshape(lim.shape[0], -1))
+        return lim.shape[0], lim.shape[1], (lim if lim.size else np.zeros(1))
 
     def searchPositionIKRanked(self, ik_poses, ik_seed_states, k=None, min_distance=None, options=None, context_state=None, timeout=0.0):
         """Up to k distinct solutions per pose, best first (MoveIt's multi-solution getPositionIK, batched): the islands of every query ranked on the device
@@ -270,7 +296,7 @@ class BioIKKinematicsPlugin:
             bio.solution_fitness = float(fit[-1])  # :632-634
         return solutions, ok, fit, codes
 
-    def searchPositionIKEach(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0):
+    def searchPositionIKEach(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0, consistency_limits=None):
         """n poses the way MoveIt asks for them: ONE searchPositionIK call per pose, each with `timeout`, the next when the last has returned -- looped inside
         the plugin library (bioik_plugin_search_each), so that the wall time of every call is the plugin core's, not this face's marshalling.
         -> (solutions [n][group variables], ok [n] bool, fitness [n], seconds [n])"""
@@ -305,21 +331,37 @@ class BioIKKinematicsPlugin:
         base = np.ascontiguousarray(base, dtype=np.float64)
         poses = np.zeros(0) if replace else np.ascontiguousarray(np.asarray(ik_poses, dtype=np.float64).reshape(n, len(self.tip_frames), 7))
         solutions, ok, fit, seconds = np.zeros((n, G)), np.zeros(n, dtype=np.uint8), np.zeros(n), np.zeros(n)
+        if consistency_limits is not None:  # (call k gets row k, or the one shared row: searchPositionIKBatchAsync)
+            rows, length, lim = self._limits(consistency_limits)
+            self._chk(self._L.bioik_plugin_search_each_limited(self._h, n, abi.dptr(seeds), abi.dptr(poses) if poses.size else None, abi.dptr(base), abi.dptr(context),
+                                                               len(caller), wire, int(replace), len(fixed), _strs(fixed), float(timeout) if timeout and timeout > 0.0 else 0.0,
+                                                               int(bool(getattr(options, "return_approximate_solution", False))), rows, length, abi.dptr(lim),
+                                                               abi.dptr(solutions), abi.u8ptr(ok), abi.dptr(fit), abi.dptr(seconds)))
+            return solutions, ok != 0, fit, seconds
         self._chk(self._L.bioik_plugin_search_each(self._h, n, abi.dptr(seeds), abi.dptr(poses) if poses.size else None, abi.dptr(base), abi.dptr(context), len(caller), wire,
                                                    int(replace), len(fixed), _strs(fixed), float(timeout) if timeout and timeout > 0.0 else 0.0,
                                                    int(bool(getattr(options, "return_approximate_solution", False))), abi.dptr(solutions), abi.u8ptr(ok), abi.dptr(fit),
                                                    abi.dptr(seconds)))
         return solutions, ok != 0, fit, seconds
 
-    def searchPositionIKBatch(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0):
-        return self.searchPositionIKBatchWait(self.searchPositionIKBatchAsync(ik_poses, ik_seed_states, options, context_state, timeout))
+    def searchPositionIKBatch(self, ik_poses, ik_seed_states, options=None, context_state=None, timeout=0.0, consistency_limits=None):
+        return self.searchPositionIKBatchWait(self.searchPositionIKBatchAsync(ik_poses, ik_seed_states, options, context_state, timeout, consistency_limits))
 
     def searchPositionIK(self, ik_poses, ik_seed_state, timeout, solution, error_code, options=None, consistency_limits=None,
                          solution_callback=None, context_state=None):
         """kinematics_plugin.cpp:437-655.  `timeout` [s] is the reference's wall-clock budget (:504, :574; honoured on the device,
-        at least one step); `gpu_max_steps` bounds the call as well."""
+        at least one step); `gpu_max_steps` bounds the call as well.  consistency_limits [group variables]: ignored unless the key gpu_consistency_limits is set (the
+        reference ignores it); with the key and a non-empty argument every group variable of the answer stays within its limit of the seed, and limits that are
+        refused (searchPositionIKBatchAsync) give NO_IK_SOLUTION."""
         poses = np.asarray(ik_poses, dtype=np.float64).reshape(1, -1, 7) if len(ik_poses) else np.zeros((1, 0, 7))
-        sols, ok, fit, codes = self.searchPositionIKBatch(poses, [ik_seed_state], options, context_state, timeout=timeout)
+        limited = bool(self.params["gpu_consistency_limits"]) and consistency_limits is not None and len(consistency_limits) > 0
+        try:
+            sols, ok, fit, codes = self.searchPositionIKBatch(poses, [ik_seed_state], options, context_state, timeout=timeout,
+                                                              consistency_limits=[list(consistency_limits)] if limited else None)
+        except ConsistencyLimitsError:
+            solution[:] = list(ik_seed_state)
+            error_code.val = MoveItErrorCodes.NO_IK_SOLUTION
+            return False
         solution[:] = list(sols[0])
         if not ok[0]:
             error_code.val = MoveItErrorCodes.NO_IK_SOLUTION

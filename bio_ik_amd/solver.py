@@ -30,6 +30,8 @@ EXPORTS = [
     "bioik_eval_check", "bioik_stream_fitness_device", "bioik_solve_batch_submit", "bioik_solve_batch_wait", "bioik_debug_reload_switches", "bioik_eval_arith",
     "bioik_resolve_islands", "bioik_solve_batch_ranked", "bioik_solve_batch_ranked_device", "bioik_sincos_domain", "bioik_sincos_small_bound",
     "bioik_problem_carry_doubles", "bioik_eval_migrate",
+    "bioik_solve_batch_bounded", "bioik_solve_batch_bounded_submit", "bioik_solve_batch_bounded_device", "bioik_eval_bounds",
+    "bioik_problem_op_count", "bioik_problem_op_variables",
 ]
 
 
@@ -74,6 +76,13 @@ def _declare(L):
     L.bioik_solve_batch_ranked.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, _pd, _pd, _pd, _pd, _pi, _pi, _pi]
     L.bioik_solve_batch_ranked_device.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bioik_solve_batch_bounded.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pi]
+    L.bioik_solve_batch_bounded_submit.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pi, C.POINTER(C.c_uint64)]
+    L.bioik_solve_batch_bounded_device.argtypes = [C.c_void_p, C.POINTER(abi.SolveParams), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bioik_eval_bounds.argtypes = [C.c_void_p, C.c_size_t, _pd, _pd, _pd]
+    L.bioik_problem_op_count.argtypes = [C.c_void_p]
+    L.bioik_problem_op_variables.argtypes = [C.c_void_p, _pi, _pi]
     return L
 
 
@@ -241,12 +250,48 @@ class HipSolver:
         self._chk(self.L.bioik_resolve_islands(self.problem, C.byref(params), int(n), C.byref(isl), C.byref(sync)))
         return isl.value, sync.value
 
+    def _bounds(self, bounds, n):
+        """bounds=(lo, hi), [n][V] each (or one row [V] for every query), as contiguous float64 arrays; an entry None stays None (a null pointer: the library refuses
+        exactly one null)"""
+        lo, hi = bounds
+        out = []
+        for b in (lo, hi):
+            if b is None:
+                out.append(None)
+                continue
+            b = _f64(b)
+            if b.size == self.V and n != 1:
+                b = np.tile(b.reshape(1, self.V), (n, 1))
+            out.append(np.ascontiguousarray(b.reshape(n, self.V)))
+        return out
+
+    def eval_bounds(self, lo, hi):
+        """bioik_eval_bounds: the rule of the per-query variable bounds in isolation: rows lo, hi [n][V] -> [n][max(ops, 1)][6], the columns of abi.BOUNDS_COLUMNS"""
+        lo = _f64(lo).reshape(-1, self.V)
+        hi = _f64(hi).reshape(-1, self.V)
+        n = lo.shape[0]
+        out = np.zeros((n, max(self.n_ops(), 1), 6))
+        self._chk(self.L.bioik_eval_bounds(self.problem, n, _d(lo), _d(hi), _d(out)))
+        return out
+
+    def n_ops(self):
+        """bioik_problem_op_count: ops of the problem's joint program"""
+        return int(self.L.bioik_problem_op_count(self.problem))
+
+    def op_variables(self):
+        """bioik_problem_op_variables: per op its robot variable and its index among the active variables (-1: no gene)"""
+        n = self.n_ops()
+        var, gene = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self.L.bioik_problem_op_variables(self.problem, _i(var), _i(gene)))
+        return var[:n], gene[:n]
+
     def set_first_query(self, first_query):
         self._chk(self.L.bioik_problem_set_first_query(self.problem, int(first_query)))
 
     # ---- the hot path -------------------------------------------------------------------------------------
-    def solve_batch(self, params, seeds, goal_params):
-        """n independent queries: seeds [n][V], goal_params [n][P] -> (solutions [n][V], fitness, success, steps)."""
+    def solve_batch(self, params, seeds, goal_params, bounds=None):
+        """n independent queries: seeds [n][V], goal_params [n][P] -> (solutions [n][V], fitness, success, steps).
+        bounds=(lo, hi): per-query variable bounds, [n][V] each (bioik_solve_batch_bounded; include/bioik_hip.h: the rule)."""
         sync_debug_switches(self.L)
         s = _f64(seeds).reshape(-1, self.V)
         n = s.shape[0]
@@ -255,6 +300,11 @@ class HipSolver:
         fit = np.zeros(n)
         suc = np.zeros(n, dtype=np.int32)
         steps = np.zeros(n, dtype=np.int32)
+        if bounds is not None:
+            lo, hi = self._bounds(bounds, n)
+            self._chk(self.L.bioik_solve_batch_bounded(self.problem, C.byref(params), n, _d(s), _d(gp), _d(lo) if lo is not None else None, _d(hi) if hi is not None else None,
+                                                       _d(sol), _d(fit), _i(suc), _i(steps)))
+            return sol, fit, suc, steps
         self._chk(self.L.bioik_solve_batch(self.problem, C.byref(params), n, _d(s), _d(gp), _d(sol), _d(fit), _i(suc), _i(steps)))
         return sol, fit, suc, steps
 
@@ -281,7 +331,7 @@ class HipSolver:
         self._chk(self.L.bioik_solve_batch_ranked_device(self.problem, C.byref(params), int(n), int(k), float(min_distance), d_seeds, d_goal_params, d_solutions,
                                                          d_fitness, d_success, d_steps, d_count, stream))
 
-    def submit_batch(self, params, seeds, goal_params):
+    def submit_batch(self, params, seeds, goal_params, bounds=None):
         """bioik_solve_batch_submit: the same solve without waiting.  Returns a ticket object; `wait_batch(ticket)` returns what solve_batch
         returns.  Up to six batches of this handle are in flight together (the library rotates over six internal streams)."""
         sync_debug_switches(self.L)
@@ -290,6 +340,11 @@ class HipSolver:
         gp = self._gp(goal_params, n)
         out = (np.zeros((n, self.V)), np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32))
         t = C.c_uint64(0)
+        if bounds is not None:
+            lo, hi = self._bounds(bounds, n)
+            self._chk(self.L.bioik_solve_batch_bounded_submit(self.problem, C.byref(params), n, _d(s), _d(gp), _d(lo) if lo is not None else None,
+                                                              _d(hi) if hi is not None else None, _d(out[0]), _d(out[1]), _i(out[2]), _i(out[3]), C.byref(t)))
+            return (t.value, out, (s, gp, lo, hi))
         self._chk(self.L.bioik_solve_batch_submit(self.problem, C.byref(params), n, _d(s), _d(gp), _d(out[0]), _d(out[1]), _i(out[2]), _i(out[3]), C.byref(t)))
         return (t.value, out, (s, gp))  # (the arrays stay alive with the ticket)
 
@@ -312,9 +367,14 @@ class HipSolver:
         self._chk(self.L.bioik_solve_batch_multi(handles, 1 + len(others), C.byref(params), n, _d(s), _d(gp), _d(sol), _d(fit), _i(suc), _i(steps)))
         return sol, fit, suc, steps
 
-    def solve_batch_device(self, params, n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, stream=0):
-        """All arguments are device pointers (ints) of arrays resident in HBM; enqueues on `stream`, does not synchronise."""
+    def solve_batch_device(self, params, n, d_seeds, d_goal_params, d_solutions, d_fitness, d_success, d_steps, stream=0, bounds=None):
+        """All arguments are device pointers (ints) of arrays resident in HBM; enqueues on `stream`, does not synchronise.
+        bounds=(d_lo, d_hi): device pointers of the per-query variable bounds, [n][V] each; they must stay valid and unchanged until the call's kernels have run."""
         sync_debug_switches(self.L)
+        if bounds is not None:
+            self._chk(self.L.bioik_solve_batch_bounded_device(self.problem, C.byref(params), int(n), d_seeds, d_goal_params, bounds[0], bounds[1], d_solutions, d_fitness,
+                                                              d_success, d_steps, stream))
+            return
         self._chk(self.L.bioik_solve_batch_device(self.problem, C.byref(params), int(n), d_seeds, d_goal_params, d_solutions, d_fitness,
                                                   d_success, d_steps, stream))
 

@@ -34,7 +34,10 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_params::island_migration in the slot of `reserved0` (0, what every caller of 6 wrote there, is off),
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_batch_bounded, bioik_solve_batch_bounded_submit, bioik_solve_batch_bounded_device, bioik_eval_bounds,
+                               bioik_problem_op_count, bioik_problem_op_variables
+                               (per-query variable bounds).
+                               6, additions that break no caller of 6: bioik_solve_params::island_migration in the slot of `reserved0` (0, what every caller of 6 wrote there, is off),
                                BIOIK_MAX_MIGRATIONS, bioik_eval_migrate, bioik_problem_carry_doubles (the islands of a query share their best every E steps).
                                6, additions that break no caller of 6: bioik_solve_batch_ranked, bioik_solve_batch_ranked_device (the k best distinct islands of every query).
                                6 (round 6): bioik_resolve_islands (the island count BIOIK_ISLANDS_AUTO gives a call of n queries, for callers that shard a request themselves);
@@ -137,7 +140,8 @@ enum {
  *   are read, sixteen queries per CU: a third more steps per ms on a full chip, but a step takes 2.5 x as long, so the stragglers of a batch run for
  *   up to 12 ms.  It pays with six to ten batches in flight on as many streams -- and hardware queues: the HIP runtime maps streams onto four unless
  *   GPU_MAX_HW_QUEUES says otherwise -- and costs an isolated call about a fifth more time.  Problems the denser mapping does not exist for (secondary
- *   goals with more than 256 children, 32 or more genes, floating joints) run as under LATENCY.
+ *   goals with more than 256 children, 32 or more genes, floating joints) run as under LATENCY.  So does a call with per-query variable bounds
+ *   (bioik_solve_batch_bounded): the dense mapping's kernel has no build that reads them.
  * AUTO: LATENCY, except in bioik_solve_batch_submit when two or more solves of the handle are already in flight: THROUGHPUT then (a caller
  *   that streams batches through the asynchronous entry gets the dense mapping once its pipeline is three deep; an isolated call stays as fast as it
  *   can be). */
@@ -410,6 +414,41 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds,
                              const double* d_goal_params, double* d_solutions, double* d_fitness,
                              int32_t* d_success, int32_t* d_steps, void* hip_stream);
+
+/* PER-QUERY VARIABLE BOUNDS: the solves above with two more arrays, var_lo and var_hi, [n][V] doubles each, indexed by robot variable (MoveIt: the
+ * consistency_limits of KinematicsBase::searchPositionIK, trajectory continuity, sampling inside joint-space boxes, pinning a joint for some queries only).
+ * THE RULE.  For query q and robot variable v that is an ACTIVE variable of the problem (bioik_problem_active_variables):
+ *   - lo = var_lo[q][v] and hi = var_hi[q][v] both finite and lo <= hi: the query is solved AS IF THE MODEL HAD BEEN CREATED WITH var_min[v] = lo, var_max[v] = hi,
+ *     var_bounded[v] = 1 -- with everything the library derives from those three: a revolute variable with hi - lo >= 2 pi 0.9999 loses its clip (and counts as
+ *     unbounded for AvoidJointLimitsGoal / CenterJointsGoal); clip_min / clip_max; span = hi - lo, 1 where that is not in [0, FLT_MAX); the limits the limit goals
+ *     and the random re-founding of a species (and the random configurations of gd_r / the gradient family's islands) read.
+ *   - otherwise (a NaN, an infinity, lo > hi): the variable keeps the model's own bounds for that query.  This is how a caller bounds only some variables.
+ * Entries of variables that are no active variables of the problem are not read.  All islands of a query share its row.  Nothing else about the solve changes:
+ * the same random streams, bioik_problem_set_first_query keying, timeout, island_sync, island_migration; every mode and both fk_modes.
+ * THE SOLVER DOES NOT CLIP THE SEED: a query whose seed lies outside its bounds may return that seed (the reference's solvers on a model narrowed that way do);
+ * a query whose seed lies inside its bounds returns a solution inside them, success or not.
+ * Both arrays NULL: the call IS the plain call (bioik_solve_batch / _submit / _device: the same launches, kernels and bits).  Exactly one NULL:
+ * BIOIK_ERR_INVALID_ARGUMENT, nothing launched, outputs untouched.  A bounded call runs the general kernel's build that reads a query's bounds from a table in
+ * LDS (k_solve_bounded; k_solve_point_bounded for gd / jac): 32 m bytes of LDS per workgroup more (m ops); a problem that no longer fits a CU's LDS with it is
+ * refused with BIOIK_ERR_UNSUPPORTED before any launch.  Under BIOIK_SCHEDULE_THROUGHPUT it runs as under LATENCY.  It neither takes nor changes the handle's
+ * measured mapping choice.  bioik_solve_batch_bounded_submit is completed by bioik_solve_batch_wait.  The device form is capturable under the contract of
+ * bioik_solve_batch_device (a linear chain, no memset node, one eager call of the same plan first); its two arrays are read by every launch of the call and must
+ * stay valid and unchanged until the call's last kernel has run.  Not provided: bounds for the ranked entries and for bioik_solve_batch_multi. */
+int bioik_solve_batch_bounded(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params,
+                              const double* var_lo /*[n][V]*/, const double* var_hi /*[n][V]*/, double* solutions, double* fitness, int32_t* success, int32_t* steps);
+int bioik_solve_batch_bounded_submit(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* seeds, const double* goal_params,
+                                     const double* var_lo, const double* var_hi, double* solutions, double* fitness, int32_t* success, int32_t* steps,
+                                     uint64_t* ticket);
+int bioik_solve_batch_bounded_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds, const double* d_goal_params,
+                                     const double* d_var_lo, const double* d_var_hi, double* d_solutions, double* d_fitness, int32_t* d_success,
+                                     int32_t* d_steps, void* hip_stream);
+/* The rule above in isolation (the device function the bounded kernels stage a query's table with, and nothing else): for n rows of bounds the six numbers of
+ * every op of the problem's joint program, out [n][max(ops, 1)][6] = vmin, vmax, span, clip_min, clip_max, unbounded (0 / 1).  Host pointers. */
+int bioik_eval_bounds(bioik_problem* p, size_t n, const double* var_lo, const double* var_hi, double* out);
+/* the ops of the problem's joint program (the rows of bioik_eval_bounds): their number, and per op its robot variable and its index among the active variables
+ * (-1: the op is no gene -- a mimic joint, a joint outside the group: its bounds are never changed) */
+int bioik_problem_op_count(const bioik_problem* p);
+int bioik_problem_op_variables(const bioik_problem* p, int32_t* variable /*[ops]*/, int32_t* gene /*[ops]*/);
 
 /* RANKED SOLVES: the k best DISTINCT solutions of every query instead of the best one (MoveIt: the KinematicsBase::getPositionIK overload that fills a
  * std::vector<std::vector<double>>).  A query's islands are independent searches; each ends with a complete result, and where bioik_solve_batch keeps the
