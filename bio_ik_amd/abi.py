@@ -23,6 +23,7 @@ JOINT_VAR_COUNT = {JOINT_FIXED: 0, JOINT_REVOLUTE: 1, JOINT_PRISMATIC: 1, JOINT_
  GOAL_AVOID_JOINT_LIMITS, GOAL_CENTER_JOINTS, GOAL_REGULARIZATION, GOAL_MINIMAL_DISPLACEMENT, GOAL_JOINT_VARIABLE,
  GOAL_SIDE, GOAL_DIRECTION, GOAL_CONE, GOAL_BALANCE, GOAL_TOUCH) = range(18)
 MAX_TOUCH_POINTS = 1024  # BIOIK_MAX_TOUCH_POINTS: collision points one TouchGoal may read
+MAX_HELD_FRAMES = 4  # BIOIK_MAX_HELD_FRAMES: distinct links whose frame the based goals of a problem need held across a walk
 GOAL_PARAM_COUNT = {GOAL_POSITION: 3, GOAL_ORIENTATION: 4, GOAL_POSE: 8, GOAL_LOOK_AT: 6, GOAL_MAX_DISTANCE: 4,
                     GOAL_MIN_DISTANCE: 4, GOAL_LINE: 6, GOAL_PLANE: 6, GOAL_AVOID_JOINT_LIMITS: 0, GOAL_CENTER_JOINTS: 0,
                     GOAL_REGULARIZATION: 0, GOAL_MINIMAL_DISPLACEMENT: 0, GOAL_JOINT_VARIABLE: 1, GOAL_SIDE: 6,
@@ -58,7 +59,8 @@ class GoalDesc(C.Structure):
 class ProblemDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_group_joints", C.c_uint32), ("group_joints", _pi),
                 ("n_goals", C.c_uint32), ("n_fixed_joints", C.c_uint32), ("goals", C.POINTER(GoalDesc)),
-                ("fixed_joints", _pi)]
+                ("fixed_joints", _pi),
+                ("goal_base_link", _pi)]  # BASE LINKS: [n_goals] link index, -1 = world; NULL: no goal has one
 
 
 class SolveParams(C.Structure):

@@ -119,4 +119,11 @@ struct Frame {  // reference include/bio_ik/frame.h:51-91
     }
 };
 
+// reference include/bio_ik/frame.h:189-209: the formulas as they stand, nothing normalised
+inline Frame inverse(const Frame& f) {
+    const Quaternion qi = f.rot.inverse();
+    return Frame(quatRotate(qi, Vector3(-f.pos.x(), -f.pos.y(), -f.pos.z())), qi);
+}
+inline Frame concat(const Frame& a, const Frame& b) { return Frame(a.pos + quatRotate(a.rot, b.pos), a.rot * b.rot); }
+
 }  // namespace bio_ik

@@ -113,6 +113,7 @@ public:
     virtual int gpuOpcode() const { return -1; }
     virtual std::string gpuLinkName() const { return std::string(); }
     virtual std::string gpuVariableName() const { return std::string(); }
+    virtual std::string gpuBaseLinkName() const { return std::string(); }  // BASE LINKS (include/bioik_hip.h): bioik_problem_desc::goal_base_link, "" = the world
     virtual void gpuParams(std::vector<double>&) const {}
 };
 

@@ -11,17 +11,30 @@ namespace bio_ik {
 
 class LinkGoalBase : public Goal {  // goal_types.h:56-78
     std::string link_name_;
+    std::string base_link_name_;  // BASE LINKS (include/bioik_hip.h; no reference counterpart): "" = the world
 
 public:
     LinkGoalBase() { weight_ = 1; }
     LinkGoalBase(const std::string& link_name, double weight) : link_name_(link_name) { weight_ = weight; }
     void setLinkName(const std::string& n) { link_name_ = n; }
     const std::string& getLinkName() const { return link_name_; }
+    // A built-in link goal with a base link is evaluated on its link's frame expressed in the base link's, R = concat(inverse(base), link): what a
+    // reference user writes as a Goal subclass with two addLink calls and a relative transform in evaluate()
+    void setBaseLinkName(const std::string& n) { base_link_name_ = n; }
+    const std::string& getBaseLinkName() const { return base_link_name_; }
     void describe(GoalContext& context) const override {
         Goal::describe(context);
         context.addLink(link_name_);
+        if (!base_link_name_.empty()) context.addLink(base_link_name_);  // behind the goal's own link: getLinkFrame(1)
     }
     std::string gpuLinkName() const override { return link_name_; }
+    std::string gpuBaseLinkName() const override { return base_link_name_; }
+
+protected:
+    // the frame the built-in goals read: the link's, or R for a goal with a base link (the device's formula, bioik_device.h: based_frame)
+    Frame goalFrame(const GoalContext& context) const {
+        return base_link_name_.empty() ? context.getLinkFrame() : concat(inverse(context.getLinkFrame(1)), context.getLinkFrame(0));
+    }
 };
 
 class PositionGoal : public LinkGoalBase {  // :80-97
@@ -32,7 +45,7 @@ public:
     PositionGoal(const std::string& link_name, const Vector3& position, double weight = 1.0) : LinkGoalBase(link_name, weight), position_(position) {}
     const Vector3& getPosition() const { return position_; }
     void setPosition(const Vector3& p) { position_ = p; }
-    double evaluate(const GoalContext& context) const override { return context.getLinkFrame().getPosition().distance2(getPosition()); }
+    double evaluate(const GoalContext& context) const override { return goalFrame(context).getPosition().distance2(getPosition()); }
     int gpuOpcode() const override { return BIOIK_GOAL_POSITION; }
     void gpuParams(std::vector<double>& o) const override { o.insert(o.end(), {position_.x(), position_.y(), position_.z()}); }
 };
@@ -49,7 +62,7 @@ public:
         : LinkGoalBase(link_name, weight), orientation_(orientation.normalized()) {}
     const Quaternion& getOrientation() const { return orientation_; }
     void setOrientation(const Quaternion& q) { orientation_ = q.normalized(); }
-    double evaluate(const GoalContext& context) const override { return quaternionDistance2(getOrientation(), context.getLinkFrame().getOrientation()); }
+    double evaluate(const GoalContext& context) const override { return quaternionDistance2(getOrientation(), goalFrame(context).getOrientation()); }
     int gpuOpcode() const override { return BIOIK_GOAL_ORIENTATION; }
     void gpuParams(std::vector<double>& o) const override { o.insert(o.end(), {orientation_.x(), orientation_.y(), orientation_.z(), orientation_.w()}); }
 };
@@ -70,7 +83,7 @@ public:
     double getRotationScale() const { return rotation_scale_; }
     void setRotationScale(double s) { rotation_scale_ = s; }
     double evaluate(const GoalContext& context) const override {
-        const Frame& f = context.getLinkFrame();
+        const Frame f = goalFrame(context);
         return f.getPosition().distance2(getPosition()) + quaternionDistance2(getOrientation(), f.getOrientation()) * (rotation_scale_ * rotation_scale_);
     }
     int gpuOpcode() const override { return BIOIK_GOAL_POSE; }
@@ -91,7 +104,7 @@ public:
     void setAxis(const Vector3& a) { axis_ = a.normalized(); }
     void setTarget(const Vector3& t) { target_ = t; }
     double evaluate(const GoalContext& context) const override {
-        const Frame& f = context.getLinkFrame();
+        const Frame f = goalFrame(context);
         const Vector3 axis = quatRotate(f.getOrientation(), axis_);
         return (target_ - f.getPosition()).normalized().distance2(axis.normalized());
     }
@@ -113,7 +126,7 @@ public:
     double getDistance() const { return distance; }
     void setDistance(double d) { distance = d; }
     double evaluate(const GoalContext& context) const override {
-        const double d = std::fmax(0.0, context.getLinkFrame().getPosition().distance(target) - distance);
+        const double d = std::fmax(0.0, goalFrame(context).getPosition().distance(target) - distance);
         return d * d;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_MAX_DISTANCE; }
@@ -124,7 +137,7 @@ class MinDistanceGoal : public MaxDistanceGoal {  // :243-270
 public:
     using MaxDistanceGoal::MaxDistanceGoal;
     double evaluate(const GoalContext& context) const override {
-        const double d = std::fmax(0.0, distance - context.getLinkFrame().getPosition().distance(target));
+        const double d = std::fmax(0.0, distance - goalFrame(context).getPosition().distance(target));
         return d * d;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_MIN_DISTANCE; }
@@ -142,7 +155,7 @@ public:
     const Vector3& getDirection() const { return direction; }
     void setDirection(const Vector3& d) { direction = d.normalized(); }
     double evaluate(const GoalContext& context) const override {
-        const Vector3& p = context.getLinkFrame().getPosition();
+        const Vector3 p = goalFrame(context).getPosition();
         return position.distance2(p - direction * direction.dot(p - position));
     }
     int gpuOpcode() const override { return BIOIK_GOAL_LINE; }
@@ -161,7 +174,7 @@ public:
     const Vector3& getNormal() const { return normal; }
     void setNormal(const Vector3& n) { normal = n.normalized(); }
     double evaluate(const GoalContext& context) const override {
-        const double d = (context.getLinkFrame().getPosition() - position).dot(normal);
+        const double d = (goalFrame(context).getPosition() - position).dot(normal);
         return d * d;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_PLANE; }
@@ -327,7 +340,7 @@ public:
     void setAxis(const Vector3& a) { axis = a.normalized(); }
     void setDirection(const Vector3& d) { direction = d.normalized(); }
     double evaluate(const GoalContext& context) const override {
-        const double f = std::fmax(0.0, quatRotate(context.getLinkFrame().getOrientation(), axis).dot(direction));
+        const double f = std::fmax(0.0, quatRotate(goalFrame(context).getOrientation(), axis).dot(direction));
         return f * f;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_SIDE; }
@@ -336,7 +349,7 @@ public:
 class DirectionGoal : public SideGoal {  // :616-644
 public:
     using SideGoal::SideGoal;
-    double evaluate(const GoalContext& context) const override { return quatRotate(context.getLinkFrame().getOrientation(), axis).distance2(direction); }
+    double evaluate(const GoalContext& context) const override { return quatRotate(goalFrame(context).getOrientation(), axis).distance2(direction); }
     int gpuOpcode() const override { return BIOIK_GOAL_DIRECTION; }
 };
 
@@ -364,7 +377,7 @@ public:
     void setDirection(const Vector3& d) { direction = d.normalized(); }
     void setAngle(double a) { angle = a; }
     double evaluate(const GoalContext& context) const override {
-        const Frame& f = context.getLinkFrame();
+        const Frame f = goalFrame(context);
         const Vector3 v = quatRotate(f.getOrientation(), axis);
         const double c = v.dot(direction) / std::sqrt(v.length2() * direction.length2());
         const double d = std::fmax(0.0, std::acos(std::fmin(1.0, std::fmax(-1.0, c))) - angle);

@@ -178,7 +178,7 @@ class Engine {
     std::shared_ptr<ProblemSet> problemFor(const std::vector<const Goal*>& goals, const std::vector<std::string>& fixed) {
         std::ostringstream key;
         key << std::hexfloat;  // exact weight bits: goals whose weights differ in any digit get their own compiled problem
-        for (auto* g : goals) key << g->gpuOpcode() << ':' << g->gpuLinkName() << ':' << g->gpuVariableName() << ':' << g->getWeight() << ':' << g->isSecondary() << ';';
+        for (auto* g : goals) key << g->gpuOpcode() << ':' << g->gpuLinkName() << ':' << g->gpuBaseLinkName() << ':' << g->gpuVariableName() << ':' << g->getWeight() << ':' << g->isSecondary() << ';';
         for (auto& f : fixed) key << '#' << f;
         const std::string k = key.str();
         for (auto it = cache_.begin(); it != cache_.end(); ++it)
@@ -187,6 +187,8 @@ class Engine {
                 return cache_.back().second;
             }
         std::vector<bioik_goal_desc> gd;
+        std::vector<int32_t> base_idx;  // bioik_problem_desc::goal_base_link (BASE LINKS): -1 = the world
+        bool any_base = false;
         for (auto* g : goals) {
             if (g->gpuOpcode() < 0) throw std::logic_error("bio_ik (MI355X): a goal without a device implementation reached the problem compiler");  // (submit() splits them off)
             bioik_goal_desc d{g->gpuOpcode(), -1, -1, g->isSecondary() ? 1 : 0, g->getWeight()};
@@ -199,6 +201,12 @@ class Engine {
                 if (d.variable < 0) throw std::runtime_error("joint variable not found: " + g->gpuVariableName());  // problem.cpp:125
             }
             gd.push_back(d);
+            base_idx.push_back(-1);
+            if (!g->gpuBaseLinkName().empty()) {
+                base_idx.back() = mv_.link_index(g->gpuBaseLinkName());
+                if (base_idx.back() < 0) throw std::runtime_error("link not found: " + g->gpuBaseLinkName());
+                any_base = true;
+            }
         }
         std::vector<int32_t> fixed_idx;
         for (auto& f : fixed) {
@@ -211,6 +219,7 @@ class Engine {
         pd.n_group_joints = (uint32_t)mv_.group_joints.size(), pd.group_joints = mv_.group_joints.data();
         pd.n_goals = (uint32_t)gd.size(), pd.goals = gd.data();
         pd.n_fixed_joints = (uint32_t)fixed_idx.size(), pd.fixed_joints = fixed_idx.data();
+        pd.goal_base_link = any_base ? base_idx.data() : nullptr;
         auto set = std::make_shared<ProblemSet>();
         for (auto* m : models_) {
             bioik_problem* p = nullptr;

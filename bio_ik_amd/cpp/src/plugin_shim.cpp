@@ -17,12 +17,13 @@ namespace {
 
 struct WireGoal : bio_ik::Goal {  // a goal of the Python package, already serialised
     int opcode = -1;
-    std::string link, variable;
+    std::string link, variable, base_link;
     std::vector<double> numbers;
     void setSecondary(bool s) { secondary_ = s; }
     int gpuOpcode() const override { return opcode; }
     std::string gpuLinkName() const override { return link; }
     std::string gpuVariableName() const override { return variable; }
+    std::string gpuBaseLinkName() const override { return base_link; }
     void gpuParams(std::vector<double>& out) const override { out.insert(out.end(), numbers.begin(), numbers.end()); }
 };
 
@@ -71,6 +72,7 @@ typedef struct bioik_plugin_goal {
     const char* variable;  // NULL / "": none
     double weight;
     const double* numbers;  // [n_numbers] the goal's per-query numbers (the same for every query of the batch)
+    const char* base_link;  // NULL / "": the world (BASE LINKS, include/bioik_hip.h)
 } bioik_plugin_goal;
 
 struct bioik_plugin {
@@ -247,6 +249,7 @@ static void buildRequest(bioik_plugin* p, InFlight& f, bio_ik::core::Request& rq
             g->opcode = goals[i].opcode;
             if (goals[i].link) g->link = goals[i].link;
             if (goals[i].variable) g->variable = goals[i].variable;
+            if (goals[i].base_link) g->base_link = goals[i].base_link;
             g->setWeight(goals[i].weight);
             g->numbers.assign(goals[i].numbers, goals[i].numbers + goals[i].n_numbers);
             g->setSecondary(goals[i].secondary != 0);

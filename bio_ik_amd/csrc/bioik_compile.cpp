@@ -181,8 +181,15 @@ HostModel::HostModel(const bioik_model_desc& d) {
     }
 }
 
+bool problem_desc_has_base_links(const bioik_problem_desc& d) {
+    // (the descriptor grew by goal_base_link without a new ABI version: a caller built against the header without it passes the shorter size and gets no base link)
+    const bool has_base = d.struct_size == sizeof(bioik_problem_desc);
+    if (!has_base && d.struct_size != offsetof(bioik_problem_desc, goal_base_link)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_desc: struct_size mismatch");
+    return has_base;
+}
+
 HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : model(m) {
-    if (d.struct_size != sizeof(bioik_problem_desc)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_desc: struct_size mismatch");
+    const int32_t* goal_base_link = problem_desc_has_base_links(d) ? d.goal_base_link : nullptr;
     const int nl = (int)m->links.size(), nv = (int)m->vars.size();
     std::memset(&dev, 0, sizeof(dev));
     dev.multi_op = -1;
@@ -224,6 +231,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         double weight;
         int secondary, param_off;
         int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them
+        int base_tip;                              // a based goal (bioik_problem_desc::goal_base_link): the public tip of its base link, else -1
     };
     std::vector<G> goals;
     double balance_total = 0.0;
@@ -232,10 +240,20 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         const bioik_goal_desc& g = d.goals[gi];
         int np = goal_param_count(g.type);
         if (np < 0) throw Error(BIOIK_ERR_UNSUPPORTED, "goal type has no device implementation");
-        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0, 0};
+        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0, 0, -1};
         if (g.link >= 0) {
             if (g.link >= nl) throw Error(BIOIK_ERR_NOT_FOUND, "link not found");
             info.tip = add_tip_link(g.link);
+        }
+        if (goal_base_link && goal_base_link[gi] >= 0) {  // BASE LINKS (include/bioik_hip.h): the goal reads its link's frame in the base link's
+            const int base = goal_base_link[gi];
+            const std::string who = "goal " + std::to_string(gi) + ": ";
+            if (base >= nl) throw Error(BIOIK_ERR_NOT_FOUND, who + "base link not found");
+            if (g.link < 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + "a base link on a goal that names no link");
+            if (base == g.link) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + "the base link is the goal's own link");
+            if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, who + "a base link on a secondary goal (secondary link goals read the null frame: a relative one would be a constant)");
+            if (g.type == BIOIK_GOAL_TOUCH || g.type == BIOIK_GOAL_BALANCE) throw Error(BIOIK_ERR_UNSUPPORTED, who + "a base link on a TouchGoal or a BalanceGoal has no device implementation");
+            info.base_tip = add_tip_link(base);  // behind the goal's own link, as a describe() with two addLink calls
         }
         if (g.variable >= 0) {
             if (g.variable >= nv) throw Error(BIOIK_ERR_NOT_FOUND, "joint variable not found");
@@ -557,6 +575,25 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             op.tip_count++;
         }
     }
+    // BASE LINKS: a based goal reads two tips and the walks keep no table of tip frames, so the goal sits at whichever of the two the walk completes LATER
+    // (the device tip order) and the earlier one parks its frame in an LDS slot of the lane (DevTip::pad0 = slot + 1), like a branch's parent frame
+    auto attach_tip = [&](const G& g) { return g.base_tip >= 0 ? std::max(dev.tip_of_out[g.tip], dev.tip_of_out[g.base_tip]) : dev.tip_of_out[g.tip]; };
+    int n_held = 0;
+    for (size_t gi = 0; gi < goals.size(); gi++) {
+        const G& g = goals[gi];
+        if (g.base_tip < 0) continue;
+        DevTip& held = dev.tips[std::min(dev.tip_of_out[g.tip], dev.tip_of_out[g.base_tip])];
+        if (held.pad0 != 0) continue;
+        if (n_held >= BIOIK_MAX_HELD_FRAMES)
+            throw Error(BIOIK_ERR_UNSUPPORTED, "goal " + std::to_string(gi) + ": more than BIOIK_MAX_HELD_FRAMES (" + std::to_string(BIOIK_MAX_HELD_FRAMES) +
+                                                   ") distinct links whose frame the based goals need held across the walk");
+        n_held++;
+        held.pad0 = 1 + n_slots++;
+    }
+    // (the later tip parks its frame too: the goal's cost is one out-of-line call that reads both frames from the lane's slots, so that no frame crosses the
+    // call in registers -- as arguments, 28 of them, they cost k_solve spilled registers on every problem, with or without a base link)
+    for (const G& g : goals)
+        if (g.base_tip >= 0 && dev.tips[attach_tip(g)].pad0 == 0) dev.tips[attach_tip(g)].pad0 = 1 + n_slots++;
     // goals: primary link goals grouped by device tip, then gene-only primary goals; secondary goals in order
     auto to_dev = [&](const G& g) {
         DevGoal o;
@@ -570,6 +607,11 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             else o.var_seed = (int)(-1 - g.var);
         }
         if (g.type == BIOIK_GOAL_TOUCH) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
+        if (g.base_tip >= 0 && g.tip >= 0) {  // var_op <= -2 marks a based goal (a link goal reads no variable): -2 - (held tip * 2 + "the held frame is the goal's own link's")
+            const int own = dev.tip_of_out[g.tip], base = dev.tip_of_out[g.base_tip];
+            o.tip = std::max(own, base);
+            o.var_op = -2 - (std::min(own, base) * 2 + (own < base ? 1 : 0));
+        }
         o.param_off = g.param_off;
         return o;
     };
@@ -577,12 +619,12 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
     for (int t = 0; t < T; t++) {
         dev.tips[t].goal_first = np;
         for (const G& g : goals)
-            if (!g.secondary && g.tip >= 0 && dev.tip_of_out[g.tip] == t) {
+            if (!g.secondary && g.tip >= 0 && attach_tip(g) == t) {
                 if (np >= BIOIK_MAX_GOALS) throw Error(BIOIK_ERR_UNSUPPORTED, "too many goals");
                 dev.primary[np++] = to_dev(g);
             }
         dev.tips[t].goal_count = np - dev.tips[t].goal_first;
-        const bool one_pose = dev.tips[t].goal_count == 1 && dev.primary[dev.tips[t].goal_first].type == BIOIK_GOAL_POSE;
+        const bool one_pose = dev.tips[t].goal_count == 1 && dev.primary[dev.tips[t].goal_first].type == BIOIK_GOAL_POSE && dev.primary[dev.tips[t].goal_first].var_op >= -1;
         dev.tips[t].pose_off = one_pose ? dev.primary[dev.tips[t].goal_first].param_off : -1;
         dev.tips[t].pose_weight_sq = one_pose ? dev.primary[dev.tips[t].goal_first].weight_sq : 0.0;
     }
@@ -614,7 +656,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
     dev.n_primary = np;
     dev.n_secondary = ns;
     dev.pose_only = (T == 1 && np == 1 && ns == 0 && dev.n_balance == 0 && dev.n_link_primary == 1 && dev.primary[0].type == BIOIK_GOAL_POSE &&
-                     dev.primary[0].tip == 0) ? 1 : 0;
+                     dev.primary[0].tip == 0 && dev.primary[0].var_op >= -1) ? 1 : 0;
     dev.pose_param_off = dev.pose_only ? dev.primary[0].param_off : 0;
     dev.pose_weight_sq = dev.pose_only ? dev.primary[0].weight_sq : 0.0;
     dev.n_ops = (int)ops.size();
@@ -636,6 +678,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
     dev.serial_chain = n_chain > 0 ? 1 : 0;
     for (int k = 0; k < n_chain; k++)
         if (ops[k].src != k - 1 || ops[k].load_slot >= 0 || ops[k].save_slot >= 0 || ops[k].mimic_src >= 0 || ops[k].type >= BIOIK_OP_FLOATING) dev.serial_chain = 0;
+    if (n_held > 0) dev.serial_chain = 0;  // (a held tip frame is a parked frame)
     dev.tips_last = dev.serial_chain && dev.n_root_tips == 0 ? 1 : 0;
     for (int k = 0; k + 1 < n_chain; k++)
         if (ops[k].tip_count != 0) dev.tips_last = 0;

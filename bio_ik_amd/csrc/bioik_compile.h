@@ -55,6 +55,9 @@ struct HostProblem {
 };
 
 int goal_param_count(int type);
+// the struct_size rule of bioik_problem_desc (include/bioik_hip.h), in one place: true if the caller's descriptor reaches goal_base_link, false if it ends in front of
+// it; any other size throws BIOIK_ERR_INVALID_ARGUMENT
+bool problem_desc_has_base_links(const bioik_problem_desc& d);
 DevSolveParams normalize_params(const bioik_solve_params& p, uint64_t first_query, size_t n_queries = 0, size_t resident_units = 2048);  // resident_units: the (query, island) workgroups of the latency schedule's kernel the device holds at once (eight per CU)  // (n_queries: what BIOIK_ISLANDS_AUTO sizes the islands to; 0: one island)
 
 }  // namespace bioik

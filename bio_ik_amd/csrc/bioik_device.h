@@ -581,13 +581,21 @@ BIOIK_CALL double goal_eval_joint_set(ProbPtr pb, int type, int var_op, int var_
     return goal_eval_joint_set_inl(pb, type, var_op, var_seed, p0, xp, xs, seed);
 }
 // PoseGoal::evaluate (goal_types.h:149-180); P: position, orientation, rotation scale
-BIOIK_DEV double pose_goal_cost(const double* P, const F7& fb) {
+template <class PP>
+BIOIK_DEV double pose_goal_cost(const PP* P, const F7& fb) {
     double e = dist2(fb.p, v3(P[0], P[1], P[2]));
     const Q4 d = Q4{P[3] - fb.q.x, P[4] - fb.q.y, P[5] - fb.q.z, P[6] - fb.q.w};
     const Q4 a = Q4{P[3] + fb.q.x, P[4] + fb.q.y, P[5] + fb.q.z, P[6] + fb.q.w};
     double rs = P[7];
     e += fmin(qdot(d, d), qdot(a, a)) * (rs * rs);
     return e;
+}
+// OrientationGoal::evaluate (goal_types.h:115-124); P: orientation
+template <class PP>
+BIOIK_DEV double orientation_goal_cost(const PP* P, const F7& fb) {
+    const Q4 d = Q4{P[0] - fb.q.x, P[1] - fb.q.y, P[2] - fb.q.z, P[3] - fb.q.w};
+    const Q4 a = Q4{P[0] + fb.q.x, P[1] + fb.q.y, P[2] + fb.q.z, P[3] + fb.q.w};
+    return fmin(qdot(d, d), qdot(a, a));
 }
 // JS_INLINE: the goals over the joint values are inlined (the one hot site: secondary fitness of every child in the pre-selection)
 template <bool JS_INLINE = false, class XA = XV, class PB = ProbPtr>
@@ -596,11 +604,8 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
     switch (type) {
         case G_POSITION:  // goal_types.h:96
             return dist2(fb.p, v3(P[0], P[1], P[2]));
-        case G_ORIENTATION: {  // :115-124
-            const Q4 d = Q4{P[0] - fb.q.x, P[1] - fb.q.y, P[2] - fb.q.z, P[3] - fb.q.w};
-            const Q4 a = Q4{P[0] + fb.q.x, P[1] + fb.q.y, P[2] + fb.q.z, P[3] + fb.q.w};
-            return fmin(qdot(d, d), qdot(a, a));
-        }
+        case G_ORIENTATION:
+            return orientation_goal_cost(P, fb);
         case G_POSE:
             return pose_goal_cost(P, fb);
         case G_AVOID_JOINT_LIMITS:
@@ -625,20 +630,101 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
     return 0.0;
 }
 
+// frame.h:189-209
+BIOIK_DEV F7 f7_invert(const F7& a) {
+    const Q4 qi = qinv(a.q);
+    return F7{qrot(qi, v3(-a.p.x, -a.p.y, -a.p.z)), qi};
+}
+// BASE LINKS (include/bioik_hip.h): a goal row with var_op <= -2 is evaluated on R = inv(A) o B, A the frame of its base link and B that of its own link, in place
+// of the tip's world frame.  The row sits at whichever of the two tips a walk completes later (f, the frame at hand); the earlier tip's frame is HELD: parked in
+// a slot of the lane's parked frames (DevTip::pad0 = slot + 1) when the walk completes it, or, where a site has a table of every tip's frame (the linearised
+// phenotypes), read from there.  var_op = -2 - (held tip * 2 + "the held frame is B").  The formula as it stands: nothing is normalised.
+// General flavour only (a problem with such a goal never reaches a lean kernel).
+template <class PP>
+BIOIK_DEV F7 slot_load(const PP* s, int nth) {  // a frame of the lane's parked-frame slots: seven values, nth apart
+    return F7{{s[0], s[(size_t)nth], s[(size_t)2 * nth]}, {s[(size_t)3 * nth], s[(size_t)4 * nth], s[(size_t)5 * nth], s[(size_t)6 * nth]}};
+}
+// One out-of-line copy each of the frame and of a based goal's cost (frames as values, the goal's numbers by their LDS pointer, as goal_eval_link_rare takes them):
+// a site pays a branch, the seven reads of the held frame and the call, and the kernels of problems without a base link next to nothing.
+BIOIK_DEV int based_held_tip(int var_op) { return (-2 - var_op) >> 1; }
+BIOIK_DEV F7 based_frame_inl(int var_op, const F7& f, const F7& held) {
+    const bool held_is_own = ((-2 - var_op) & 1) != 0;
+    const F7 a = held_is_own ? f : held, b = held_is_own ? held : f;
+    return f7_concat(f7_invert(a), b);
+}
+BIOIK_CALL F7 based_frame(int var_op, F7 f, F7 held) { return based_frame_inl(var_op, f, held); }
+BIOIK_DEV double based_goal_cost_inl(int type, int var_op, const lds_f64* P, const F7& f, const F7& held) {
+    const F7 r = based_frame_inl(var_op, f, held);
+    if (type == G_POSITION) return dist2(r.p, v3(P[0], P[1], P[2]));  // (goal_eval's cases for the three frame goals, by the functions it calls)
+    if (type == G_ORIENTATION) return orientation_goal_cost(P, r);
+    if (type == G_POSE) return pose_goal_cost(P, r);
+    return goal_eval_link_rare(type, P, r);
+}
+// (the held frame as values: the sites that read it from a table of tip frames; as the lane's slot: the exact walks)
+BIOIK_CALL double based_goal_cost(int type, int var_op, const lds_f64* P, F7 f, F7 held) { return based_goal_cost_inl(type, var_op, P, f, held); }
+BIOIK_CALL double based_goal_cost_slots(int type, int var_op, const lds_f64* P, const lds_f64* own, const lds_f64* slot, int nth) {
+    return based_goal_cost_inl(type, var_op, P, slot_load(own, nth), slot_load(slot, nth));
+}
+BIOIK_DEV void slot_store(double* sl, int nth, const F7& f) {
+    sl[0] = f.p.x, sl[(size_t)nth] = f.p.y, sl[(size_t)2 * nth] = f.p.z;
+    sl[(size_t)3 * nth] = f.q.x, sl[(size_t)4 * nth] = f.q.y, sl[(size_t)5 * nth] = f.q.z, sl[(size_t)6 * nth] = f.q.w;
+}
+// a walk's tip section: the tip's frame goes to its slot if a based goal of a later tip reads it
+template <class PB>
+BIOIK_DEV void hold_tip(PB pb, int t, const F7& f, double* slots_of_child) {
+    if constexpr (pb_flavour<PB>::general) {
+        const int hs = pb->tips[t].pad0;
+        if (hs > 0) slot_store(slots_of_child + (size_t)(hs - 1) * 7 * p_nthreads() + p_tid_fresh(), p_nthreads(), f);
+    }
+}
+// ... and the held frame of tip `ht` as an exact walk of this lane left it
+template <class PB>
+struct HeldSlots {
+    PB pb;
+    const double* slots_of_child;
+    BIOIK_DEV const double* slot(int ht) const { return slots_of_child + (size_t)(pb->tips[ht].pad0 - 1) * 7 * p_nthreads() + p_tid_fresh(); }
+    BIOIK_DEV F7 operator()(int ht) const { return slot_load(slot(ht), p_nthreads()); }
+    // t: the tip the goal sits at (the walk has parked its frame too, bioik_compile.cpp)
+    BIOIK_DEV double cost(int type, int var_op, const double* P, int t) const {
+        return based_goal_cost_slots(type, var_op, (const lds_f64*)P, (const lds_f64*)slot(t), (const lds_f64*)slot(based_held_tip(var_op)), p_nthreads());
+    }
+};
+template <class Held, class = void>
+struct held_in_slots : std::false_type {};
+template <class PB>
+struct held_in_slots<HeldSlots<PB>> : std::true_type {};
+template <class Held>
+BIOIK_DEV double based_cost(const Held& held, int type, int var_op, const double* P, const F7& f, int t) {
+    if constexpr (held_in_slots<Held>::value) return held.cost(type, var_op, P, t);
+    else return based_goal_cost(type, var_op, (const lds_f64*)P, f, held(based_held_tip(var_op)));
+}
+struct HeldNone {  // the sites that evaluate goals without a link (null frames): no row there is based
+    BIOIK_DEV F7 operator()(int) const { return F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}; }
+};
+
 // Σ weight² · e over the primary link goals of one tip (problem.cpp:244-257, grouped by tip)
 // (sum: the fitness so far.  The reference adds goal after goal to ONE running sum (problem.cpp:244-257); a tip's goals continue the caller's sum instead of
 // forming one of their own, so that (s + a) + b is what is computed, not s + (a + b) -- the same for every evaluation path of the device, and the reference's
 // bits wherever the goals are listed in the order the walk completes their tips, gene-only goals behind them)
-template <class XA, class PB>
-BIOIK_DEV double tip_goals(PB pb, int t, const F7& f, const XA& x, const QueryCtx& qc, double sum) {
+// held(tip): the frame of an earlier tip that a based goal of this one reads (above)
+template <class XA, class PB, class Held>
+BIOIK_DEV double tip_goals(PB pb, int t, const F7& f, const XA& x, const QueryCtx& qc, double sum, const Held& held) {
 #if !defined(BIOIK_NO_POSE_ONLY)
     // the usual tip: one PoseGoal (DevTip::pose_off): the sum below without the goal table's dependent scalar loads
     if (pb->tips[t].pose_off >= 0) return sum + pose_goal_cost(qc.par + pb->tips[t].pose_off, f) * pb->tips[t].pose_weight_sq;
 #endif
     const int g0 = pb->tips[t].goal_first, g1 = g0 + pb->tips[t].goal_count;
-    for (int g = g0; g < g1; g++)
+    for (int g = g0; g < g1; g++) {
+        if constexpr (pb_flavour<PB>::general) {
+            const int vo = pb->primary[g].var_op;
+            if (vo < -1) {
+                sum += based_cost(held, pb->primary[g].type, vo, qc.par + pb->primary[g].param_off, f, t) * pb->primary[g].weight_sq;
+                continue;
+            }
+        }
         sum += goal_eval<false, XA>(pb, pb->primary[g].type, pb->primary[g].var_op, pb->primary[g].var_seed, qc.par + pb->primary[g].param_off, f, x, qc, pb->primary[g].pad) *
                pb->primary[g].weight_sq;
+    }
     return sum;
 }
 // primary goals that read no link
@@ -731,11 +817,6 @@ BIOIK_DEV void secondary_fitness_n(PB pb, const XA (&x)[N], const QueryCtx& qc, 
 //   tip_fn(t, frame): called with device tip index t as soon as the tip's frame is complete
 // The loop trip count and every constant are wave-uniform: control flow is scalar, constants arrive in SGPRs.
 // ---------------------------------------------------------------------------------------------------------
-// frame.h:189-209
-BIOIK_DEV F7 f7_invert(const F7& a) {
-    const Q4 qi = qinv(a.q);
-    return F7{qrot(qi, v3(-a.p.x, -a.p.y, -a.p.z)), qi};
-}
 // Floating / planar joints (RobotJointEvaluator::getJointFrame, forward_kinematics.h:120-135): the joint's 7 / 3 values travel
 // as an F7 (floating: translation, quaternion; planar: x, y, theta in p), and the arithmetic -- normalisation of the quaternion
 // (sqrt, four divisions) or sincos, two frame concatenations -- is ONE out-of-line value function: these joints are rare, and
@@ -817,8 +898,11 @@ BIOIK_DEV void fk_walk(PB pb, const XA& x, double* slots, double* frames_out, Ti
         if (pb->tips[t].has_e) {
             double e[7];
             for (int c = 0; c < 7; c++) e[c] = pb->tips[t].e[c];
-            tip_fn(t, f7_load(e));
+            const F7 o = f7_load(e);
+            hold_tip(pb, t, o, slots);
+            tip_fn(t, o);
         } else {
+            hold_tip(pb, t, f, slots);
             tip_fn(t, f);
         }
     }
@@ -885,8 +969,11 @@ BIOIK_DEV void fk_walk(PB pb, const XA& x, double* slots, double* frames_out, Ti
             if (pb->tips[t].has_e) {
                 double e[7];
                 for (int c2 = 0; c2 < 7; c2++) e[c2] = pb->tips[t].e[c2];
-                tip_fn(t, f7_concat(f, f7_load(e)));
+                const F7 o = f7_concat(f, f7_load(e));
+                hold_tip(pb, t, o, slots);
+                tip_fn(t, o);
             } else {
+                hold_tip(pb, t, f, slots);
                 tip_fn(t, f);
             }
         }
@@ -920,7 +1007,7 @@ BIOIK_DEV double eval_exact_primary(PB pb, const XA& x, const QueryCtx& qc, doub
     double sum = 0.0;
     V3 bal = v3(0.0, 0.0, 0.0);
     fk_walk(pb, x, slots, nullptr, [&](int t, const F7& f) {
-        sum = tip_goals(pb, t, f, x, qc, sum);
+        sum = tip_goals(pb, t, f, x, qc, sum, HeldSlots<PB>{pb, slots});
         balance_tip(pb, t, f, bal);
     }, prefix);
     sum = nonlink_primary(pb, x, qc, sum);
@@ -1012,6 +1099,8 @@ BIOIK_DEV void fk_walk_n(PB pb, const XA (&x)[N], double* slots, int slot_set_st
 #pragma unroll
             for (int j = 0; j < N; j++) o[j] = f[j];
         }
+        if constexpr (pb_flavour<PB>::general && !SERIAL)
+            for (int j = 0; j < N; j++) hold_tip(pb, t, o[j], slots + (size_t)j * slot_set_stride);
         tip_fn(t, o);
     }
     int k_begin = 0;
@@ -1130,6 +1219,8 @@ BIOIK_DEV void fk_walk_n(PB pb, const XA (&x)[N], double* slots, int slot_set_st
 #pragma unroll
                 for (int j = 0; j < N; j++) o[j] = f[j];
             }
+            if constexpr (pb_flavour<PB>::general)
+                for (int j = 0; j < N; j++) hold_tip(pb, t, o[j], slots + (size_t)j * slot_set_stride);
             tip_fn(t, o);
         }
     }
@@ -1156,6 +1247,14 @@ BIOIK_DEV void eval_exact_primary_n(PB pb, const XA (&x)[N], const QueryCtx& qc,
             const int po = p_fresh(pb->primary[g].param_off);
             const double w = pb->primary[g].weight_sq;
             const double* P = qc.par + po;
+            if constexpr (pb_flavour<PB>::general && !SERIAL) {
+                if (var_op < -1) {  // a based goal: R from the frame this child's walk has held (BASE LINKS)
+#pragma unroll
+                    for (int j = 0; j < N; j++)
+                        out[j] += HeldSlots<PB>{pb, slots + (size_t)j * slot_set_stride}.cost(type, var_op, P, t) * w;
+                    continue;
+                }
+            }
 #pragma unroll
             for (int j = 0; j < N; j++) out[j] += goal_eval<false, XA>(pb, type, var_op, var_seed, P, f[j], x[j], qc, pb->primary[g].pad) * w;
         }
@@ -1224,7 +1323,7 @@ BIOIK_DEV double eval_linear_primary(PB pb, const XA& x, const QueryCtx& qc, con
     V3 bal = v3(0.0, 0.0, 0.0);
     for (int t = 0; t < T; t++) {
         const F7 f = linear_tip(pb, t, x, lm);
-        sum = tip_goals(pb, t, f, x, qc, sum);
+        sum = tip_goals(pb, t, f, x, qc, sum, [&](int ht) { return linear_tip(pb, ht, x, lm); });
         balance_tip(pb, t, f, bal);
     }
     sum = nonlink_primary(pb, x, qc, sum);
@@ -1729,11 +1828,23 @@ BIOIK_CALL int check_frame_goal(int type, const lds_f64* P, F7 fb, double dpos, 
     return ok ? 1 : 0;
 }
 
-template <class PB>
-BIOIK_DEV bool check_goal(PB pb, int g, const F7& fb, const XV& x, const QueryCtx& qc, double dpos, double drot, double dtwist) {
+template <class PB, class Held>
+BIOIK_DEV bool check_goal(PB pb, int g, const F7& f_tip, const XV& x, const QueryCtx& qc, double dpos, double drot, double dtwist, const Held& held) {
     const int type = pb->primary[g].type;
     const double* P = qc.par + pb->primary[g].param_off;
     bool ok = true;
+    F7 fb = f_tip;
+    if constexpr (pb_flavour<PB>::general) {  // BASE LINKS: the success test reads R where the cost does
+        const int vo = pb->primary[g].var_op;
+        if (vo < -1) {
+            if (type != G_POSITION && type != G_ORIENTATION && type != G_POSE) {
+                const double dmax = fmin(BIOIK_DBL_MAX, fmin(p_fresh(dpos), dtwist));
+                const double d = based_cost(held, type, vo, P, f_tip, pb->primary[g].tip) * pb->primary[g].weight_sq;
+                return d < dmax * dmax;
+            }
+            fb = based_frame(vo, f_tip, held(based_held_tip(vo)));
+        }
+    }
     if (type == G_POSITION || type == G_ORIENTATION || type == G_POSE) {
         ok = check_frame_goal(type, (const lds_f64*)P, fb, dpos, drot, dtwist) != 0;
     } else {
@@ -1761,7 +1872,7 @@ BIOIK_NOINLINE FitCheck exact_fitness_check(PB pb, XV x, QueryCtx qc, double* sl
     double sum = 0.0;
     V3 bal = v3(0.0, 0.0, 0.0);
     fk_walk<COOP>(pb, x, slots, nullptr, [&](int t, const F7& f) {
-        sum = tip_goals(pb, t, f, x, qc, sum);
+        sum = tip_goals(pb, t, f, x, qc, sum, HeldSlots<PB>{pb, slots});
         balance_tip(pb, t, f, bal);
 #if !defined(BIOIK_NO_POSE_ONLY)
         if (do_check && pb->tips[t].pose_off >= 0) {
@@ -1770,14 +1881,14 @@ BIOIK_NOINLINE FitCheck exact_fitness_check(PB pb, XV x, QueryCtx qc, double* sl
 #endif
         if (do_check) {
             const int g0 = pb->tips[t].goal_first, g1 = g0 + pb->tips[t].goal_count;
-            for (int g = g0; g < g1; g++) good = check_goal(pb, g, f, x, qc, dpos, drot, dtwist) && good;
+            for (int g = g0; g < g1; g++) good = check_goal(pb, g, f, x, qc, dpos, drot, dtwist, HeldSlots<PB>{pb, slots}) && good;
         }
     }, prefix);
     sum = nonlink_primary(pb, x, qc, sum);
     sum += balance_cost(pb, bal, qc);
     if (do_check) {
         const F7 zero = F7{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-        for (int g = pb->n_link_primary; g < pb->n_primary; g++) good = check_goal(pb, g, zero, x, qc, dpos, drot, dtwist) && good;
+        for (int g = pb->n_link_primary; g < pb->n_primary; g++) good = check_goal(pb, g, zero, x, qc, dpos, drot, dtwist, HeldNone{}) && good;
         if constexpr (pb_flavour<PB>::general) {  // a goal type the success test does not know: weighted cost < min(dpos, dtwist)^2 (problem.cpp:327-334)
             const double dmax = fmin(BIOIK_DBL_MAX, fmin(dpos, dtwist));
             for (int g = 0; g < pb->n_balance; g++) good = (balance_goal_cost(pb, g, bal, qc) < dmax * dmax) && good;

@@ -627,8 +627,16 @@ static size_t eval_lds(const bioik_problem* p, size_t bytes) {
     return bytes;
 }
 
-// a problem a lean kernel can run (bioik_platform.h, pb_flavour): no floating / planar joints, ops that meet the genes in gene order, no BalanceGoal, no TouchGoal
-static bool lean_capable(const DevProblem& d) { return d.multi_op < 0 && d.n_quat == 0 && d.genes_follow_ops != 0 && d.n_balance == 0 && d.touch_points == nullptr; }
+// a problem a lean kernel can run (bioik_platform.h, pb_flavour): no floating / planar joints, ops that meet the genes in gene order, no BalanceGoal, no TouchGoal, no based goal
+// a problem with a based goal (BASE LINKS, include/bioik_hip.h): some tip holds its frame for a later one
+static bool has_based_goal(const DevProblem& d) {
+    for (int t = 0; t < d.T; t++)
+        if (d.tips[t].pad0 != 0) return true;
+    return false;
+}
+static bool lean_capable(const DevProblem& d) {
+    return d.multi_op < 0 && d.n_quat == 0 && d.genes_follow_ops != 0 && d.n_balance == 0 && d.touch_points == nullptr && !has_based_goal(d);
+}
 
 // the timeout of a solve on the device clock (bioik_problem: clock_*)
 static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t stream, SolveArgs& a) {
@@ -1116,6 +1124,8 @@ struct SolveLauncher {
 
 static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t stream, const SolveSwitches& sw, unsigned int* error_word,
                          const RankedArgs* ranked = nullptr) {
+    if (sp_in.solver == 2 && has_based_goal(p->host.dev))
+        throw Error(BIOIK_ERR_UNSUPPORTED, "BIOIK_MODE_JAC on a problem with a based goal (bioik_problem_desc::goal_base_link): its tip objectives are world poses; gd, gd_r and gd_c work");
     if (arrays.n == 0) return;
     SolveLauncher s(p, sp_in, arrays, stream, sw, error_word);
     s.ranked = ranked;
@@ -1299,7 +1309,7 @@ int bioik_problem_create(bioik_model* model, const bioik_problem_desc* desc, bio
     API_BEGIN
     if (!model || !desc || !out) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (desc->struct_size != sizeof(bioik_problem_desc)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_desc: struct_size mismatch");
+    bioik::problem_desc_has_base_links(*desc);  // (throws on a struct_size that is none of the descriptor's: before any field beyond it is read)
     if ((desc->n_goals && !desc->goals) || (desc->n_group_joints && !desc->group_joints) || (desc->n_fixed_joints && !desc->fixed_joints))
         throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_desc: a count is non-zero but its array is null");
     std::unique_ptr<bioik_problem> p(new bioik_problem(model, *desc));

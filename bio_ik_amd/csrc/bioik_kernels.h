@@ -1949,7 +1949,7 @@ BIOIK_DEV void solve_memetic(Frame& F, SpeciesState& S, double*& popS, int rank_
 #endif
                 double acc = 0.0;
                 V3 bal = v3(0.0, 0.0, 0.0);
-                for (int t = 0; t < T; t++) {
+                auto tip_frame = [&](int t) -> F7 {
                     F7 f = frame_of(fc, t);
                     if (dstep != 0.0) {
                         double d[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1960,7 +1960,11 @@ BIOIK_DEV void solve_memetic(Frame& F, SpeciesState& S, double*& popS, int rank_
                         f = F7{{BK_FMA(d[0], dstep, f.p.x), BK_FMA(d[1], dstep, f.p.y), BK_FMA(d[2], dstep, f.p.z)},
                                {BK_FMA(d[3], dstep, f.q.x), BK_FMA(d[4], dstep, f.q.y), BK_FMA(d[5], dstep, f.q.z), BK_FMA(d[6], dstep, f.q.w)}};
                     }
-                    acc = tip_goals(pb, t, f, x, qc, acc);
+                    return f;
+                };
+                for (int t = 0; t < T; t++) {
+                    const F7 f = tip_frame(t);
+                    acc = tip_goals(pb, t, f, x, qc, acc, tip_frame);  // (a based goal reads its held tip's frame from the same table: BASE LINKS, bioik_device.h)
                     balance_tip(pb, t, f, bal);
                 }
                 acc = nonlink_primary(pb, x, qc, acc);

@@ -54,10 +54,11 @@ class Goal:
 class LinkGoalBase(Goal):
     """goal_types.h:56-78"""
 
-    def __init__(self, link_name="", weight=1.0):
+    def __init__(self, link_name="", weight=1.0, base_link=""):
         super().__init__()
         self.weight_ = float(weight)
         self.link_name_ = link_name
+        self.base_link_name_ = base_link
 
     def setLinkName(self, n):
         self.link_name_ = n
@@ -68,12 +69,23 @@ class LinkGoalBase(Goal):
     def link_name(self):
         return self.link_name_
 
+    # BASE LINKS (include/bioik_hip.h; no reference counterpart): the goal is evaluated on the link's frame expressed in the base link's frame,
+    # R = inverse(base) o link; "" (the default) is the world.  ProblemTemplate marshals it into bioik_problem_desc::goal_base_link.
+    def setBaseLinkName(self, n):
+        self.base_link_name_ = n
+
+    def getBaseLinkName(self):
+        return self.base_link_name_
+
+    def base_link_name(self):
+        return self.base_link_name_ or None
+
 
 class PositionGoal(LinkGoalBase):
     opcode = abi.GOAL_POSITION
 
-    def __init__(self, link_name="", position=(0, 0, 0), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", position=(0, 0, 0), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.position_ = _vec3(position)
 
     def getPosition(self):
@@ -89,8 +101,8 @@ class PositionGoal(LinkGoalBase):
 class OrientationGoal(LinkGoalBase):
     opcode = abi.GOAL_ORIENTATION
 
-    def __init__(self, link_name="", orientation=(0, 0, 0, 1), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", orientation=(0, 0, 0, 1), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.orientation_ = _normalized(orientation)  # goal_types.h:110
 
     def getOrientation(self):
@@ -106,8 +118,8 @@ class OrientationGoal(LinkGoalBase):
 class PoseGoal(LinkGoalBase):
     opcode = abi.GOAL_POSE
 
-    def __init__(self, link_name="", position=(0, 0, 0), orientation=(0, 0, 0, 1), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", position=(0, 0, 0), orientation=(0, 0, 0, 1), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.position_ = _vec3(position)
         self.orientation_ = _normalized(orientation)  # goal_types.h:139
         self.rotation_scale_ = 0.5                    # goal_types.h:133,140
@@ -137,8 +149,8 @@ class PoseGoal(LinkGoalBase):
 class LookAtGoal(LinkGoalBase):
     opcode = abi.GOAL_LOOK_AT
 
-    def __init__(self, link_name="", axis=(1, 0, 0), target=(0, 0, 0), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", axis=(1, 0, 0), target=(0, 0, 0), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.axis_ = _vec3(axis)  # constructor does not normalise (goal_types.h:194-199); the setter does (:202)
         self.target_ = _vec3(target)
 
@@ -159,8 +171,8 @@ class LookAtGoal(LinkGoalBase):
 
 
 class _DistanceGoal(LinkGoalBase):
-    def __init__(self, link_name="", target=(0, 0, 0), distance=1.0, weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", target=(0, 0, 0), distance=1.0, weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.target = _vec3(target)
         self.distance = float(distance)
 
@@ -191,8 +203,8 @@ class MinDistanceGoal(_DistanceGoal):
 class LineGoal(LinkGoalBase):
     opcode = abi.GOAL_LINE
 
-    def __init__(self, link_name="", position=(0, 0, 0), direction=(1, 0, 0), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", position=(0, 0, 0), direction=(1, 0, 0), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.position = _vec3(position)
         self.direction = _normalized(direction)  # goal_types.h:286
 
@@ -215,8 +227,8 @@ class LineGoal(LinkGoalBase):
 class PlaneGoal(LinkGoalBase):
     opcode = abi.GOAL_PLANE
 
-    def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.position = _vec3(position)
         self.normal = _normalized(normal)  # goal_types.h:314
 
@@ -241,8 +253,8 @@ class TouchGoal(LinkGoalBase):
     link's collision points and disks of the robot model (RobotModel.add_collision_box / _sphere / _points / _cylinder / _cone, or the URDF reader): no FCL."""
     opcode = abi.GOAL_TOUCH
 
-    def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", position=(0, 0, 0), normal=(0, 0, 1), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.position = _vec3(position)
         self.normal = _normalized(normal)  # goal_types.h:371
 
@@ -327,8 +339,8 @@ class JointVariableGoal(Goal):
 
 
 class _AxisDirectionGoal(LinkGoalBase):
-    def __init__(self, link_name="", axis=(0, 0, 1), direction=(0, 0, 1), weight=1.0):
-        super().__init__(link_name, weight)
+    def __init__(self, link_name="", axis=(0, 0, 1), direction=(0, 0, 1), weight=1.0, base_link=""):
+        super().__init__(link_name, weight, base_link)
         self.axis = _vec3(axis)  # constructors do not normalise (goal_types.h:596-601, 627-632); setters do
         self.direction = _vec3(direction)
 
@@ -360,8 +372,8 @@ class ConeGoal(LinkGoalBase):
     opcode = abi.GOAL_CONE
 
     def __init__(self, link_name="", axis=(0, 0, 1), direction=(0, 0, 1), angle=0.0, weight=1.0, position=None,
-                 position_weight=None):
-        super().__init__(link_name, weight)
+                 position_weight=None, base_link=""):
+        super().__init__(link_name, weight, base_link)
         # three reference constructors, goal_types.h:673-699
         self.position = _vec3(position if position is not None else (0, 0, 0))
         self.position_weight = float(position_weight if position_weight is not None else (1.0 if position is not None else 0.0))

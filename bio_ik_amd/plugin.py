@@ -36,7 +36,8 @@ class _Settings(C.Structure):  # bioik_plugin_settings (cpp/src/plugin_shim.cpp)
 
 class _WireGoal(C.Structure):  # bioik_plugin_goal
     _fields_ = [("opcode", C.c_int32), ("secondary", C.c_int32), ("n_numbers", C.c_int32), ("reserved", C.c_int32),
-                ("link", C.c_char_p), ("variable", C.c_char_p), ("weight", C.c_double), ("numbers", C.POINTER(C.c_double))]
+                ("link", C.c_char_p), ("variable", C.c_char_p), ("weight", C.c_double), ("numbers", C.POINTER(C.c_double)),
+                ("base_link", C.c_char_p)]  # BASE LINKS (include/bioik_hip.h): "" = the world
 
 
 _shims = {}
@@ -270,6 +271,7 @@ class BioIKKinematicsPlugin:
             w.opcode, w.secondary, w.n_numbers, w.weight = g.opcode, int(g.isSecondary()), len(numbers), g.getWeight()
             w.link = (g.link_name() or "").encode()
             w.variable = (g.variable_name() or "").encode()
+            w.base_link = ((g.base_link_name() if hasattr(g, "base_link_name") else None) or "").encode()
             w.numbers = abi.dptr(numbers)
         if context_state is None:
             context, base = m.default_positions(), self._base_default
@@ -322,6 +324,7 @@ class BioIKKinematicsPlugin:
             w.opcode, w.secondary, w.n_numbers, w.weight = g.opcode, int(g.isSecondary()), len(numbers), g.getWeight()
             w.link = (g.link_name() or "").encode()
             w.variable = (g.variable_name() or "").encode()
+            w.base_link = ((g.base_link_name() if hasattr(g, "base_link_name") else None) or "").encode()
             w.numbers = abi.dptr(numbers)
         if context_state is None:
             context, base = m.default_positions(), self._base_default

@@ -20,6 +20,7 @@ class ProblemTemplate:
         self.fixed_joints = list(fixed_joints)
         n = len(self.goals)
         self._goal_descs = (abi.GoalDesc * max(n, 1))()
+        self._goal_base_link = np.full(max(n, 1), -1, dtype=np.int32)  # BASE LINKS (include/bioik_hip.h): bioik_problem_desc::goal_base_link
         self.param_offsets = []
         off = 0
         for i, g in enumerate(self.goals):
@@ -33,6 +34,8 @@ class ProblemTemplate:
             d.variable = model.variable_index(vn) if vn is not None else -1
             d.secondary = 1 if g.isSecondary() else 0
             d.weight = g.getWeight()
+            bn = g.base_link_name() if hasattr(g, "base_link_name") else None
+            self._goal_base_link[i] = model.link_index(bn) if bn is not None else -1
             self.param_offsets.append(off)
             off += abi.GOAL_PARAM_COUNT[g.opcode]
         self.param_count = off
@@ -48,6 +51,7 @@ class ProblemTemplate:
         d.n_fixed_joints = len(self._fixed)
         d.goals = C.cast(self._goal_descs, C.POINTER(abi.GoalDesc))
         d.fixed_joints = abi.iptr(self._fixed) if len(self._fixed) else None
+        d.goal_base_link = abi.iptr(self._goal_base_link) if (self._goal_base_link >= 0).any() else None
         return d
 
     def pack_params(self, goals=None):

@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_solve_batch_bounded, bioik_solve_batch_bounded_submit, bioik_solve_batch_bounded_device, bioik_eval_bounds,
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_problem_desc::goal_base_link behind the fields every caller of 6 fills (a shorter struct_size gets none),
+                               BIOIK_MAX_HELD_FRAMES (BASE LINKS: a link goal evaluated in another link's frame).
+                               6, additions that break no caller of 6: bioik_solve_batch_bounded, bioik_solve_batch_bounded_submit, bioik_solve_batch_bounded_device, bioik_eval_bounds,
                                bioik_problem_op_count, bioik_problem_op_variables
                                (per-query variable bounds).
                                6, additions that break no caller of 6: bioik_solve_params::island_migration in the slot of `reserved0` (0, what every caller of 6 wrote there, is off),
@@ -215,6 +217,23 @@ typedef struct bioik_goal_desc {
     double weight;     /* Goal::getWeight()                                                */
 } bioik_goal_desc;
 
+/* BASE LINKS (no reference counterpart: there such a goal is a LinkFunctionGoal or a Goal subclass with two addLink calls).  A link goal -- POSITION, ORIENTATION,
+ * POSE, LOOK_AT, MAX_DISTANCE, MIN_DISTANCE, LINE, PLANE, SIDE, DIRECTION, CONE -- may name a BASE LINK in bioik_problem_desc::goal_base_link.  With A the base
+ * link's frame and B the goal link's frame of the same individual, the goal is evaluated on
+ *     R = concat(invert(A), B):   R.q = conj(A.q) (x) B.q,   R.p = rotate(conj(A.q), -A.p) + rotate(conj(A.q), B.p)        (reference frame.h:189-209)
+ * in place of the link's world frame -- the formula as it stands, nothing normalised, also for the unnormalised quaternions of BIOIK_FK_LINEAR phenotypes -- in
+ * both places a link goal reads a frame: its cost (the parameters keep their meaning, read in the base link's frame) and the success test (Position / Orientation /
+ * Pose: the dpos / drot / dtwist test on R; the others: weighted cost < min(dpos, dtwist)^2, problem.cpp:327-334).  Base -1 is the world: everything as without the field.
+ * The base link becomes a tip link of the problem and the joints of its chain active variables, as any link a goal names (problem.cpp:125, 191-204).
+ * A walk keeps no table of tip frames: a based goal is attached to whichever of its two links the walk completes LATER, the earlier one's frame is held until then;
+ * at most BIOIK_MAX_HELD_FRAMES DISTINCT links of a problem can be held (the number of based goals is limited only by the goal tables).  Such a problem runs in the
+ * general kernel flavour (k_solve / k_solve_bounded / k_solve_point*), 56 bytes of LDS per lane more for every held link and for every link a based goal sits at.
+ * Refused by bioik_problem_create: base >= n_links BIOIK_ERR_NOT_FOUND; a base on a goal without a link, or equal to the goal's own link: BIOIK_ERR_INVALID_ARGUMENT;
+ * a base on a secondary goal (secondary link goals read the null frame, ik_base.h:163: it would be a constant), on BIOIK_GOAL_TOUCH or BIOIK_GOAL_BALANCE, or more
+ * than BIOIK_MAX_HELD_FRAMES distinct held links: BIOIK_ERR_UNSUPPORTED.  Refused by every solve entry: BIOIK_MODE_JAC on a problem with a based goal,
+ * BIOIK_ERR_UNSUPPORTED (its tip objectives are world poses, ik_gradient.cpp:64-66; gd, gd_r, gd_c minimise the fitness and work). */
+#define BIOIK_MAX_HELD_FRAMES 4
+
 /* ---- problem template = the arguments of Problem::initialize (reference src/problem.cpp:72-228)
  *      that do not change from query to query. -------------------------------------------------- */
 typedef struct bioik_problem_desc {
@@ -225,6 +244,9 @@ typedef struct bioik_problem_desc {
     uint32_t n_fixed_joints;
     const bioik_goal_desc* goals;
     const int32_t* fixed_joints; /* link indices of BioIKKinematicsQueryOptions::fixed_joints (goal.h:124) */
+    /* BASE LINKS (above).  A caller whose struct_size ends in front of this field (a build against the header without it) gets none; a size that ends inside it
+       is BIOIK_ERR_INVALID_ARGUMENT. */
+    const int32_t* goal_base_link; /* [n_goals] link index, -1 = world; NULL: no goal has one */
 } bioik_problem_desc;
 
 /* ---- solver parameters = IKParams (reference src/utils.h:64-85) restricted to bio2*, plus the
