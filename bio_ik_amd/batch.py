@@ -133,6 +133,29 @@ def _gather(s, dev, group):
     return None
 
 
+def _share_obstacles(solver, dev, group):
+    """Every rank's handle gets rank 0's obstacle tables (ClearanceGoals: data beside the template, changed on a live handle by HipSolver.set_obstacles): the shards
+    are parts of one solve.  One broadcast per ClearanceGoal of the template; a template without one costs nothing, a single process has nothing to share."""
+    import torch
+    import torch.distributed as dist
+    rank, world, live = _rank_world(group)
+    template = getattr(solver, "template", None)
+    tables = template.obstacle_tables() if hasattr(template, "obstacle_tables") else {}
+    if not live or not tables:
+        return
+    from . import abi
+    for k in sorted(tables):
+        buf = torch.zeros(1 + 4 * abi.MAX_OBSTACLES, dtype=torch.float64, device=dev)
+        if rank == 0:
+            rows = np.asarray(solver.obstacles.get(k, np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4)
+            buf[0] = rows.shape[0]
+            buf[1:1 + rows.size] = torch.from_numpy(rows.ravel()).to(dev)
+        dist.broadcast(buf, src=0, group=group)
+        if rank != 0:
+            host = buf.cpu().numpy()
+            solver.set_obstacles(k, host[1:1 + 4 * int(host[0])].reshape(-1, 4))
+
+
 _STREAMS = {}
 
 
@@ -166,6 +189,8 @@ def solve_mixed(blocks, device=None, group=None):
     with one (solutions, fitness, success, steps) per block, None elsewhere."""
     import torch
     dev = _device(device)
+    for solver, _, _, _ in blocks:
+        _share_obstacles(solver, dev, group)
     shards = [_scatter(solver, seeds, gp, dev, group) for solver, _, seeds, gp in blocks]
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)  # the scattered rows are complete before the solver streams read them

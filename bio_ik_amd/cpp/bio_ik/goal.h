@@ -115,6 +115,9 @@ public:
     virtual std::string gpuVariableName() const { return std::string(); }
     virtual std::string gpuBaseLinkName() const { return std::string(); }  // BASE LINKS (include/bioik_hip.h): bioik_problem_desc::goal_base_link, "" = the world
     virtual void gpuParams(std::vector<double>&) const {}
+    // BIOIK_GOAL_CLEARANCE: the goal's obstacle table, rows cx cy cz R in the world frame -- DATA beside the problem template (bioik_problem_set_obstacles), the same for
+    // every query of a call; null for every other goal
+    virtual const std::vector<double>* gpuObstacles() const { return nullptr; }
 };
 
 #if defined(BIOIK_WITH_KINEMATICS_BASE)

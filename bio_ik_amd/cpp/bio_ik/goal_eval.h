@@ -20,7 +20,7 @@ public:
         RobotInfo info;                                                                  // one entry per robot variable
         std::function<int(const std::string&)> variable_index;                           // robot variable by name, -1: unknown
         std::function<Frame(const std::string&, const std::vector<double>&)> link_frame;  // global frame of a link at a full variable vector
-        std::function<const std::vector<double>*(const std::string&)> link_points;       // collision points x y z r of a link (TouchGoal); may be empty
+        std::function<const std::vector<double>*(const std::string&)> link_points;       // collision points x y z r of a link (TouchGoal, ClearanceGoal); may be empty
         std::function<const std::vector<double>*(const std::string&)> link_disks;        // collision disks cx cy cz r ax ay az 0 of a link (TouchGoal); may be empty
     };
 

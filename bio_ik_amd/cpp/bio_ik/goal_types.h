@@ -429,6 +429,65 @@ public:
     void gpuParams(std::vector<double>& o) const override { o.insert(o.end(), {position.x(), position.y(), position.z(), normal.x(), normal.y(), normal.z()}); }
 };
 
+// ClearanceGoal (no reference counterpart; include/bioik_hip.h: BIOIK_GOAL_CLEARANCE): the spheres of the link -- its collision points x y z r of the robot model -- keep
+// at least `margin` away from a table of obstacle spheres cx cy cz R in the world frame (at most BIOIK_MAX_OBSTACLES rows):
+//     w_i = p + rotate(q, v_i)     s_ij = (margin + r_i) + R_j     pen = s_ij > 0 ? max(0, s_ij - |w_i - c_j|) : 0     cost = sum_i sum_j pen^2
+// The margin is a per-query number; the table is data of the goal, shared by every query of a call: the plugin core uploads it to the device when it differs from what
+// the compiled problem holds (it is no part of the problem cache's key).  A link with disks or with a shape that is no set of spheres is refused by the device.
+class ClearanceGoal : public LinkGoalBase {
+    double margin_;
+    std::vector<double> obstacles_;
+
+public:
+    ClearanceGoal() : margin_(0.0) {}
+    ClearanceGoal(const std::string& link_name, double margin, const std::vector<double>& obstacles = std::vector<double>(), double weight = 1.0)
+        : LinkGoalBase(link_name, weight), margin_(margin) {
+        setObstacles(obstacles);
+    }
+    double getMargin() const { return margin_; }
+    void setMargin(double m) { margin_ = m; }
+    const std::vector<double>& getObstacles() const { return obstacles_; }
+    void setObstacles(const std::vector<double>& rows) {  // cx cy cz R per obstacle: what bioik_problem_set_obstacles accepts
+        if (rows.size() % 4 != 0) throw std::invalid_argument("ClearanceGoal: obstacle rows are cx cy cz R");
+        if (rows.size() / 4 > (size_t)BIOIK_MAX_OBSTACLES) throw std::invalid_argument("ClearanceGoal: more than BIOIK_MAX_OBSTACLES obstacles");
+        for (size_t i = 0; i < rows.size(); i++)
+            if (!std::isfinite(rows[i]) || (i % 4 == 3 && rows[i] < 0)) throw std::invalid_argument("ClearanceGoal: an obstacle row must be finite with a radius >= 0");
+        obstacles_ = rows;
+    }
+    void addObstacle(const Vector3& centre, double radius) {
+        std::vector<double> rows = obstacles_;
+        rows.insert(rows.end(), {centre.x(), centre.y(), centre.z(), radius});
+        setObstacles(rows);
+    }
+    // the formula above with the quaternion as it is, unit or not (frame.h:108-149): i outer, j inner, one running sum
+    static double cost(const Frame& fb, double margin, const std::vector<double>& points, const std::vector<double>& obstacles) {
+        const Quaternion q = fb.getOrientation();
+        const Vector3 u(q.x(), q.y(), q.z()), p = fb.getPosition();
+        double sum = 0.0;
+        for (size_t i = 0; i + 4 <= points.size(); i += 4) {
+            if (points[i + 3] < 0) continue;  // (the marker of a shape that is no point set: the device refuses such a link)
+            const Vector3 v(points[i], points[i + 1], points[i + 2]);
+            const Vector3 t = u.cross(v);
+            const Vector3 w = p + v + (t * q.w() + u.cross(t)) * 2.0;
+            const double sm = margin + points[i + 3];
+            for (size_t j = 0; j + 4 <= obstacles.size(); j += 4) {
+                const double s = sm + obstacles[j + 3];
+                const Vector3 e = Vector3(obstacles[j], obstacles[j + 1], obstacles[j + 2]) - w;
+                const double d2 = e.dot(e);
+                if (s > 0 && d2 < s * s) {
+                    const double pen = std::fmax(0.0, s - std::sqrt(d2));
+                    sum += pen * pen;
+                }
+            }
+        }
+        return sum;
+    }
+    double evaluate(const GoalContext& context) const override { return cost(context.getLinkFrame(), margin_, context.getLinkPoints(), obstacles_); }
+    int gpuOpcode() const override { return BIOIK_GOAL_CLEARANCE; }
+    void gpuParams(std::vector<double>& o) const override { o.push_back(margin_); }
+    const std::vector<double>* gpuObstacles() const override { return &obstacles_; }
+};
+
 class BalanceGoal : public Goal {  // goal_types.h:540-566, goal_types.cpp:231-272
     Vector3 target_, axis_;
 

@@ -47,7 +47,7 @@ struct ModelView {
     std::vector<double> var_max_velocity;  // VariableBounds::max_velocity_ (RobotInfo, include/bio_ik/robot_info.h:70-106)
     std::vector<uint8_t> var_prismatic;
     std::function<void(const std::string& link, const double* positions, double* frame7)> link_frame;  // global frame of a link at a full variable vector
-    std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal on the host); may be empty
+    std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal, ClearanceGoal on the host); may be empty
     std::function<const std::vector<double>*(const std::string& link)> link_disks;   // collision disks cx cy cz r ax ay az 0 of a link (likewise)
     std::vector<std::string> var_names;  // optional: the variables' names, for messages (consistency limits that are refused name their variable)
 };
@@ -162,6 +162,7 @@ struct Request {
 class Engine {
     struct ProblemSet {  // one compiled problem per device for ONE goal structure
         std::vector<bioik_problem*> per_device;
+        std::map<size_t, std::vector<double>> obstacles;  // per ClearanceGoal (index in the goal list): the table every handle of the set holds (none yet: the empty one)
         ~ProblemSet() {
             for (auto* p : per_device) bioik_problem_destroy(p);
         }
@@ -324,6 +325,20 @@ private:
         const size_t K = tk->replicas;
         std::shared_ptr<ProblemSet> set = problemFor(device_goals, rq.fixed_joints);
         tk->problems = set, tk->handles = set->per_device;
+        // the obstacle tables of the ClearanceGoals are DATA, no part of the cache's key: a goal's table goes to the handles when it differs from what they hold.
+        // bioik_problem_set_obstacles completes the handle's tickets in flight (their results are delivered to their own tickets' arrays) before it copies
+        for (size_t gi = 0; gi < device_goals.size(); gi++) {
+            const std::vector<double>* rows = device_goals[gi]->gpuObstacles();
+            if (!rows) continue;
+            std::vector<double>& held = set->obstacles[gi];
+            if (held == *rows) continue;
+            for (bioik_problem* h : set->per_device)
+                if (bioik_problem_set_obstacles(h, (int)gi, rows->size() / 4, rows->empty() ? nullptr : rows->data()) != BIOIK_OK) {
+                    set->obstacles.erase(gi);  // (what the handles hold is no longer known to be one table: the next request uploads again)
+                    throw std::runtime_error(std::string("bio_ik (MI355X): ") + bioik_last_error());
+                }
+            held = *rows;
+        }
         bioik_problem* problem = tk->handles.front();
         const size_t P = (size_t)bioik_problem_param_count(problem);
         tk->active.resize((size_t)bioik_problem_active_variable_count(problem));

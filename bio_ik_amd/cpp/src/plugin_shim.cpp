@@ -19,12 +19,14 @@ struct WireGoal : bio_ik::Goal {  // a goal of the Python package, already seria
     int opcode = -1;
     std::string link, variable, base_link;
     std::vector<double> numbers;
+    std::vector<double> obstacles;  // BIOIK_GOAL_CLEARANCE: the goal's table, rows cx cy cz R
     void setSecondary(bool s) { secondary_ = s; }
     int gpuOpcode() const override { return opcode; }
     std::string gpuLinkName() const override { return link; }
     std::string gpuVariableName() const override { return variable; }
     std::string gpuBaseLinkName() const override { return base_link; }
     void gpuParams(std::vector<double>& out) const override { out.insert(out.end(), numbers.begin(), numbers.end()); }
+    const std::vector<double>* gpuObstacles() const override { return opcode == BIOIK_GOAL_CLEARANCE ? &obstacles : nullptr; }
 };
 
 struct InFlight {
@@ -73,6 +75,8 @@ typedef struct bioik_plugin_goal {
     double weight;
     const double* numbers;  // [n_numbers] the goal's per-query numbers (the same for every query of the batch)
     const char* base_link;  // NULL / "": the world (BASE LINKS, include/bioik_hip.h)
+    const double* obstacles;  // BIOIK_GOAL_CLEARANCE: [n_obstacles][4] cx cy cz R, world frame (the goal's table: data, the same for every query); else NULL
+    uint64_t n_obstacles;
 } bioik_plugin_goal;
 
 struct bioik_plugin {
@@ -252,6 +256,7 @@ static void buildRequest(bioik_plugin* p, InFlight& f, bio_ik::core::Request& rq
             if (goals[i].base_link) g->base_link = goals[i].base_link;
             g->setWeight(goals[i].weight);
             g->numbers.assign(goals[i].numbers, goals[i].numbers + goals[i].n_numbers);
+            if (goals[i].obstacles && goals[i].n_obstacles) g->obstacles.assign(goals[i].obstacles, goals[i].obstacles + 4 * goals[i].n_obstacles);
             g->setSecondary(goals[i].secondary != 0);
             rq.goals.push_back(g);
         }

@@ -62,6 +62,7 @@ int goal_param_count(int type) {
         case BIOIK_GOAL_CONE: return 11;
         case BIOIK_GOAL_BALANCE: return 6;
         case BIOIK_GOAL_TOUCH: return 6;
+        case BIOIK_GOAL_CLEARANCE: return 1;  // (18 is no opcode: include/bioik_hip.h)
     }
     return -1;
 }
@@ -230,7 +231,8 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         long var;
         double weight;
         int secondary, param_off;
-        int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them
+        int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them.  ClearanceGoal: its points, and in
+                                                   // disk_count the first row of its obstacle block
         int base_tip;                              // a based goal (bioik_problem_desc::goal_base_link): the public tip of its base link, else -1
     };
     std::vector<G> goals;
@@ -253,6 +255,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             if (base == g.link) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + "the base link is the goal's own link");
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, who + "a base link on a secondary goal (secondary link goals read the null frame: a relative one would be a constant)");
             if (g.type == BIOIK_GOAL_TOUCH || g.type == BIOIK_GOAL_BALANCE) throw Error(BIOIK_ERR_UNSUPPORTED, who + "a base link on a TouchGoal or a BalanceGoal has no device implementation");
+            if (g.type == BIOIK_GOAL_CLEARANCE) throw Error(BIOIK_ERR_UNSUPPORTED, who + "a base link on a ClearanceGoal (self-collision: obstacles in another link's frame) has no device implementation");
             info.base_tip = add_tip_link(base);  // behind the goal's own link, as a describe() with two addLink calls
         }
         if (g.variable >= 0) {
@@ -276,6 +279,25 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             info.point_first = (int)(touch_points.size() / 4), info.point_count = count, info.disk_count = dcount;
             touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
             touch_points.insert(touch_points.end(), m->disks.begin() + (size_t)dfirst * 8, m->disks.begin() + (size_t)(dfirst + dcount) * 8);
+        }
+        clearance_block.push_back(-1);
+        if (g.type == BIOIK_GOAL_CLEARANCE) {  // the spheres of the link, as the points the model was given; behind them the goal's obstacle block, empty
+            if (g.link < 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "ClearanceGoal names no link");
+            const int first = m->point_first[g.link], count = m->point_first[g.link + 1] - first;
+            for (int i = 0; i < count; i++)
+                if (m->points[(size_t)(first + i) * 4 + 3] < 0.0)
+                    throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: a row of the link in bioik_model_desc::link_points has the radius -1, the marker of a shape that is no "
+                                                       "set of spheres (a mesh without its vertices, a cylinder or a cone left as it was): no device implementation, not approximated");
+            if (m->disk_first[g.link + 1] - m->disk_first[g.link] > 0)
+                throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link carries disks (bioik_model_desc::link_disks: a cylinder or a cone); only spheres have a device implementation, not approximated");
+            if (count <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "ClearanceGoal: the link has no collision points (bioik_model_desc::link_points)");
+            if (count > BIOIK_MAX_TOUCH_POINTS)
+                throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) + ") collision points");
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = count;
+            touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
+            info.disk_count = (int)(touch_points.size() / 4);  // (DevGoal::pad: the first row of the obstacle block -- its count row, all zero bits: no obstacle)
+            touch_points.insert(touch_points.end(), (size_t)(1 + BIOIK_MAX_OBSTACLES) * 4, 0.0);
+            clearance_block.back() = info.disk_count;
         }
         if (g.type == BIOIK_GOAL_BALANCE) {  // BalanceGoal::describe (goal_types.cpp:231-255): every link with mass becomes a tip, in link order
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, "BalanceGoal cannot be a secondary goal (the reference's has no such constructor)");
@@ -606,7 +628,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             if (g.var >= 0) o.var_op = dev.op_of_gene[g.var];
             else o.var_seed = (int)(-1 - g.var);
         }
-        if (g.type == BIOIK_GOAL_TOUCH) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
+        if (g.type == BIOIK_GOAL_TOUCH || g.type == BIOIK_GOAL_CLEARANCE) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
         if (g.base_tip >= 0 && g.tip >= 0) {  // var_op <= -2 marks a based goal (a link goal reads no variable): -2 - (held tip * 2 + "the held frame is the goal's own link's")
             const int own = dev.tip_of_out[g.tip], base = dev.tip_of_out[g.base_tip];
             o.tip = std::max(own, base);

@@ -50,6 +50,7 @@ struct HostProblem {
     std::vector<int> tip_links;         // link per public tip
     int param_count = 0;
     std::vector<double> touch_points;   // the points of the links the TouchGoals name and behind each goal's points its disks, goal after goal (DevGoal::var_op / var_seed / pad index it): uploaded once by bioik_problem_create
+    std::vector<int> clearance_block;   // per goal of bioik_problem_desc::goals: the first row of its obstacle block in touch_points (bioik_types.h), -1 for a goal that is no ClearanceGoal
     DevProblem dev;
     HostProblem(const HostModel* m, const bioik_problem_desc& d);
 };

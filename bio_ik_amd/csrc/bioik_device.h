@@ -21,7 +21,7 @@
 enum {
     G_POSITION = 0, G_ORIENTATION = 1, G_POSE = 2, G_LOOK_AT = 3, G_MAX_DISTANCE = 4, G_MIN_DISTANCE = 5, G_LINE = 6,
     G_PLANE = 7, G_AVOID_JOINT_LIMITS = 8, G_CENTER_JOINTS = 9, G_REGULARIZATION = 10, G_MINIMAL_DISPLACEMENT = 11,
-    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15, G_TOUCH = 17
+    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15, G_TOUCH = 17, G_CLEARANCE = 19
 };
 enum { FK_LINEAR = 0, FK_EXACT = 1 };
 
@@ -308,6 +308,64 @@ BIOIK_CALL double goal_eval_touch(ProbPtr pb_, int first, int count, int disks, 
     }
     const double d = fmin(m0, m1) - dot3(normal, v3(P[0], P[1], P[2]) - fb.p);
     return d * d;
+}
+// ClearanceGoal (include/bioik_hip.h: BIOIK_GOAL_CLEARANCE; no reference counterpart): the spheres of the link -- its points (v_i, r_i) -- keep `margin` = P[0]
+// away from the goal's table of obstacle spheres (c_j, R_j) in the world frame:
+//     w_i = p + rotate(q, v_i)     s_ij = (margin + r_i) + R_j     pen = s_ij > 0 ? max(0, s_ij - |w_i - c_j|) : 0     cost = sum_i sum_j pen^2
+// first / count: the goal's `count` >= 1 point rows in DevProblem::touch_points, as a TouchGoal's.  block: the first row of the goal's OBSTACLE BLOCK in the same
+// buffer, BIOIK_MAX_OBSTACLES + 1 rows of four doubles that bioik_problem_create lays out once: row 0 holds the number of obstacles m (an int32 in its first
+// four bytes), rows 1 ... m are cx cy cz R.  The count is read HERE, from device memory, on every evaluation: bioik_problem_set_obstacles rewrites block and
+// count in place, and a captured graph replays with the table of the moment.
+// Both tables are the same for every lane: wavefront-uniform pointers, scalar loads, the numbers SGPR operands (goal_eval_touch above).  Per point one
+// rotation and translation (bk_qrot, then three additions) and margin + r_i, hoisted out of the inner loop.  Two obstacles per trip -- eight doubles of table, the
+// width of goal_eval_touch's trips, for the same reason: the scalar registers a callee may use without saving any -- but ONE running sum, i outer, j inner,
+// ascending, from 0 (the header states the order; fma(pen, pen, sum) per pair that penetrates).  An obstacle left over is a trip of its own.
+// The square root is taken only where  s > 0 && d2 < s * s,  d2 = |w - c|^2 -- and that skip is EXACT, not an approximation: for a correctly rounded root
+// sqrt(fl(s * s)) == s (s a double, no overflow or underflow of the square: |s| between 1e-150 and 1e150), and rounding is monotone, so d2 >= fl(s * s) implies
+// fl(sqrt(d2)) >= fl(sqrt(fl(s * s))) = s, hence max(0, s - fl(sqrt(d2))) = 0: the pair adds nothing either way.  (A NaN in d2 or s fails the test: the pair adds
+// nothing.)  A plain `if`: the compiler skips the block where no lane of the wavefront takes it (an execz branch); lanes that diverge run it under their mask.
+// m = 0: the cost is 0.0 without a look at the points.
+// One out-of-line copy, reached only from the general kernel flavour: the lean and dense kernels are compiled without it.
+typedef decltype(&((ProbPtr)0)->n_ops) UniformI32;  // read-only 32-bit words in the address space of the problem block
+BIOIK_DEV double clearance_pair(double sum, const V3& w, double sm, double cx, double cy, double cz, double R) {
+    const double s = sm + R;
+    const double d2 = dist2(w, v3(cx, cy, cz));
+    if (s > 0.0 && d2 < s * s) {
+        const double pen = fmax(0.0, s - sqrt(d2));
+        sum = BK_FMA(pen, pen, sum);
+    }
+    return sum;
+}
+BIOIK_CALL double goal_eval_clearance(ProbPtr pb_, int first, int count, int block, const lds_f64* P, F7 fb) {
+    const unsigned long long pba = (unsigned long long)pb_;
+    const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
+    const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * p_uniform(first));
+    const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
+    const unsigned long long oaddr = (unsigned long long)(pb->touch_points + 4 * p_uniform(block));
+    const UniformF64 head = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(oaddr >> 32)) << 32) | (unsigned int)p_uniform((int)oaddr));
+    const int n = p_uniform(count);
+    int m = p_uniform(*(UniformI32)head);
+    m = m < 0 ? 0 : (m > BIOIK_DEV_MAX_OBSTACLES ? BIOIK_DEV_MAX_OBSTACLES : m);  // (never beyond the block, whatever the word holds)
+    if (m == 0) return 0.0;
+    const UniformF64 o = head + 4;
+    const double margin = P[0];
+    double sum = 0.0;
+    for (int i = 0; i < n; i++) {
+        const UniformF64 a = v + 4 * i;
+        const V3 w = fb.p + qrot(fb.q, v3(a[0], a[1], a[2]));
+        const double sm = margin + a[3];
+        int j = 0;
+        for (; j + 2 <= m; j += 2) {
+            const UniformF64 c = o + 4 * j;
+            sum = clearance_pair(sum, w, sm, c[0], c[1], c[2], c[3]);
+            sum = clearance_pair(sum, w, sm, c[4], c[5], c[6], c[7]);
+        }
+        if (j < m) {
+            const UniformF64 c = o + 4 * j;
+            sum = clearance_pair(sum, w, sm, c[0], c[1], c[2], c[3]);
+        }
+    }
+    return sum;
 }
 // The link goals beyond position / orientation / pose: one out-of-line copy (sqrt, divisions, acos) instead of one per
 // evaluation site.  P: the goal's numbers (at most 11, goal_types.h) where they lie in LDS -- the pointer crosses the call with its
@@ -623,8 +681,11 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
         default:  // the remaining link goals
             // TouchGoal: only in the general flavour (the launcher hands a problem with one to k_solve, never to a lean kernel: those stay as they were).  A link
             // goal has no variable: var_op / var_seed carry its first point and its number of points, aux (DevGoal::pad) its number of disks
-            if constexpr (pb_flavour<PB>::general)
+            // ClearanceGoal: likewise; var_op / var_seed its first point and its number of points, aux the first row of its obstacle block
+            if constexpr (pb_flavour<PB>::general) {
                 if (type == G_TOUCH) return goal_eval_touch(pb, var_op, var_seed, aux, (const lds_f64*)P, fb);
+                if (type == G_CLEARANCE) return goal_eval_clearance(pb, var_op, var_seed, aux, (const lds_f64*)P, fb);
+            }
             return goal_eval_link_rare(type, (const lds_f64*)P, fb);
     }
     return 0.0;

@@ -24,7 +24,8 @@
 
 static_assert((int)G_POSITION == (int)BIOIK_GOAL_POSITION && (int)G_POSE == (int)BIOIK_GOAL_POSE && (int)G_CONE == (int)BIOIK_GOAL_CONE &&
                   (int)G_JOINT_VARIABLE == (int)BIOIK_GOAL_JOINT_VARIABLE && (int)G_MINIMAL_DISPLACEMENT == (int)BIOIK_GOAL_MINIMAL_DISPLACEMENT &&
-                  (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS && (int)G_TOUCH == (int)BIOIK_GOAL_TOUCH,
+                  (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS && (int)G_TOUCH == (int)BIOIK_GOAL_TOUCH && (int)G_CLEARANCE == (int)BIOIK_GOAL_CLEARANCE &&
+                  BIOIK_DEV_MAX_OBSTACLES == BIOIK_MAX_OBSTACLES,
               "goal opcodes out of sync with include/bioik_hip.h");
 static_assert((int)FK_LINEAR == (int)BIOIK_FK_LINEAR && (int)FK_EXACT == (int)BIOIK_FK_EXACT, "fk modes out of sync");
 
@@ -350,7 +351,7 @@ struct bioik_problem {
     bioik_model* model;
     bioik::HostProblem host;
     DevProblem* d_pb = nullptr;
-    double* d_touch = nullptr;  // DevProblem::touch_points: the collision points the problem's TouchGoals read (null without one)
+    double* d_touch = nullptr;  // DevProblem::touch_points: the collision points the problem's TouchGoals read, the points and obstacle blocks of its ClearanceGoals (null without either)
     // Host-pointer solves (bioik_solve_batch, bioik_solve_batch_submit / _wait) go through one of kIoSlots slots, each with a grow-only
     // device arena, its page-locked host mirror (one DMA in, one DMA out per solve) and its own stream: up to kIoSlots batches of one
     // handle are in flight together, the tail of one solve behind the bulk of the next.  Streams are created at a
@@ -627,7 +628,8 @@ static size_t eval_lds(const bioik_problem* p, size_t bytes) {
     return bytes;
 }
 
-// a problem a lean kernel can run (bioik_platform.h, pb_flavour): no floating / planar joints, ops that meet the genes in gene order, no BalanceGoal, no TouchGoal, no based goal
+// a problem a lean kernel can run (bioik_platform.h, pb_flavour): no floating / planar joints, ops that meet the genes in gene order, no BalanceGoal, no TouchGoal, no
+// ClearanceGoal (either one puts its tables into touch_points: the buffer is there exactly for a problem with one of the two), no based goal
 // a problem with a based goal (BASE LINKS, include/bioik_hip.h): some tip holds its frame for a later one
 static bool has_based_goal(const DevProblem& d) {
     for (int t = 0; t < d.T; t++)
@@ -1378,7 +1380,84 @@ int bioik_problem_set_first_query(bioik_problem* p, uint64_t first_query) {
     return BIOIK_OK;
 }
 
-int bioik_resolve_islands(const bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t* islands, int32_t* island_sync) {
+// ---- obstacle tables of the ClearanceGoals (include/bioik_hip.h; the block's layout: bioik_types.h) ----
+// the first row of goal `goal_index`'s obstacle block in touch_points; throws for anything that is no ClearanceGoal of the problem
+static size_t obstacle_block(const bioik_problem* p, int goal_index, const char* who) {
+    if (!p) throw Error(BIOIK_ERR_INVALID_ARGUMENT, std::string(who) + ": null handle");
+    if (goal_index < 0 || (size_t)goal_index >= p->host.clearance_block.size())
+        throw Error(BIOIK_ERR_INVALID_ARGUMENT, std::string(who) + ": goal index " + std::to_string(goal_index) + " out of range (the problem has " + std::to_string(p->host.clearance_block.size()) + " goals)");
+    if (p->host.clearance_block[goal_index] < 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, std::string(who) + ": goal " + std::to_string(goal_index) + " is not a CLEARANCE goal");
+    return (size_t)p->host.clearance_block[goal_index];
+}
+static void upload_obstacles(bioik_problem* p, size_t row, size_t n, const double* spheres);
+int bioik_problem_set_obstacles(bioik_problem* p, int goal_index, size_t n, const double* spheres) {
+    API_BEGIN
+    const size_t row = obstacle_block(p, goal_index, "bioik_problem_set_obstacles");
+    if (n > (size_t)BIOIK_MAX_OBSTACLES)
+        throw Error(BIOIK_ERR_UNSUPPORTED, "bioik_problem_set_obstacles: " + std::to_string(n) + " obstacles, more than BIOIK_MAX_OBSTACLES (" + std::to_string(BIOIK_MAX_OBSTACLES) + ")");
+    if (n > 0 && !spheres) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_set_obstacles: spheres is null");
+    for (size_t i = 0; i < n; i++) {
+        for (int c = 0; c < 4; c++)
+            if (!std::isfinite(spheres[4 * i + c])) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_set_obstacles: row " + std::to_string(i) + " holds a number that is not finite");
+        if (spheres[4 * i + 3] < 0.0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_problem_set_obstacles: row " + std::to_string(i) + " has a radius < 0");
+    }
+    upload_obstacles(p, row, n, spheres);
+    API_END
+}
+static void upload_obstacles(bioik_problem* p, size_t row, size_t n, const double* spheres) {  // (checked rows)
+    std::lock_guard<std::mutex> lock(p->mtx);
+    DeviceGuard on_device(p->model->device);
+    // nothing of this handle reads the table while it changes: the submitted tickets are completed, the handle's own streams drained (the slots' and the default
+    // stream of the function-level entries); device-pointer solves on the caller's streams are the caller's to wait for
+    for (auto& sl : p->io) io_finish(p, sl);
+    for (auto& sl : p->io)
+        if (sl.stream_made) be_sync(sl.stream);
+    be_sync(0);
+    // count row and rows in ONE copy, to an address that never changes (the host's copy of the buffer is kept current: obstacle_count reads it)
+    double* block = p->host.touch_points.data() + 4 * row;
+    const int32_t count = (int32_t)n;
+    std::memset(block, 0, 4 * sizeof(double));
+    std::memcpy(block, &count, sizeof(count));
+    if (n) std::memcpy(block + 4, spheres, n * 4 * sizeof(double));
+    be_h2d(p->d_touch + 4 * row, block, (1 + n) * 4 * sizeof(double), 0);
+    be_sync(0);
+}
+// bioik_solve_batch_multi: the shards are parts of ONE solve, so every handle gets the obstacle tables of problems[0] (a handle that holds them already is left alone)
+static void share_obstacles(bioik_problem* const* problems, int n_problems) {
+    bioik_problem* p0 = problems[0];
+    for (size_t g = 0; g < p0->host.clearance_block.size(); g++) {
+        if (p0->host.clearance_block[g] < 0) continue;
+        std::vector<double> block((size_t)(1 + BIOIK_MAX_OBSTACLES) * 4);
+        {
+            std::lock_guard<std::mutex> lock(p0->mtx);
+            std::memcpy(block.data(), p0->host.touch_points.data() + 4 * (size_t)p0->host.clearance_block[g], block.size() * sizeof(double));
+        }
+        int32_t count = 0;
+        std::memcpy(&count, block.data(), sizeof(count));
+        for (int r = 1; r < n_problems; r++) {
+            bioik_problem* q = problems[r];
+            if (q->host.clearance_block.size() != p0->host.clearance_block.size() || q->host.clearance_block[g] < 0)
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_solve_batch_multi: the handles were compiled from different problem templates");
+            bool same;
+            {
+                std::lock_guard<std::mutex> lock(q->mtx);
+                same = std::memcmp(q->host.touch_points.data() + 4 * (size_t)q->host.clearance_block[g], block.data(), (size_t)(1 + count) * 4 * sizeof(double)) == 0;
+            }
+            if (!same) upload_obstacles(q, (size_t)q->host.clearance_block[g], (size_t)count, block.data() + 4);
+        }
+    }
+}
+int bioik_problem_obstacle_count(const bioik_problem* p, int goal_index) {
+    API_BEGIN
+    const size_t row = obstacle_block(p, goal_index, "bioik_problem_obstacle_count");
+    std::lock_guard<std::mutex> lock(const_cast<bioik_problem*>(p)->mtx);
+    int32_t count = 0;
+    std::memcpy(&count, p->host.touch_points.data() + 4 * row, sizeof(count));
+    return count;
+    API_END
+}
+
+int bioik_resolve_islands(const bioik_problem* p,const bioik_solve_params* params, size_t n, int32_t* islands, int32_t* island_sync) {
     API_BEGIN
     if (!p || !params || !islands || !island_sync) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "null argument");
     const DevSolveParams r = bioik::normalize_params(*params, 0, n, 8 * (size_t)p->model->dev.cus);
@@ -1644,6 +1723,7 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
     }
     const size_t V = problems[0]->host.dev.V, P = problems[0]->host.dev.P;
     check_arrays(problems[0], SolveArrays{n, seeds, goal_params, solutions, fitness, success, steps, nullptr});
+    share_obstacles(problems, n_problems);
     const uint64_t first = problems[0]->first_query;
     const size_t W = (size_t)n_problems;
     // BIOIK_ISLANDS_AUTO: one island count for the whole batch, sized to the largest shard (what one device gets), so that every shard runs the same solve

@@ -79,8 +79,12 @@ struct DevGoal {
     int32_t var_op;     // op index of the goal's variable (JointVariableGoal), -1 none.  TouchGoal (a link goal: it has no variable): its first point in touch_points, counted in rows of four doubles
     int32_t var_seed;   // robot variable index when the goal's joint is fixed (GoalContext::getVariablePosition, goal.h:70-77), -1 none.  TouchGoal: its number of points
     int32_t param_off;  // offset of the goal's numbers inside the per-query parameter vector
-    int32_t pad;        // TouchGoal: its number of disks, whose rows lie directly behind its points in touch_points (0 for every other goal)
+    int32_t pad;        // TouchGoal: its number of disks, whose rows lie directly behind its points in touch_points (0 for every other goal).  ClearanceGoal (var_op / var_seed as a
+                        // TouchGoal's): the first row of its obstacle block in touch_points
 };
+// ClearanceGoal: an obstacle block is 1 + BIOIK_DEV_MAX_OBSTACLES rows of four doubles in DevProblem::touch_points -- row 0: the number of obstacles, an int32 in its first
+// four bytes; rows 1 ...: cx cy cz R, world frame.  Laid out once by bioik_problem_create, rewritten in place by bioik_problem_set_obstacles (= BIOIK_MAX_OBSTACLES, include/bioik_hip.h)
+#define BIOIK_DEV_MAX_OBSTACLES 256
 
 struct DevProblem {
     // the scalars one code site reads together sit in one 16-byte group, so that they arrive with one scalar load
@@ -124,7 +128,8 @@ struct DevProblem {
     DevGoal secondary[BIOIK_MAX_GOALS];
     DevGoal balance[BIOIK_MAX_BALANCE];  // params: target[3] axis[3]
     // TouchGoals: the collision points (x y z r, link frame) of the links they name and behind each goal's points its disks (cx cy cz r ax ay az 0: the
-    // ends of cylinders, the bases of cones), goal after goal, in a buffer of global memory that the problem handle owns (null without such a goal).  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
+    // ends of cylinders, the bases of cones), goal after goal, in a buffer of global memory that the problem handle owns (null without such a goal).  ClearanceGoals:
+    // their points and their obstacle blocks (above) in the same buffer.  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
     const double* touch_points;
 };
 

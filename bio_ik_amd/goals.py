@@ -282,6 +282,56 @@ class TouchGoal(LinkGoalBase):
         return d * d
 
 
+class ClearanceGoal(LinkGoalBase):
+    """No reference counterpart (include/bioik_hip.h: BIOIK_GOAL_CLEARANCE): the spheres of the link -- the link's collision points of the robot model, each with its
+    radius -- keep at least `margin` away from a table of obstacle spheres in the world frame, rows cx cy cz R, at most abi.MAX_OBSTACLES of them.  The margin is a
+    per-query parameter; the table is data of the goal, shared by every query: ProblemTemplate carries it, HipSolver uploads it when the handle is created and
+    HipSolver.set_obstacles replaces it on a live handle."""
+    opcode = abi.GOAL_CLEARANCE
+
+    def __init__(self, link_name="", margin=0.0, obstacles=(), weight=1.0):
+        super().__init__(link_name, weight, "")
+        self.margin_ = float(margin)
+        self.setObstacles(obstacles)
+
+    def getMargin(self):
+        return self.margin_
+
+    def setMargin(self, m):
+        self.margin_ = float(m)
+
+    def getObstacles(self):
+        return self.obstacles_
+
+    def setObstacles(self, spheres):
+        """rows cx cy cz R: finite, R >= 0, at most abi.MAX_OBSTACLES (what bioik_problem_set_obstacles accepts)"""
+        a = np.array(spheres, dtype=np.float64).reshape(-1, 4)
+        if a.shape[0] > abi.MAX_OBSTACLES:
+            raise ValueError("ClearanceGoal: %d obstacles, more than MAX_OBSTACLES (%d)" % (a.shape[0], abi.MAX_OBSTACLES))
+        if not np.isfinite(a).all() or (a[:, 3] < 0).any():
+            raise ValueError("ClearanceGoal: an obstacle row must be finite with a radius >= 0")
+        self.obstacles_ = np.ascontiguousarray(a)
+
+    def params(self):
+        return np.array([self.margin_])
+
+    def evaluate(self, frame, points):
+        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link).  The device's formula in numpy
+        (plain multiplications and additions where the device fuses them: equal up to rounding)."""
+        f = np.asarray(frame, dtype=np.float64)
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        obs = self.obstacles_
+        if obs.shape[0] == 0 or pts.shape[0] == 0:
+            return 0.0
+        u, w = f[3:6], f[6]
+        t = np.cross(u[None], pts[:, :3])
+        world = f[None, :3] + pts[:, :3] + 2.0 * (w * t + np.cross(u[None], t))  # q as it is, not normalised
+        s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
+        d = np.linalg.norm(world[:, None, :] - obs[None, :, :3], axis=2)
+        pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
+        return float((pen * pen).sum())
+
+
 class _JointSetGoal(Goal):
     def __init__(self, weight=1.0, secondary=True):
         super().__init__()

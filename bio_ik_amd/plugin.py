@@ -37,7 +37,19 @@ class _Settings(C.Structure):  # bioik_plugin_settings (cpp/src/plugin_shim.cpp)
 class _WireGoal(C.Structure):  # bioik_plugin_goal
     _fields_ = [("opcode", C.c_int32), ("secondary", C.c_int32), ("n_numbers", C.c_int32), ("reserved", C.c_int32),
                 ("link", C.c_char_p), ("variable", C.c_char_p), ("weight", C.c_double), ("numbers", C.POINTER(C.c_double)),
-                ("base_link", C.c_char_p)]  # BASE LINKS (include/bioik_hip.h): "" = the world
+                ("base_link", C.c_char_p),  # BASE LINKS (include/bioik_hip.h): "" = the world
+                ("obstacles", C.POINTER(C.c_double)), ("n_obstacles", C.c_uint64)]  # ClearanceGoal: its table, rows cx cy cz R (data: the plugin core uploads it when it changes)
+
+
+def _wire_obstacles(w, g, keep):
+    """a ClearanceGoal's table onto its wire record (`keep` holds the array while the call runs); every other goal: none"""
+    rows = g.getObstacles() if g.opcode == abi.GOAL_CLEARANCE else None
+    if rows is None or not len(rows):
+        w.obstacles, w.n_obstacles = None, 0
+        return
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 4)
+    keep.append(rows)
+    w.obstacles, w.n_obstacles = abi.dptr(rows), rows.shape[0]
 
 
 _shims = {}
@@ -273,6 +285,7 @@ class BioIKKinematicsPlugin:
             w.variable = (g.variable_name() or "").encode()
             w.base_link = ((g.base_link_name() if hasattr(g, "base_link_name") else None) or "").encode()
             w.numbers = abi.dptr(numbers)
+            _wire_obstacles(w, g, keep)
         if context_state is None:
             context, base = m.default_positions(), self._base_default
         else:
@@ -326,6 +339,7 @@ class BioIKKinematicsPlugin:
             w.variable = (g.variable_name() or "").encode()
             w.base_link = ((g.base_link_name() if hasattr(g, "base_link_name") else None) or "").encode()
             w.numbers = abi.dptr(numbers)
+            _wire_obstacles(w, g, keep)
         if context_state is None:
             context, base = m.default_positions(), self._base_default
         else:

@@ -54,6 +54,14 @@ class ProblemTemplate:
         d.goal_base_link = abi.iptr(self._goal_base_link) if (self._goal_base_link >= 0).any() else None
         return d
 
+    def obstacle_tables(self, goals=None):
+        """{goal index: rows cx cy cz R} of the ClearanceGoals of `goals` (default: the template's own goal objects).  The tables are data beside the descriptor:
+        bioik_problem_desc has no room for them, they reach a handle through bioik_problem_set_obstacles (HipSolver does that when it creates one)."""
+        goals = self.goals if goals is None else goals
+        if len(goals) != len(self.goals):
+            raise ValueError("goal list does not match the problem template")
+        return {k: g.getObstacles() for k, g in enumerate(goals) if g.opcode == abi.GOAL_CLEARANCE}
+
     def pack_params(self, goals=None):
         """Flat parameter vector [P] of `goals` (default: the template's own goal objects)."""
         goals = self.goals if goals is None else goals

@@ -32,6 +32,7 @@ EXPORTS = [
     "bioik_problem_carry_doubles", "bioik_eval_migrate",
     "bioik_solve_batch_bounded", "bioik_solve_batch_bounded_submit", "bioik_solve_batch_bounded_device", "bioik_eval_bounds",
     "bioik_problem_op_count", "bioik_problem_op_variables",
+    "bioik_problem_set_obstacles", "bioik_problem_obstacle_count",
 ]
 
 
@@ -83,6 +84,9 @@ def _declare(L):
     L.bioik_eval_bounds.argtypes = [C.c_void_p, C.c_size_t, _pd, _pd, _pd]
     L.bioik_problem_op_count.argtypes = [C.c_void_p]
     L.bioik_problem_op_variables.argtypes = [C.c_void_p, _pi, _pi]
+    if hasattr(L, "bioik_problem_set_obstacles"):  # (BIOIK_HIP_LIBRARY may name an earlier build of ABI 6 for an A/B run: it has no ClearanceGoal)
+        L.bioik_problem_set_obstacles.argtypes = [C.c_void_p, C.c_int, C.c_size_t, _pd]
+        L.bioik_problem_obstacle_count.argtypes = [C.c_void_p, C.c_int]
     return L
 
 
@@ -217,6 +221,16 @@ class HipSolver:
         self.L.bioik_problem_active_variables(self.problem, _i(self.active_variables))
         self.tip_links = np.zeros(self.T, dtype=np.int32)
         self.L.bioik_problem_tip_links(self.problem, _i(self.tip_links))
+        self.obstacles = {}
+        # the obstacle tables of the template's ClearanceGoals (data of the goals, not of the descriptor): a new handle's are empty
+        try:
+            tables = template.obstacle_tables() if hasattr(template, "obstacle_tables") else {}
+            for k, rows in tables.items():
+                if len(rows):
+                    self.set_obstacles(k, rows)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "problem", None):
@@ -284,6 +298,21 @@ class HipSolver:
         var, gene = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
         self._chk(self.L.bioik_problem_op_variables(self.problem, _i(var), _i(gene)))
         return var[:n], gene[:n]
+
+    def set_obstacles(self, goal_index, spheres):
+        """bioik_problem_set_obstacles: replace the obstacle table of ClearanceGoal `goal_index` (an index into the template's goals) by rows cx cy cz R.  The
+        library completes this handle's submitted tickets and waits for its own streams first; device-pointer solves on the caller's streams are the caller's to
+        wait for."""
+        a = np.ascontiguousarray(np.array(spheres, dtype=np.float64).reshape(-1, 4))
+        self._chk(self.L.bioik_problem_set_obstacles(self.problem, int(goal_index), a.shape[0], _d(a) if a.shape[0] else None))
+        self.obstacles[int(goal_index)] = a  # (what the handle holds now: bio_ik_amd.batch hands it to the other ranks' handles)
+
+    def obstacle_count(self, goal_index):
+        """bioik_problem_obstacle_count: rows of the goal's obstacle table on this handle"""
+        rc = self.L.bioik_problem_obstacle_count(self.problem, int(goal_index))
+        if rc < 0:
+            self._chk(rc)
+        return int(rc)
 
     def set_first_query(self, first_query):
         self._chk(self.L.bioik_problem_set_first_query(self.problem, int(first_query)))

@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_problem_desc::goal_base_link behind the fields every caller of 6 fills (a shorter struct_size gets none),
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: BIOIK_GOAL_CLEARANCE (opcode 19; 18 stays unknown), BIOIK_MAX_OBSTACLES, bioik_problem_set_obstacles,
+                               bioik_problem_obstacle_count (a link's spheres keep clear of a table of obstacle spheres).
+                               6, additions that break no caller of 6: bioik_problem_desc::goal_base_link behind the fields every caller of 6 fills (a shorter struct_size gets none),
                                BIOIK_MAX_HELD_FRAMES (BASE LINKS: a link goal evaluated in another link's frame).
                                6, additions that break no caller of 6: bioik_solve_batch_bounded, bioik_solve_batch_bounded_submit, bioik_solve_batch_bounded_device, bioik_eval_bounds,
                                bioik_problem_op_count, bioik_problem_op_variables
@@ -102,9 +104,36 @@ enum {
                                             the normal, what the reference's hill climb returns; a disk's is exact in closed form, and n_l is not
                                             assumed to be of unit length).  A link with neither points nor disks: BIOIK_ERR_INVALID_ARGUMENT; more
                                             than BIOIK_MAX_TOUCH_POINTS points and disks together: BIOIK_ERR_UNSUPPORTED                        */
-    BIOIK_GOAL_TYPE_COUNT = 18
+    BIOIK_GOAL_TYPE_COUNT = 18,          /* the opcodes 0 ... 17 are the reference's closed-form classes.  OPCODE 18 IS NO GOAL AND STAYS UNKNOWN: bioik_goal_param_count(18) is -1
+                                            and bioik_problem_create refuses it (callers and tests of ABI 6 rely on that) */
+    BIOIK_GOAL_CLEARANCE = 19            /* no reference counterpart (there: a solution_callback behind the search).  params: margin.  The spheres of the link keep at least
+                                            `margin` away from the goal's table of OBSTACLE SPHERES in the world frame (bioik_problem_set_obstacles below).  With the
+                                            link's frame (p, q), its rows (v_i, r_i), i < n, of bioik_model_desc::link_points and the obstacle rows (c_j, R_j), j < m:
+                                                w_i  = p + rotate(q, v_i)            q as it is, not normalised (the phenotypes of BIOIK_FK_LINEAR included)
+                                                s_ij = (margin + r_i) + R_j
+                                                pen  = s_ij > 0 ? max(0, s_ij - |w_i - c_j|) : 0
+                                                cost = sum_i sum_j pen^2             i outer, j inner, both ascending, one running sum from 0
+                                            The operations, each rounded once, in this order (fma(a, b, c) = a b + c with one rounding; bio_ik_amd/csrc/bioik_fused.h):
+                                                t = q.xyz x v:      t.x = fma(q.y, v.z, -(q.z v.y)),  t.y = fma(q.z, v.x, -(q.x v.z)),  t.z = fma(q.x, v.y, -(q.y v.x))
+                                                u = q.w t + q.xyz x t: u.x = fma(q.w, t.x, fma(q.y, t.z, -(q.z t.y))),  u.y = fma(q.w, t.y, fma(q.z, t.x, -(q.x t.z))),  u.z = fma(q.w, t.z, fma(q.x, t.y, -(q.y t.x)))
+                                                rotate(q, v) = fma(2, u, v) per component (bk_qrot of bioik_fused.h), then w = p + that: three additions
+                                                sm = margin + r_i;   s = sm + R_j;   e = c_j - w_i (three subtractions);   d2 = fma(e.x, e.x, fma(e.y, e.y, e.z e.z))
+                                                if (s > 0 && d2 < s s) { pen = max(0, s - sqrt(d2));  sum = fma(pen, pen, sum); }          sqrt correctly rounded
+                                            The test in front of the root skips nothing that would count: sqrt(fl(s s)) == s for a correctly rounded root, rounding is
+                                            monotone, so d2 >= fl(s s) implies fl(sqrt(d2)) >= s and pen = 0.  A NaN in d2 or s fails the test: the pair adds nothing.
+                                            m = 0 (a new problem; an empty table): the cost is exactly 0.  Success test: the default branch of every non-pose link goal,
+                                            weighted cost < min(dpos, dtwist)^2 -- "clear of every obstacle by the margin, up to the threshold".  A secondary
+                                            ClearanceGoal reads the null frame, like every secondary link goal of this library.  jac, gd*, ranked, bounded, migration,
+                                            timeout and island_sync behave as for a problem with a TouchGoal; such a problem runs in the general kernel flavour.
+                                            Refused by bioik_problem_create: a link without points BIOIK_ERR_INVALID_ARGUMENT; a link that carries disks or a marker row
+                                            (r == -1: never approximated silently), more than BIOIK_MAX_TOUCH_POINTS points, a base link on the goal (self-collision):
+                                            BIOIK_ERR_UNSUPPORTED.  About nine FP64 issue slots per pair that does not penetrate and eighteen per point (counted in the
+                                            code, not timed): 8 points against 16 obstacles cost about as much as the chain walk of a 7-joint arm
+                                            (measured rates: profiles/clearance_goal_metadata_and_bench.log) */
     /* JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
 };
+/* Obstacle spheres one BIOIK_GOAL_CLEARANCE may hold (every evaluation of every individual reads all of them against every point of the link). */
+#define BIOIK_MAX_OBSTACLES 256
 /* Points one BIOIK_GOAL_TOUCH may read (the table of its link).  The minimum is a loop every evaluation of every individual runs in full: about five
  * FP64 issue slots per point (three fused multiply-adds, a minimum and its canonicalisation; counted in the compiled loop, not timed), so by that count a few
  * hundred points cost as much as the whole chain walk of a 7-joint arm (profiles/touch_goal_metadata_and_bench.log has measured solves per second at 8, 64 and 1024 points).
@@ -338,7 +367,8 @@ void bioik_model_destroy(bioik_model* m);
  * (problem.cpp:72-228, ik_base.h:154-161, forward_kinematics.h:253-330, 566-599).
  * Size limits of one problem (BIOIK_ERR_UNSUPPORTED beyond them): 64 moving joints on the union of the goal chains (a short
  * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals,
- * BIOIK_MAX_TOUCH_POINTS collision points and disks together per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS).
+ * BIOIK_MAX_TOUCH_POINTS collision points and disks together per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS),
+ * BIOIK_MAX_TOUCH_POINTS points per ClearanceGoal and BIOIK_MAX_OBSTACLES obstacles in its table (the same buffer; the table's storage is there at full capacity from the start).
  * Tips and joints are further bounded TOGETHER by the 160 KiB of LDS of a CU: the function-level entry points hold 7 x tips x joints doubles
  * of tables plus a genotype column per lane (64 tips on 12 joints: 71 KiB; 24 tips on 63 joints: about 137 KiB; 64 tips on 63 joints: about
  * 290 KiB), the solvers hold more.  A problem beyond that is accepted here and refused with BIOIK_ERR_UNSUPPORTED by every entry point that
@@ -357,6 +387,18 @@ int bioik_problem_variable_count(const bioik_problem* p);                 /* rob
  * keyed by (random_seed, global query index, island), so a batch sharded over several GPUs / calls reproduces the
  * unsharded run when every shard announces its offset.  (New: the reference has one query per call.) */
 int bioik_problem_set_first_query(bioik_problem* p, uint64_t first_query);
+/* OBSTACLE TABLES of the problem's BIOIK_GOAL_CLEARANCE goals: one table per goal, at most BIOIK_MAX_OBSTACLES rows cx cy cz R (centre in the world frame, radius
+ * R >= 0), shared by every query.  `goal_index` counts bioik_problem_desc::goals.  A new problem has empty tables (such a goal then costs exactly 0).
+ * set_obstacles replaces the goal's whole table by the n rows of `spheres` (host pointer; n = 0: `spheres` may be NULL).  Refused, and the table then is what it was:
+ * a null handle, an index out of range or a goal that is no CLEARANCE goal, n > 0 with spheres NULL, a number that is not finite or R < 0:
+ * BIOIK_ERR_INVALID_ARGUMENT; n > BIOIK_MAX_OBSTACLES: BIOIK_ERR_UNSUPPORTED.
+ * The call takes the handle's lock, completes the handle's submitted tickets (their results are delivered), waits for the handle's own streams and copies before it
+ * returns: every solve or evaluation called after it reads the new table, every one completed before it read the old one.  Device-pointer solves on the CALLER's
+ * streams are the caller's to wait for (CONCURRENCY below).  The storage is allocated once, at full capacity, by bioik_problem_create and its address never
+ * changes; the row count lives in device memory beside the rows, not in anything a launch is given: a solve captured into a hipGraph REPLAYS WITH WHATEVER TABLE
+ * IS CURRENT at the replay.  obstacle_count: the rows of the goal's table, or BIOIK_ERR_INVALID_ARGUMENT as above. */
+int bioik_problem_set_obstacles(bioik_problem* p, int goal_index, size_t n, const double* spheres /* [n][4] cx cy cz R, world frame */);
+int bioik_problem_obstacle_count(const bioik_problem* p, int goal_index);
 /* What bioik_solve_params::islands = BIOIK_ISLANDS_AUTO means for a call of n queries on this handle's device: the island count and island_sync the call would
  * run with (an explicit count comes back as it is).  For callers that cut ONE request into several calls -- the MoveIt plugin's shards over `gpu_devices` --
  * and want every part to run the same solve whatever its size: resolve once for the largest part (ceil(rows / W), as bioik_solve_batch_multi does) and pass the
@@ -388,7 +430,10 @@ int bioik_solve_batch(bioik_problem* p, const bioik_solve_params* params, size_t
  * device, and may be created and destroyed while other handles are solving).  bioik_last_error() is per thread.
  * NOT allowed while any call of that handle is running or any solve of it is in flight (no lock covers them): bioik_problem_set_first_query (bioik_solve_batch and
  * bioik_solve_batch_multi read the offset before they take the lock), bioik_problem_destroy (wait for device-pointer solves on your own streams first; submitted
- * tickets are completed by it) and, process-wide, bioik_debug_reload_switches (diagnostics).  (tests/concurrency_cases.py) */
+ * tickets are completed by it) and, process-wide, bioik_debug_reload_switches (diagnostics).  (tests/concurrency_cases.py)
+ * bioik_problem_set_obstacles stands between the two groups: it takes the handle's lock, completes the handle's submitted tickets and waits for the handle's own streams
+ * before it copies, so it is safe beside every call of the first group -- but a device-pointer solve that is still RUNNING on one of the caller's own streams is the
+ * caller's to wait for first (the library does not know those streams): such a solve may read rows of either table.  bioik_problem_obstacle_count takes the lock too. */
 
 /* The same solve without waiting for it — for a caller with a STREAM of batches, the batched counterpart of calling
  * IKParallel::solve() from several threads (reference src/ik_parallel.h:193-218 keeps its own worker threads busy the same way).
@@ -432,7 +477,9 @@ int bioik_solve_batch_multi(bioik_problem* const* problems, int n_problems, cons
  * share a buffer must not overlap: launch them on one stream, or wait for one before launching the next (or capture from different streams).
  * The one eager call before a capture must take the same plan as the captured call -- the same queries, islands, mode, population and steps,
  * under the same BIOIK_SOLVE_* switches: a call in one launch sizes other scratch than one with hand-overs.  Destroy the graphs before the
- * handle.  A call with island_migration > 0 that would migrate (more than one island, E < max_steps) is NOT capturable: BIOIK_ERR_UNSUPPORTED on a capturing stream. */
+ * handle.  A problem with a BIOIK_GOAL_CLEARANCE: the captured kernels read the goal's obstacle table and its row count from the handle's device memory at every replay, so a
+ * replay runs with WHATEVER TABLE IS CURRENT (bioik_problem_set_obstacles between two replays takes effect; wait for a replay before changing the table).
+ * A call with island_migration > 0 that would migrate (more than one island, E < max_steps) is NOT capturable: BIOIK_ERR_UNSUPPORTED on a capturing stream. */
 int bioik_solve_batch_device(bioik_problem* p, const bioik_solve_params* params, size_t n, const double* d_seeds,
                              const double* d_goal_params, double* d_solutions, double* d_fitness,
                              int32_t* d_success, int32_t* d_steps, void* hip_stream);
