@@ -23,13 +23,14 @@ JOINT_VAR_COUNT = {JOINT_FIXED: 0, JOINT_REVOLUTE: 1, JOINT_PRISMATIC: 1, JOINT_
  GOAL_AVOID_JOINT_LIMITS, GOAL_CENTER_JOINTS, GOAL_REGULARIZATION, GOAL_MINIMAL_DISPLACEMENT, GOAL_JOINT_VARIABLE,
  GOAL_SIDE, GOAL_DIRECTION, GOAL_CONE, GOAL_BALANCE, GOAL_TOUCH) = range(18)
 GOAL_CLEARANCE = 19  # (18 is no opcode: bioik_goal_param_count(18) == -1)
-MAX_OBSTACLES = 256  # BIOIK_MAX_OBSTACLES: obstacle spheres one ClearanceGoal may hold
+GOAL_SELF_CLEARANCE = 20  # two links of the robot keep apart: the second link travels in bioik_problem_desc::goal_base_link
+MAX_OBSTACLES = 256  # BIOIK_MAX_OBSTACLES: obstacle spheres one ClearanceGoal may hold; the other link's spheres of a SelfClearanceGoal
 MAX_TOUCH_POINTS = 1024  # BIOIK_MAX_TOUCH_POINTS: collision points one TouchGoal may read
 MAX_HELD_FRAMES = 4  # BIOIK_MAX_HELD_FRAMES: distinct links whose frame the based goals of a problem need held across a walk
 GOAL_PARAM_COUNT = {GOAL_POSITION: 3, GOAL_ORIENTATION: 4, GOAL_POSE: 8, GOAL_LOOK_AT: 6, GOAL_MAX_DISTANCE: 4,
                     GOAL_MIN_DISTANCE: 4, GOAL_LINE: 6, GOAL_PLANE: 6, GOAL_AVOID_JOINT_LIMITS: 0, GOAL_CENTER_JOINTS: 0,
                     GOAL_REGULARIZATION: 0, GOAL_MINIMAL_DISPLACEMENT: 0, GOAL_JOINT_VARIABLE: 1, GOAL_SIDE: 6,
-                    GOAL_DIRECTION: 6, GOAL_CONE: 11, GOAL_BALANCE: 6, GOAL_TOUCH: 6, GOAL_CLEARANCE: 1}
+                    GOAL_DIRECTION: 6, GOAL_CONE: 11, GOAL_BALANCE: 6, GOAL_TOUCH: 6, GOAL_CLEARANCE: 1, GOAL_SELF_CLEARANCE: 1}
 
 # ---- solver modes (IKFactory names, reference src/ik_evolution_2.cpp:652-654) ----
 MODE_BIO2, MODE_BIO2_MEMETIC, MODE_BIO2_MEMETIC_L, MODE_GD_C, MODE_JAC, MODE_GD, MODE_GD_R = 0, 1, 2, 3, 4, 5, 6

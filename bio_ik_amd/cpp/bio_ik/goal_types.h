@@ -488,6 +488,30 @@ public:
     const std::vector<double>* gpuObstacles() const override { return &obstacles_; }
 };
 
+// SelfClearanceGoal (no reference counterpart; include/bioik_hip.h: BIOIK_GOAL_SELF_CLEARANCE): the spheres of the link keep at least `margin` away from the spheres
+// of ANOTHER link of the same robot -- self-collision between two links.  The other link is the goal's base link (BASE LINKS): describe() adds both links, and the
+// cost is ClearanceGoal's on R = concat(inverse(other), link) with the other link's collision points as the obstacle table.  Both tables are the robot model's.
+class SelfClearanceGoal : public LinkGoalBase {
+    double margin_;
+
+public:
+    SelfClearanceGoal() : margin_(0.0) {}
+    SelfClearanceGoal(const std::string& link_name, const std::string& other_link, double margin = 0.0, double weight = 1.0) : LinkGoalBase(link_name, weight), margin_(margin) {
+        setBaseLinkName(other_link);
+    }
+    double getMargin() const { return margin_; }
+    void setMargin(double m) { margin_ = m; }
+    void setOtherLinkName(const std::string& n) { setBaseLinkName(n); }
+    const std::string& getOtherLinkName() const { return getBaseLinkName(); }
+    // (reads both frames and both links' points: the hybrid path scores candidates with it)
+    double evaluate(const GoalContext& context) const override {
+        if (getBaseLinkName().empty()) return 0.0;  // (no other link: the device refuses such a goal)
+        return ClearanceGoal::cost(goalFrame(context), margin_, context.getLinkPoints(0), context.getLinkPoints(1));
+    }
+    int gpuOpcode() const override { return BIOIK_GOAL_SELF_CLEARANCE; }
+    void gpuParams(std::vector<double>& o) const override { o.push_back(margin_); }
+};
+
 class BalanceGoal : public Goal {  // goal_types.h:540-566, goal_types.cpp:231-272
     Vector3 target_, axis_;
 

@@ -63,6 +63,7 @@ int goal_param_count(int type) {
         case BIOIK_GOAL_BALANCE: return 6;
         case BIOIK_GOAL_TOUCH: return 6;
         case BIOIK_GOAL_CLEARANCE: return 1;  // (18 is no opcode: include/bioik_hip.h)
+        case BIOIK_GOAL_SELF_CLEARANCE: return 1;
     }
     return -1;
 }
@@ -232,7 +233,8 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         double weight;
         int secondary, param_off;
         int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them.  ClearanceGoal: its points, and in
-                                                   // disk_count the first row of its obstacle block
+                                                   // disk_count the first row of its obstacle block.  SelfClearanceGoal: the first row of its block (its link's rows, directly
+                                                   // behind them the other link's), in point_count its link's rows, in disk_count the other link's
         int base_tip;                              // a based goal (bioik_problem_desc::goal_base_link): the public tip of its base link, else -1
     };
     std::vector<G> goals;
@@ -247,6 +249,8 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             if (g.link >= nl) throw Error(BIOIK_ERR_NOT_FOUND, "link not found");
             info.tip = add_tip_link(g.link);
         }
+        if (g.type == BIOIK_GOAL_SELF_CLEARANCE && !(goal_base_link && goal_base_link[gi] >= 0))  // (the other link is part of the goal, not an option)
+            throw Error(BIOIK_ERR_INVALID_ARGUMENT, "goal " + std::to_string(gi) + ": a SelfClearanceGoal needs its other link in bioik_problem_desc::goal_base_link (none given: the field is NULL, -1 or behind struct_size)");
         if (goal_base_link && goal_base_link[gi] >= 0) {  // BASE LINKS (include/bioik_hip.h): the goal reads its link's frame in the base link's
             const int base = goal_base_link[gi];
             const std::string who = "goal " + std::to_string(gi) + ": ";
@@ -298,6 +302,32 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             info.disk_count = (int)(touch_points.size() / 4);  // (DevGoal::pad: the first row of the obstacle block -- its count row, all zero bits: no obstacle)
             touch_points.insert(touch_points.end(), (size_t)(1 + BIOIK_MAX_OBSTACLES) * 4, 0.0);
             clearance_block.back() = info.disk_count;
+        }
+        if (g.type == BIOIK_GOAL_SELF_CLEARANCE) {  // the spheres of the goal's link and directly behind them those of the other link, both as the points the model was given
+            const std::string who = "goal " + std::to_string(gi) + ": SelfClearanceGoal: ";
+            const int links[2] = {g.link, goal_base_link[gi]};  // (both checked above: a link, a base that is another link)
+            const int caps[2] = {BIOIK_MAX_TOUCH_POINTS, BIOIK_MAX_OBSTACLES};
+            const char* const names[2] = {"the goal's link", "the other link"};
+            const char* const cap_names[2] = {"BIOIK_MAX_TOUCH_POINTS", "BIOIK_MAX_OBSTACLES"};
+            int counts[2];
+            for (int k = 0; k < 2; k++) {
+                const int first = m->point_first[links[k]], count = m->point_first[links[k] + 1] - first;
+                for (int i = 0; i < count; i++)
+                    if (m->points[(size_t)(first + i) * 4 + 3] < 0.0)
+                        throw Error(BIOIK_ERR_UNSUPPORTED, who + "a row of " + names[k] + " in bioik_model_desc::link_points has the radius -1, the marker of a shape that is no "
+                                                               "set of spheres (a mesh without its vertices, a cylinder or a cone left as it was): no device implementation, not approximated");
+                if (m->disk_first[links[k] + 1] - m->disk_first[links[k]] > 0)
+                    throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " carries disks (bioik_model_desc::link_disks: a cylinder or a cone); only spheres have a device implementation, not approximated");
+                if (count <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + names[k] + " has no collision points (bioik_model_desc::link_points)");
+                if (count > caps[k])
+                    throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " has more than " + cap_names[k] + " (" + std::to_string(caps[k]) + ") collision points");
+                counts[k] = count;
+            }
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = counts[0], info.disk_count = counts[1];
+            for (int k = 0; k < 2; k++) {
+                const int first = m->point_first[links[k]];
+                touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + counts[k]) * 4);
+            }
         }
         if (g.type == BIOIK_GOAL_BALANCE) {  // BalanceGoal::describe (goal_types.cpp:231-255): every link with mass becomes a tip, in link order
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, "BalanceGoal cannot be a secondary goal (the reference's has no such constructor)");
@@ -629,6 +659,8 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             else o.var_seed = (int)(-1 - g.var);
         }
         if (g.type == BIOIK_GOAL_TOUCH || g.type == BIOIK_GOAL_CLEARANCE) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
+        // SelfClearanceGoal (always based: var_op is taken below): var_seed = the first row of its block in touch_points, pad = rows of its link | rows of the other link << 16 (bioik_types.h)
+        if (g.type == BIOIK_GOAL_SELF_CLEARANCE) o.var_seed = g.point_first, o.pad = g.point_count | (g.disk_count << 16);
         if (g.base_tip >= 0 && g.tip >= 0) {  // var_op <= -2 marks a based goal (a link goal reads no variable): -2 - (held tip * 2 + "the held frame is the goal's own link's")
             const int own = dev.tip_of_out[g.tip], base = dev.tip_of_out[g.base_tip];
             o.tip = std::max(own, base);

@@ -21,7 +21,7 @@
 enum {
     G_POSITION = 0, G_ORIENTATION = 1, G_POSE = 2, G_LOOK_AT = 3, G_MAX_DISTANCE = 4, G_MIN_DISTANCE = 5, G_LINE = 6,
     G_PLANE = 7, G_AVOID_JOINT_LIMITS = 8, G_CENTER_JOINTS = 9, G_REGULARIZATION = 10, G_MINIMAL_DISPLACEMENT = 11,
-    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15, G_TOUCH = 17, G_CLEARANCE = 19
+    G_JOINT_VARIABLE = 12, G_SIDE = 13, G_DIRECTION = 14, G_CONE = 15, G_TOUCH = 17, G_CLEARANCE = 19, G_SELF_CLEARANCE = 20
 };
 enum { FK_LINEAR = 0, FK_EXACT = 1 };
 
@@ -726,6 +726,66 @@ BIOIK_CALL double based_goal_cost(int type, int var_op, const lds_f64* P, F7 f, 
 BIOIK_CALL double based_goal_cost_slots(int type, int var_op, const lds_f64* P, const lds_f64* own, const lds_f64* slot, int nth) {
     return based_goal_cost_inl(type, var_op, P, slot_load(own, nth), slot_load(slot, nth));
 }
+// SelfClearanceGoal (include/bioik_hip.h: BIOIK_GOAL_SELF_CLEARANCE; no reference counterpart): the spheres (v_i, r_i) of the goal's link keep `margin` away from the
+// spheres (c_j, R_j) of another link of the same robot, read in that link's frame: a based goal whose frame is R = inv(other link) o link (based_frame_inl, as it
+// stands), and from w_i = R.p + rotate(R.q, v_i) on goal_eval_clearance's arithmetic word for word (clearance_pair; i outer, j inner, ascending, one running sum).
+// first: the first row of the goal's block in DevProblem::touch_points -- the n rows of its link and DIRECTLY behind them the m rows of the other link, both fixed
+// when the problem is created (no count word in memory, no obstacle block); counts = n | m << 16, n and m >= 1 (DevGoal::var_seed / pad, bioik_types.h).
+// Both tables wavefront-uniform: scalar loads, the numbers SGPR operands.  Two obstacles per trip as there, but the rows of trip k + 1 are REQUESTED IN FRONT OF the
+// arithmetic of trip k (goal_eval_clearance waits for its own load every trip), and the last trip of a point requests the first rows of the next point's first trip:
+// the index wraps to 0, so every request stays inside the block -- eight doubles where two rows are left, four where one is (the leftover row of an odd m, or m = 1).
+// Plain C++: the compiler is free to place the wait where the values are first needed, which is behind the arithmetic.  The same bits as a loop without it.
+// One out-of-line body (goal_eval_self_clearance) with two doors, like based_goal_cost / based_goal_cost_slots: the frames as values (the sites with a table of tip
+// frames) or as the lane's two slots (the exact walks).  A site that routes a based row sends type 20 here under a branch of its own and leaves the call of every
+// other based goal as it was.  (Tried and dropped: the problem pointer and the row's index as three more arguments of based_goal_cost_slots itself, the branch inside
+// it -- every based goal's call then pays them, and k_solve grew by 26 spilled VGPRs and 51 KB of code where this form costs 2 and 20 KB.)
+// Reached only from the general kernel flavour.
+BIOIK_CALL double goal_eval_self_clearance(ProbPtr pb_, int first, int counts, double margin, F7 r) {
+    const unsigned long long pba = (unsigned long long)pb_;
+    const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
+    const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * p_uniform(first));
+    const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
+    const int nm = p_uniform(counts);
+    int n = nm & 0xffff, m = (nm >> 16) & 0xffff;
+    n = n > BIOIK_DEV_MAX_TOUCH_POINTS ? BIOIK_DEV_MAX_TOUCH_POINTS : n;  // (never beyond what the problem compiler can have laid out, whatever the word holds)
+    m = m > BIOIK_DEV_MAX_OBSTACLES ? BIOIK_DEV_MAX_OBSTACLES : m;
+    if (n == 0 || m == 0) return 0.0;
+    const UniformF64 o = v + 4 * n;
+    double sum = 0.0;
+    // the rows of the trip at hand (a: two rows, or one in a0 ... a3) and of the one behind it (b)
+    double a0 = o[0], a1 = o[1], a2 = o[2], a3 = o[3], a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
+    if (m >= 2) a4 = o[4], a5 = o[5], a6 = o[6], a7 = o[7];
+    for (int i = 0; i < n; i++) {
+        const UniformF64 pt = v + 4 * i;
+        const V3 w = r.p + qrot(r.q, v3(pt[0], pt[1], pt[2]));
+        const double sm = margin + pt[3];
+        int j = 0;
+        for (; j + 2 <= m; j += 2) {
+            const int jn = j + 2 < m ? j + 2 : 0;  // (the next trip's first row: the leftover row, or back to row 0 for the next point)
+            const UniformF64 c = o + 4 * jn;
+            const double b0 = c[0], b1 = c[1], b2 = c[2], b3 = c[3];
+            double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+            if (jn + 2 <= m) b4 = c[4], b5 = c[5], b6 = c[6], b7 = c[7];
+            sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
+            sum = clearance_pair(sum, w, sm, a4, a5, a6, a7);
+            a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+        }
+        if (j < m) {  // the leftover row is at hand in a0 ... a3; behind it row 0 again
+            const double b0 = o[0], b1 = o[1], b2 = o[2], b3 = o[3];
+            double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+            if (m >= 2) b4 = o[4], b5 = o[5], b6 = o[6], b7 = o[7];
+            sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
+            a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+        }
+    }
+    return sum;
+}
+BIOIK_CALL double self_clearance_cost(ProbPtr pb, int first, int counts, int var_op, const lds_f64* P, F7 f, F7 held) {
+    return goal_eval_self_clearance(pb, first, counts, P[0], based_frame_inl(var_op, f, held));
+}
+BIOIK_CALL double self_clearance_cost_slots(ProbPtr pb, int first, int counts, int var_op, const lds_f64* P, const lds_f64* own, const lds_f64* slot, int nth) {
+    return goal_eval_self_clearance(pb, first, counts, P[0], based_frame_inl(var_op, slot_load(own, nth), slot_load(slot, nth)));
+}
 BIOIK_DEV void slot_store(double* sl, int nth, const F7& f) {
     sl[0] = f.p.x, sl[(size_t)nth] = f.p.y, sl[(size_t)2 * nth] = f.p.z;
     sl[(size_t)3 * nth] = f.q.x, sl[(size_t)4 * nth] = f.q.y, sl[(size_t)5 * nth] = f.q.z, sl[(size_t)6 * nth] = f.q.w;
@@ -745,8 +805,12 @@ struct HeldSlots {
     const double* slots_of_child;
     BIOIK_DEV const double* slot(int ht) const { return slots_of_child + (size_t)(pb->tips[ht].pad0 - 1) * 7 * p_nthreads() + p_tid_fresh(); }
     BIOIK_DEV F7 operator()(int ht) const { return slot_load(slot(ht), p_nthreads()); }
-    // t: the tip the goal sits at (the walk has parked its frame too, bioik_compile.cpp)
-    BIOIK_DEV double cost(int type, int var_op, const double* P, int t) const {
+    // t: the tip the goal sits at (the walk has parked its frame too, bioik_compile.cpp); g: the goal's row in DevProblem::primary (a SelfClearanceGoal reads its tables' place there)
+    BIOIK_DEV double cost(int type, int var_op, const double* P, int t, int g) const {
+        if constexpr (pb_flavour<PB>::general) {
+            if (type == G_SELF_CLEARANCE)
+                return self_clearance_cost_slots(pb, pb->primary[g].var_seed, pb->primary[g].pad, var_op, (const lds_f64*)P, (const lds_f64*)slot(t), (const lds_f64*)slot(based_held_tip(var_op)), p_nthreads());
+        }
         return based_goal_cost_slots(type, var_op, (const lds_f64*)P, (const lds_f64*)slot(t), (const lds_f64*)slot(based_held_tip(var_op)), p_nthreads());
     }
 };
@@ -754,9 +818,10 @@ template <class Held, class = void>
 struct held_in_slots : std::false_type {};
 template <class PB>
 struct held_in_slots<HeldSlots<PB>> : std::true_type {};
-template <class Held>
-BIOIK_DEV double based_cost(const Held& held, int type, int var_op, const double* P, const F7& f, int t) {
-    if constexpr (held_in_slots<Held>::value) return held.cost(type, var_op, P, t);
+template <class PB, class Held>
+BIOIK_DEV double based_cost(PB pb, const Held& held, int g, int type, int var_op, const double* P, const F7& f, int t) {
+    if constexpr (held_in_slots<Held>::value) return held.cost(type, var_op, P, t, g);
+    else if (type == G_SELF_CLEARANCE) return self_clearance_cost(pb, pb->primary[g].var_seed, pb->primary[g].pad, var_op, (const lds_f64*)P, f, held(based_held_tip(var_op)));
     else return based_goal_cost(type, var_op, (const lds_f64*)P, f, held(based_held_tip(var_op)));
 }
 struct HeldNone {  // the sites that evaluate goals without a link (null frames): no row there is based
@@ -779,7 +844,7 @@ BIOIK_DEV double tip_goals(PB pb, int t, const F7& f, const XA& x, const QueryCt
         if constexpr (pb_flavour<PB>::general) {
             const int vo = pb->primary[g].var_op;
             if (vo < -1) {
-                sum += based_cost(held, pb->primary[g].type, vo, qc.par + pb->primary[g].param_off, f, t) * pb->primary[g].weight_sq;
+                sum += based_cost(pb, held, g, pb->primary[g].type, vo, qc.par + pb->primary[g].param_off, f, t) * pb->primary[g].weight_sq;
                 continue;
             }
         }
@@ -1312,7 +1377,7 @@ BIOIK_DEV void eval_exact_primary_n(PB pb, const XA (&x)[N], const QueryCtx& qc,
                 if (var_op < -1) {  // a based goal: R from the frame this child's walk has held (BASE LINKS)
 #pragma unroll
                     for (int j = 0; j < N; j++)
-                        out[j] += HeldSlots<PB>{pb, slots + (size_t)j * slot_set_stride}.cost(type, var_op, P, t) * w;
+                        out[j] += HeldSlots<PB>{pb, slots + (size_t)j * slot_set_stride}.cost(type, var_op, P, t, g) * w;
                     continue;
                 }
             }
@@ -1900,7 +1965,7 @@ BIOIK_DEV bool check_goal(PB pb, int g, const F7& f_tip, const XV& x, const Quer
         if (vo < -1) {
             if (type != G_POSITION && type != G_ORIENTATION && type != G_POSE) {
                 const double dmax = fmin(BIOIK_DBL_MAX, fmin(p_fresh(dpos), dtwist));
-                const double d = based_cost(held, type, vo, P, f_tip, pb->primary[g].tip) * pb->primary[g].weight_sq;
+                const double d = based_cost(pb, held, g, type, vo, P, f_tip, pb->primary[g].tip) * pb->primary[g].weight_sq;
                 return d < dmax * dmax;
             }
             fb = based_frame(vo, f_tip, held(based_held_tip(vo)));

@@ -25,7 +25,7 @@
 static_assert((int)G_POSITION == (int)BIOIK_GOAL_POSITION && (int)G_POSE == (int)BIOIK_GOAL_POSE && (int)G_CONE == (int)BIOIK_GOAL_CONE &&
                   (int)G_JOINT_VARIABLE == (int)BIOIK_GOAL_JOINT_VARIABLE && (int)G_MINIMAL_DISPLACEMENT == (int)BIOIK_GOAL_MINIMAL_DISPLACEMENT &&
                   (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS && (int)G_TOUCH == (int)BIOIK_GOAL_TOUCH && (int)G_CLEARANCE == (int)BIOIK_GOAL_CLEARANCE &&
-                  BIOIK_DEV_MAX_OBSTACLES == BIOIK_MAX_OBSTACLES,
+                  (int)G_SELF_CLEARANCE == (int)BIOIK_GOAL_SELF_CLEARANCE && BIOIK_DEV_MAX_OBSTACLES == BIOIK_MAX_OBSTACLES && BIOIK_DEV_MAX_TOUCH_POINTS == BIOIK_MAX_TOUCH_POINTS,
               "goal opcodes out of sync with include/bioik_hip.h");
 static_assert((int)FK_LINEAR == (int)BIOIK_FK_LINEAR && (int)FK_EXACT == (int)BIOIK_FK_EXACT, "fk modes out of sync");
 
@@ -351,7 +351,7 @@ struct bioik_problem {
     bioik_model* model;
     bioik::HostProblem host;
     DevProblem* d_pb = nullptr;
-    double* d_touch = nullptr;  // DevProblem::touch_points: the collision points the problem's TouchGoals read, the points and obstacle blocks of its ClearanceGoals (null without either)
+    double* d_touch = nullptr;  // DevProblem::touch_points: the collision points the problem's TouchGoals read, the points and obstacle blocks of its ClearanceGoals, the rows of both links of its SelfClearanceGoals (null without any)
     // Host-pointer solves (bioik_solve_batch, bioik_solve_batch_submit / _wait) go through one of kIoSlots slots, each with a grow-only
     // device arena, its page-locked host mirror (one DMA in, one DMA out per solve) and its own stream: up to kIoSlots batches of one
     // handle are in flight together, the tail of one solve behind the bulk of the next.  Streams are created at a

@@ -85,6 +85,10 @@ struct DevGoal {
 // ClearanceGoal: an obstacle block is 1 + BIOIK_DEV_MAX_OBSTACLES rows of four doubles in DevProblem::touch_points -- row 0: the number of obstacles, an int32 in its first
 // four bytes; rows 1 ...: cx cy cz R, world frame.  Laid out once by bioik_problem_create, rewritten in place by bioik_problem_set_obstacles (= BIOIK_MAX_OBSTACLES, include/bioik_hip.h)
 #define BIOIK_DEV_MAX_OBSTACLES 256
+// SelfClearanceGoal (always a based goal: var_op holds the based encoding): var_seed = the first row of its block in DevProblem::touch_points -- the n rows x y z r of its own
+// link and directly behind them the m rows of the other link, each in its link's frame, fixed when the problem is created (no count word, no obstacle block) -- and
+// pad = n | m << 16, 1 <= n <= BIOIK_DEV_MAX_TOUCH_POINTS (= BIOIK_MAX_TOUCH_POINTS), 1 <= m <= BIOIK_DEV_MAX_OBSTACLES
+#define BIOIK_DEV_MAX_TOUCH_POINTS 1024
 
 struct DevProblem {
     // the scalars one code site reads together sit in one 16-byte group, so that they arrive with one scalar load
@@ -129,7 +133,7 @@ struct DevProblem {
     DevGoal balance[BIOIK_MAX_BALANCE];  // params: target[3] axis[3]
     // TouchGoals: the collision points (x y z r, link frame) of the links they name and behind each goal's points its disks (cx cy cz r ax ay az 0: the
     // ends of cylinders, the bases of cones), goal after goal, in a buffer of global memory that the problem handle owns (null without such a goal).  ClearanceGoals:
-    // their points and their obstacle blocks (above) in the same buffer.  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
+    // their points and their obstacle blocks (above) in the same buffer; SelfClearanceGoals: the rows of their two links.  Every lane reads the same point at the same time: scalar loads, like the rest of this block.
     const double* touch_points;
 };
 

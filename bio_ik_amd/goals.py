@@ -332,6 +332,57 @@ class ClearanceGoal(LinkGoalBase):
         return float((pen * pen).sum())
 
 
+class SelfClearanceGoal(LinkGoalBase):
+    """No reference counterpart (include/bioik_hip.h: BIOIK_GOAL_SELF_CLEARANCE): the spheres of the link -- its collision points of the robot model, each with its
+    radius -- keep at least `margin` away from the spheres of ANOTHER link of the same robot.  The other link is the goal's base link (BASE LINKS): the cost is
+    ClearanceGoal's, read in the other link's frame R = inverse(other) o link, with the other link's points as the obstacle table.  Both tables are the model's: the
+    goal carries the two names and the margin (a per-query parameter)."""
+    opcode = abi.GOAL_SELF_CLEARANCE
+
+    def __init__(self, link_name="", other_link="", margin=0.0, weight=1.0):
+        super().__init__(link_name, weight, other_link)
+        self.margin_ = float(margin)
+
+    def getMargin(self):
+        return self.margin_
+
+    def setMargin(self, m):
+        self.margin_ = float(m)
+
+    def setOtherLinkName(self, n):
+        self.setBaseLinkName(n)
+
+    def getOtherLinkName(self):
+        return self.getBaseLinkName()
+
+    def params(self):
+        return np.array([self.margin_])
+
+    def evaluate(self, frame, other_frame, points, other_points):
+        """The cost on the host: frame / other_frame = the link's and the other link's px py pz qx qy qz qw, points [n][4] / other_points [m][4] =
+        RobotModel.collision_points of the two.  The device's formula in numpy (plain multiplications and additions where the device fuses them: equal up to
+        rounding); quaternions as they are, not normalised."""
+        b, a = np.asarray(frame, dtype=np.float64), np.asarray(other_frame, dtype=np.float64)
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        obs = np.asarray(other_points, dtype=np.float64).reshape(-1, 4)
+        if obs.shape[0] == 0 or pts.shape[0] == 0:
+            return 0.0
+
+        def rotate(q, v):  # v + 2 (w (u x v) + u x (u x v))
+            t = np.cross(q[:3], v)
+            return v + 2.0 * (q[3] * t + np.cross(q[:3], t))
+
+        def mul(p, q):
+            return np.append(p[3] * q[:3] + q[3] * p[:3] + np.cross(p[:3], q[:3]), p[3] * q[3] - p[:3] @ q[:3])
+        c = a[3:] * np.array([-1.0, -1.0, -1.0, 1.0])  # R = concat(invert(A), B)
+        rp, rq = rotate(c, -a[:3]) + rotate(c, b[:3]), mul(c, b[3:])
+        centres = rp[None] + np.array([rotate(rq, v) for v in pts[:, :3]])
+        s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
+        d = np.linalg.norm(centres[:, None, :] - obs[None, :, :3], axis=2)
+        pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
+        return float((pen * pen).sum())
+
+
 class _JointSetGoal(Goal):
     def __init__(self, weight=1.0, secondary=True):
         super().__init__()

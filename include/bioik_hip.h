@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: BIOIK_GOAL_CLEARANCE (opcode 19; 18 stays unknown), BIOIK_MAX_OBSTACLES, bioik_problem_set_obstacles,
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: BIOIK_GOAL_SELF_CLEARANCE (opcode 20: the spheres of two links of the robot keep apart; the second link in goal_base_link).
+                               6, additions that break no caller of 6: BIOIK_GOAL_CLEARANCE (opcode 19; 18 stays unknown), BIOIK_MAX_OBSTACLES, bioik_problem_set_obstacles,
                                bioik_problem_obstacle_count (a link's spheres keep clear of a table of obstacle spheres).
                                6, additions that break no caller of 6: bioik_problem_desc::goal_base_link behind the fields every caller of 6 fills (a shorter struct_size gets none),
                                BIOIK_MAX_HELD_FRAMES (BASE LINKS: a link goal evaluated in another link's frame).
@@ -130,6 +131,32 @@ enum {
                                             BIOIK_ERR_UNSUPPORTED.  About nine FP64 issue slots per pair that does not penetrate and eighteen per point (counted in the
                                             code, not timed): 8 points against 16 obstacles cost about as much as the chain walk of a 7-joint arm
                                             (measured rates: profiles/clearance_goal_metadata_and_bench.log) */
+    ,
+    BIOIK_GOAL_SELF_CLEARANCE = 20       /* no reference counterpart (there: a solution_callback behind the search).  params: margin.  SELF-COLLISION BETWEEN TWO LINKS: the
+                                            spheres of the goal's link L keep at least `margin` away from the spheres of a second link O of the same robot (the "other"
+                                            link), which bioik_problem_desc::goal_base_link[g] names -- for this opcode the field is REQUIRED.  L's rows (v_i, r_i), i < n, and
+                                            O's rows (c_j, R_j), j < m, both of bioik_model_desc::link_points, each in its own link's frame; both tables are known when the
+                                            problem is created (no bioik_problem_set_obstacles table, no count word in device memory).  With A = O's frame and B = L's
+                                            frame of the same individual:
+                                                R    = concat(invert(A), B)          exactly the R of BASE LINKS below, in its order of operations: nothing normalised, the
+                                                                                     phenotypes of BIOIK_FK_LINEAR included
+                                                w_i  = R.p + rotate(R.q, v_i)        L's sphere centres in O's frame
+                                                s_ij = (margin + r_i) + R_j
+                                                pen  = s_ij > 0 ? max(0, s_ij - |w_i - c_j|) : 0
+                                                cost = sum_i sum_j pen^2             i outer, j inner, both ascending, one running sum from 0
+                                            From w_i on the operations, their order, the fused ones and the exact test in front of the root (s > 0 && d2 < s s) are those of
+                                            BIOIK_GOAL_CLEARANCE above, word for word, with (R.p, R.q) in place of (p, q).  Success test: the default branch of every non-pose
+                                            link goal, weighted cost < min(dpos, dtwist)^2, on R.  jac, gd*, ranked, bounded, migration, timeout and island_sync behave as
+                                            for any problem with a based goal: BIOIK_MODE_JAC is refused at the solve call.  The goal (L, O) and the goal (O, L) state the
+                                            same distances and differ in the order of summation: equal up to rounding, not bit for bit.
+                                            Refused by bioik_problem_create, the message naming the goal's index: no other link (-1, a NULL goal_base_link, a struct_size
+                                            that ends in front of the field), a goal that names no link, the other link the goal's own, either link without points:
+                                            BIOIK_ERR_INVALID_ARGUMENT; either link with disks or a marker row (r == -1: never approximated), L with more than
+                                            BIOIK_MAX_TOUCH_POINTS points, O with more than BIOIK_MAX_OBSTACLES, a secondary goal, more than BIOIK_MAX_HELD_FRAMES held
+                                            links: BIOIK_ERR_UNSUPPORTED; an unknown other link: BIOIK_ERR_NOT_FOUND.  bioik_problem_set_obstacles and
+                                            bioik_problem_obstacle_count say "not a CLEARANCE goal" of it.  Such a problem runs in the general kernel flavour.  Not built:
+                                            capsules, a broad phase, pairs taken automatically from an SRDF's collision matrix
+                                            (measured: profiles/self_clearance_metadata_and_bench.log) */
     /* JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
 };
 /* Obstacle spheres one BIOIK_GOAL_CLEARANCE may hold (every evaluation of every individual reads all of them against every point of the link). */
@@ -260,7 +287,8 @@ typedef struct bioik_goal_desc {
  * Refused by bioik_problem_create: base >= n_links BIOIK_ERR_NOT_FOUND; a base on a goal without a link, or equal to the goal's own link: BIOIK_ERR_INVALID_ARGUMENT;
  * a base on a secondary goal (secondary link goals read the null frame, ik_base.h:163: it would be a constant), on BIOIK_GOAL_TOUCH or BIOIK_GOAL_BALANCE, or more
  * than BIOIK_MAX_HELD_FRAMES distinct held links: BIOIK_ERR_UNSUPPORTED.  Refused by every solve entry: BIOIK_MODE_JAC on a problem with a based goal,
- * BIOIK_ERR_UNSUPPORTED (its tip objectives are world poses, ik_gradient.cpp:64-66; gd, gd_r, gd_c minimise the fitness and work). */
+ * BIOIK_ERR_UNSUPPORTED (its tip objectives are world poses, ik_gradient.cpp:64-66; gd, gd_r, gd_c minimise the fitness and work).
+ * BIOIK_GOAL_SELF_CLEARANCE reads the same R with its base link as the OTHER link, and for it the field is required (a base on BIOIK_GOAL_CLEARANCE stays refused). */
 #define BIOIK_MAX_HELD_FRAMES 4
 
 /* ---- problem template = the arguments of Problem::initialize (reference src/problem.cpp:72-228)
