@@ -26,6 +26,7 @@ GOAL_CLEARANCE = 19  # (18 is no opcode: bioik_goal_param_count(18) == -1)
 GOAL_SELF_CLEARANCE = 20  # two links of the robot keep apart: the second link travels in bioik_problem_desc::goal_base_link
 MAX_OBSTACLES = 256  # BIOIK_MAX_OBSTACLES: obstacle spheres one ClearanceGoal may hold; the other link's spheres of a SelfClearanceGoal
 MAX_TOUCH_POINTS = 1024  # BIOIK_MAX_TOUCH_POINTS: collision points one TouchGoal may read
+MAX_LINK_CAPSULES = 64  # BIOIK_MAX_LINK_CAPSULES: capsules one goal may read from one link
 MAX_HELD_FRAMES = 4  # BIOIK_MAX_HELD_FRAMES: distinct links whose frame the based goals of a problem need held across a walk
 GOAL_PARAM_COUNT = {GOAL_POSITION: 3, GOAL_ORIENTATION: 4, GOAL_POSE: 8, GOAL_LOOK_AT: 6, GOAL_MAX_DISTANCE: 4,
                     GOAL_MIN_DISTANCE: 4, GOAL_LINE: 6, GOAL_PLANE: 6, GOAL_AVOID_JOINT_LIMITS: 0, GOAL_CENTER_JOINTS: 0,
@@ -51,7 +52,8 @@ class ModelDesc(C.Structure):
                 ("joint_mimic_offset", _pd), ("var_min", _pd), ("var_max", _pd), ("var_bounded", _pu8),
                 ("var_max_velocity", _pd), ("link_mass", _pd), ("link_center", _pd),
                 ("link_point_first", _pi), ("link_points", _pd),  # (collision points for TouchGoal; a struct_size that ends in front of them is accepted)
-                ("link_disk_first", _pi), ("link_disks", _pd)]  # (collision disks for TouchGoal: the ends of cylinders, the bases of cones; likewise)
+                ("link_disk_first", _pi), ("link_disks", _pd),  # (collision disks for TouchGoal: the ends of cylinders, the bases of cones; likewise)
+                ("link_capsule_first", _pi), ("link_capsules", _pd)]  # (collision capsules ax ay az r bx by bz 0 for ClearanceGoal, SelfClearanceGoal, TouchGoal; likewise)
 
 
 class GoalDesc(C.Structure):

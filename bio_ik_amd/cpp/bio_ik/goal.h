@@ -53,6 +53,7 @@ protected:
     const RobotInfo* robot_info_ = nullptr;
     mutable std::vector<double> temp_vector_;
     std::vector<const std::vector<double>*> goal_link_points_;  // per link of the goal: its collision points x y z r in the link frame (TouchGoal), or null
+    std::vector<const std::vector<double>*> goal_link_capsules_;  // per link of the goal: its collision capsules ax ay az r bx by bz 0 in the link frame, or null
     std::vector<const std::vector<double>*> goal_link_disks_;   // per link of the goal: its collision disks cx cy cz r ax ay az 0 in the link frame (TouchGoal), or null
 
 public:
@@ -66,6 +67,11 @@ public:
     const std::vector<double>& getLinkDisks(size_t i = 0) const {
         static const std::vector<double> none;
         return i < goal_link_disks_.size() && goal_link_disks_[i] ? *goal_link_disks_[i] : none;
+    }
+    // the collision capsules of the goal's i-th link (a segment's two ends and a radius), rows ax ay az r bx by bz 0 in the link frame
+    const std::vector<double>& getLinkCapsules(size_t i = 0) const {
+        static const std::vector<double> none;
+        return i < goal_link_capsules_.size() && goal_link_capsules_[i] ? *goal_link_capsules_[i] : none;
     }
     const Frame& getLinkFrame(size_t i = 0) const { return tip_link_frames_[goal_link_indices_[i]]; }
     double getVariablePosition(size_t i = 0) const {

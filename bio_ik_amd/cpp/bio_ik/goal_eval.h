@@ -22,6 +22,7 @@ public:
         std::function<Frame(const std::string&, const std::vector<double>&)> link_frame;  // global frame of a link at a full variable vector
         std::function<const std::vector<double>*(const std::string&)> link_points;       // collision points x y z r of a link (TouchGoal, ClearanceGoal); may be empty
         std::function<const std::vector<double>*(const std::string&)> link_disks;        // collision disks cx cy cz r ax ay az 0 of a link (TouchGoal); may be empty
+        std::function<const std::vector<double>*(const std::string&)> link_capsules;     // collision capsules ax ay az r bx by bz 0 of a link (TouchGoal, ClearanceGoal, SelfClearanceGoal); may be empty
     };
 
 private:
@@ -60,6 +61,7 @@ public:
                 c.goal_link_indices_.push_back(t);
                 c.goal_link_points_.push_back(model_.link_points ? model_.link_points(name) : nullptr);
                 c.goal_link_disks_.push_back(model_.link_disks ? model_.link_disks(name) : nullptr);
+                c.goal_link_capsules_.push_back(model_.link_capsules ? model_.link_capsules(name) : nullptr);
             }
             for (auto& name : c.goal_variable_names_) {
                 const int ivar = model_.variable_index(name);

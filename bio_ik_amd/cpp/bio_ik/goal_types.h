@@ -404,7 +404,7 @@ public:
     const Vector3& getNormal() const { return normal; }
     // d = min(min_i (n_l . v_i - r_i), min_j (n_l . c_j - r_j |n_l x a_j|)) - normal . (position - p), n_l = the normal turned by the conjugate of the link's quaternion (tf2's inverse(), goal_types.cpp:170)
     static double distance(const Frame& fb, const Vector3& position, const Vector3& normal, const std::vector<double>& points,
-                           const std::vector<double>& disks = std::vector<double>()) {
+                           const std::vector<double>& disks = std::vector<double>(), const std::vector<double>& capsules = std::vector<double>()) {
         const Quaternion q = fb.getOrientation();
         // v + 2 (w t + u x t), t = u x v with u = -q.xyz: the quaternion as it is, unit or not (frame.h:108-149)
         const Vector3 u(-q.x(), -q.y(), -q.z());
@@ -419,10 +419,12 @@ public:
             const Vector3 rim = nl.cross(Vector3(disks[i + 4], disks[i + 5], disks[i + 6]));
             dmin = std::fmin(dmin, nl.x() * disks[i] + nl.y() * disks[i + 1] + nl.z() * disks[i + 2] - disks[i + 3] * std::sqrt(rim.dot(rim)));
         }
+        for (size_t i = 0; i + 8 <= capsules.size(); i += 8)  // a capsule's support is the smaller of its two end spheres' (exact): the device reads it as those two points
+            for (size_t e = 0; e < 8; e += 4) dmin = std::fmin(dmin, nl.x() * capsules[i + e] + nl.y() * capsules[i + e + 1] + nl.z() * capsules[i + e + 2] - capsules[i + 3]);
         return dmin - normal.dot(position - fb.getPosition());
     }
     double evaluate(const GoalContext& context) const override {
-        const double d = distance(context.getLinkFrame(), position, normal, context.getLinkPoints(), context.getLinkDisks());
+        const double d = distance(context.getLinkFrame(), position, normal, context.getLinkPoints(), context.getLinkDisks(), context.getLinkCapsules());
         return d * d;
     }
     int gpuOpcode() const override { return BIOIK_GOAL_TOUCH; }
@@ -459,6 +461,67 @@ public:
         rows.insert(rows.end(), {centre.x(), centre.y(), centre.z(), radius});
         setObstacles(rows);
     }
+    // CAPSULES (include/bioik_hip.h), restated on the host with plain multiplications and additions where the device fuses them: equal up to rounding
+    static Vector3 carry(const Frame& fb, const Vector3& v) {  // p + rotate(q, v), q as it is
+        const Quaternion q = fb.getOrientation();
+        const Vector3 u(q.x(), q.y(), q.z());
+        const Vector3 t = u.cross(v);
+        return fb.getPosition() + v + (t * q.w() + u.cross(t)) * 2.0;
+    }
+    static double clamp01(double x) { return std::fmin(std::fmax(x, 0.0), 1.0); }
+    static double segmentPointD2(const Vector3& a, const Vector3& b, const Vector3& c) {
+        const Vector3 u = b - a, e = c - a;
+        const double uu = u.dot(u), ru = uu > DBL_MIN ? 1.0 / uu : 0.0;
+        const Vector3 x = c - (a + u * clamp01(e.dot(u) * ru));
+        return x.dot(x);
+    }
+    static double segmentSegmentD2(const Vector3& a, const Vector3& b, const Vector3& c, const Vector3& d) {
+        const Vector3 u = b - a, v = d - c, w = a - c;
+        const double uu = u.dot(u), vv = v.dot(v), uv = u.dot(v), uw = u.dot(w), vw = v.dot(w);
+        const double ru = uu > DBL_MIN ? 1.0 / uu : 0.0, rv = vv > DBL_MIN ? 1.0 / vv : 0.0;
+        const double den = uu * vv - uv * uv;
+        double s = den > 0.0 ? clamp01((uv * vw - vv * uw) / den) : 0.0;
+        const double t = (uv * s + vw) * rv, tc = clamp01(t);
+        if (tc != t || rv == 0.0) s = clamp01((uv * tc - uw) * ru);
+        const Vector3 x = (a + u * s) - (c + v * tc);
+        return x.dot(x);
+    }
+    static double tail(double sum, double s, double d2) {
+        if (s > 0 && d2 < s * s) {
+            const double pen = std::fmax(0.0, s - std::sqrt(d2));
+            sum += pen * pen;
+        }
+        return sum;
+    }
+    // the pairs that involve a capsule: the link's points, then its capsules, each against the other side's points (`obstacles`) and then its capsules (taken as they are)
+    static double capsuleCost(double sum, const Frame& fb, double margin, const std::vector<double>& points, const std::vector<double>& capsules, const std::vector<double>& obstacles,
+                              const std::vector<double>& other_capsules) {
+        for (size_t i = 0; i + 4 <= points.size() && !other_capsules.empty(); i += 4) {
+            if (points[i + 3] < 0) continue;
+            const Vector3 w = carry(fb, Vector3(points[i], points[i + 1], points[i + 2]));
+            for (size_t j = 0; j + 8 <= other_capsules.size(); j += 8) {
+                const double* o = &other_capsules[j];
+                sum = tail(sum, (margin + points[i + 3]) + o[3], segmentPointD2(Vector3(o[0], o[1], o[2]), Vector3(o[4], o[5], o[6]), w));
+            }
+        }
+        for (size_t i = 0; i + 8 <= capsules.size(); i += 8) {
+            const double* k = &capsules[i];
+            const Vector3 a = carry(fb, Vector3(k[0], k[1], k[2])), b = carry(fb, Vector3(k[4], k[5], k[6]));
+            for (size_t j = 0; j + 4 <= obstacles.size(); j += 4)
+                sum = tail(sum, (margin + k[3]) + obstacles[j + 3], segmentPointD2(a, b, Vector3(obstacles[j], obstacles[j + 1], obstacles[j + 2])));
+            for (size_t j = 0; j + 8 <= other_capsules.size(); j += 8) {
+                const double* o = &other_capsules[j];
+                sum = tail(sum, (margin + k[3]) + o[3], segmentSegmentD2(a, b, Vector3(o[0], o[1], o[2]), Vector3(o[4], o[5], o[6])));
+            }
+        }
+        return sum;
+    }
+    // with capsules: the point pairs as below, then the pairs that involve a capsule (opcode 19: `other_capsules` empty; the order of summation differs from the device's
+    // where both links of a SelfClearanceGoal carry points AND capsules: equal up to rounding)
+    static double cost(const Frame& fb, double margin, const std::vector<double>& points, const std::vector<double>& obstacles, const std::vector<double>& capsules,
+                       const std::vector<double>& other_capsules = std::vector<double>()) {
+        return capsuleCost(cost(fb, margin, points, obstacles), fb, margin, points, capsules, obstacles, other_capsules);
+    }
     // the formula above with the quaternion as it is, unit or not (frame.h:108-149): i outer, j inner, one running sum
     static double cost(const Frame& fb, double margin, const std::vector<double>& points, const std::vector<double>& obstacles) {
         const Quaternion q = fb.getOrientation();
@@ -482,7 +545,7 @@ public:
         }
         return sum;
     }
-    double evaluate(const GoalContext& context) const override { return cost(context.getLinkFrame(), margin_, context.getLinkPoints(), obstacles_); }
+    double evaluate(const GoalContext& context) const override { return cost(context.getLinkFrame(), margin_, context.getLinkPoints(), obstacles_, context.getLinkCapsules()); }
     int gpuOpcode() const override { return BIOIK_GOAL_CLEARANCE; }
     void gpuParams(std::vector<double>& o) const override { o.push_back(margin_); }
     const std::vector<double>* gpuObstacles() const override { return &obstacles_; }
@@ -506,7 +569,7 @@ public:
     // (reads both frames and both links' points: the hybrid path scores candidates with it)
     double evaluate(const GoalContext& context) const override {
         if (getBaseLinkName().empty()) return 0.0;  // (no other link: the device refuses such a goal)
-        return ClearanceGoal::cost(goalFrame(context), margin_, context.getLinkPoints(0), context.getLinkPoints(1));
+        return ClearanceGoal::cost(goalFrame(context), margin_, context.getLinkPoints(0), context.getLinkPoints(1), context.getLinkCapsules(0), context.getLinkCapsules(1));
     }
     int gpuOpcode() const override { return BIOIK_GOAL_SELF_CLEARANCE; }
     void gpuParams(std::vector<double>& o) const override { o.push_back(margin_); }

@@ -107,6 +107,7 @@ public:
         };
         mv.link_points = [&rm](const std::string& link) { return rm.collisionPoints(link); };
         mv.link_disks = [&rm](const std::string& link) { return rm.collisionDisks(link); };
+        mv.link_capsules = [&rm](const std::string& link) { return rm.collisionCapsules(link); };
         joint_names.clear();
         for (int j : jmg.active_joints) {
             joint_names.push_back(rm.joint_names[j]);

@@ -49,6 +49,7 @@ struct ModelView {
     std::function<void(const std::string& link, const double* positions, double* frame7)> link_frame;  // global frame of a link at a full variable vector
     std::function<const std::vector<double>*(const std::string& link)> link_points;  // collision points x y z r of a link (TouchGoal, ClearanceGoal on the host); may be empty
     std::function<const std::vector<double>*(const std::string& link)> link_disks;   // collision disks cx cy cz r ax ay az 0 of a link (likewise)
+    std::function<const std::vector<double>*(const std::string& link)> link_capsules;  // collision capsules ax ay az r bx by bz 0 of a link (likewise); may be empty
     std::vector<std::string> var_names;  // optional: the variables' names, for messages (consistency limits that are refused name their variable)
 };
 
@@ -533,6 +534,7 @@ public:
             hm.variable_index = mv_.variable_index;
             hm.link_points = mv_.link_points;
             hm.link_disks = mv_.link_disks;
+            hm.link_capsules = mv_.link_capsules;
             const ModelView* mv = &mv_;
             hm.link_frame = [mv](const std::string& name, const std::vector<double>& p) {
                 double f[7];

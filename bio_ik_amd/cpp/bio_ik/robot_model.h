@@ -41,8 +41,10 @@ public:
         double radius, length, origin[7];
     };
     std::map<int, std::vector<SolidRef>> link_solids;
-    mutable std::vector<int32_t> point_first_, disk_first_;  // flattened by desc()
-    mutable std::vector<double> points_flat_, disks_flat_;
+    // capsules: per link rows ax ay az r bx by bz 0 in the link frame -- a segment's two ends and a radius (ClearanceGoal, SelfClearanceGoal; TouchGoal reads each as two spheres)
+    std::map<int, std::vector<double>> link_capsules;
+    mutable std::vector<int32_t> point_first_, disk_first_, capsule_first_;  // flattened by desc()
+    mutable std::vector<double> points_flat_, disks_flat_, capsules_flat_;
 
     // points (x y z triples) with radii (empty: all 0), moved by the shape's collision origin (px py pz qx qy qz qw; null or the identity: untouched)
     void addCollisionPoints(const std::string& link, const std::vector<double>& xyz, const std::vector<double>& radii = {}, const double* origin = nullptr) {
@@ -95,6 +97,34 @@ public:
             t.insert(t.end(), {c[0], c[1], c[2], rows[i + 3], a[0], a[1], a[2], 0.0});
         }
     }
+    // raw capsules: rows ax ay az r bx by bz 0 (radius >= 0, the two ends different: a sphere is a point row), both ends moved by the shape's collision origin
+    void addCollisionCapsules(const std::string& link, const std::vector<double>& rows, const double* origin = nullptr) {
+        std::vector<double>& t = link_capsules[linkIndex(link)];
+        const bool ident = !origin || (origin[0] == 0 && origin[1] == 0 && origin[2] == 0 && origin[3] == 0 && origin[4] == 0 && origin[5] == 0 && origin[6] == 1);
+        for (size_t i = 0; i + 8 <= rows.size(); i += 8) {
+            double a[3] = {rows[i], rows[i + 1], rows[i + 2]}, b[3] = {rows[i + 4], rows[i + 5], rows[i + 6]};
+            for (int c = 0; c < 8; c++)
+                if (!std::isfinite(rows[i + c])) throw std::runtime_error("collision capsules must be finite");
+            if (!(rows[i + 3] >= 0) || rows[i + 7] != 0) throw std::runtime_error("collision capsules: radius >= 0, an eighth number 0");
+            if (a[0] == b[0] && a[1] == b[1] && a[2] == b[2]) throw std::runtime_error("collision capsules: the two ends coincide (a sphere is a point row: addCollisionSphere)");
+            if (!ident) {
+                double r[3];
+                rotate(origin + 3, a, r);
+                for (int k = 0; k < 3; k++) a[k] = r[k] + origin[k];
+                rotate(origin + 3, b, r);
+                for (int k = 0; k < 3; k++) b[k] = r[k] + origin[k];
+            }
+            t.insert(t.end(), {a[0], a[1], a[2], rows[i + 3], b[0], b[1], b[2], 0.0});
+        }
+    }
+    // a capsule centred on its origin with its axis along z; `length` is the SEGMENT's length (the capsule is length + 2 radius long overall)
+    void addCollisionCapsule(const std::string& link, double radius, double length, const double* origin = nullptr) {
+        addCollisionCapsules(link, {0.0, 0.0, -0.5 * length, radius, 0.0, 0.0, 0.5 * length, 0.0}, origin);
+    }
+    const std::vector<double>* collisionCapsules(const std::string& link) const {
+        auto it = link_capsules.find(linkIndex(link));
+        return it == link_capsules.end() ? nullptr : &it->second;
+    }
     // URDF <cylinder> / shapes::Cylinder: centred on its origin, axis z -- its two end disks (exact: a cylinder is their convex hull)
     void addCollisionCylinder(const std::string& link, double radius, double length, const double* origin = nullptr) {
         addCollisionDisks(link, {0.0, 0.0, -0.5 * length, radius, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.5 * length, radius, 0.0, 0.0, 1.0, 0.0}, origin);
@@ -112,13 +142,17 @@ public:
         for (int c = 0; c < 7; c++) r.origin[c] = origin[c];
         link_solids[linkIndex(link)].push_back(r);
     }
-    // every solid the URDF reader recorded (of `link`, or of all links) becomes its disks, and exactly the marker row the reader left for it goes
-    void resolveCollisionSolids(const std::string& link = "") {
+    // every solid the URDF reader recorded (of `link`, or of all links) becomes its disks, and exactly the marker row the reader left for it goes.
+    // cylinders = "capsule": a cylinder becomes its BOUNDING CAPSULE instead (the same radius, the segment its whole axis), which ClearanceGoal and SelfClearanceGoal can
+    // measure -- an approximation asked for by name, never silent: it contains the cylinder and overshoots it by the radius at each end
+    void resolveCollisionSolids(const std::string& link = "", const std::string& cylinders = "disks") {
+        if (cylinders != "disks" && cylinders != "capsule") throw std::runtime_error("resolveCollisionSolids: cylinders is \"disks\" or \"capsule\"");
         for (auto& ls : link_solids) {
             if (!link.empty() && ls.first != linkIndex(link)) continue;
             const std::string& name = link_names[ls.first];
             for (const SolidRef& r : ls.second) {
-                if (r.kind == "cylinder") addCollisionCylinder(name, r.radius, r.length, r.origin);
+                if (r.kind == "cylinder" && cylinders == "capsule") addCollisionCapsule(name, r.radius, r.length, r.origin);
+                else if (r.kind == "cylinder") addCollisionCylinder(name, r.radius, r.length, r.origin);
                 else addCollisionCone(name, r.radius, r.length, r.origin);
                 std::vector<double>& t = link_points[ls.first];
                 for (size_t i = 0; i + 4 <= t.size(); i += 4)
@@ -306,6 +340,13 @@ public:
             disk_first_.push_back((int32_t)(disks_flat_.size() / 8));
         }
         if (!disks_flat_.empty()) d.link_disk_first = disk_first_.data(), d.link_disks = disks_flat_.data();
+        capsule_first_.assign(1, 0), capsules_flat_.clear();
+        for (size_t l = 0; l < link_names.size(); l++) {
+            auto it = link_capsules.find((int)l);
+            if (it != link_capsules.end()) capsules_flat_.insert(capsules_flat_.end(), it->second.begin(), it->second.end());
+            capsule_first_.push_back((int32_t)(capsules_flat_.size() / 8));
+        }
+        if (!capsules_flat_.empty()) d.link_capsule_first = capsule_first_.data(), d.link_capsules = capsules_flat_.data();
         return d;
     }
     // frame algebra for the plugin boundary (goal poses into the model frame, kinematics_plugin.cpp:487-502)

@@ -6,6 +6,7 @@
 // flat joint program (DevProblem) the gfx950 kernels walk: fixed links are folded into per-joint constant frames,
 // branch frames get LDS slots, goals are grouped by the tip they read.
 #include "bioik_compile.h"
+#include "bioik_fused.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -82,7 +83,9 @@ static int joint_var_count(int type) {
 HostModel::HostModel(const bioik_model_desc& d) {
     // (the descriptor grew by link_point_first / link_points without a new ABI version: a caller built against the header without them passes the shorter size)
     // and then by link_disk_first / link_disks in the same way: the three sizes are accepted, one between two of them is not
-    const bool has_disks = d.struct_size == sizeof(bioik_model_desc);
+    // and then by link_capsule_first / link_capsules: four sizes
+    const bool has_capsules = d.struct_size == sizeof(bioik_model_desc);
+    const bool has_disks = has_capsules || d.struct_size == offsetof(bioik_model_desc, link_capsule_first);
     const bool has_points = has_disks || d.struct_size == offsetof(bioik_model_desc, link_disk_first);
     if (!has_points && d.struct_size != offsetof(bioik_model_desc, link_point_first)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: struct_size mismatch");
     if (d.n_links == 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "model has no links");
@@ -144,6 +147,23 @@ HostModel::HostModel(const bioik_model_desc& d) {
             const double len = std::sqrt(disks[i + 4] * disks[i + 4] + disks[i + 5] * disks[i + 5] + disks[i + 6] * disks[i + 6]);
             if (!(std::fabs(len - 1.0) <= 1e-9)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the axis of a collision disk must be of unit length (within 1e-9)");
             if (disks[i + 7] != 0.0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the eighth number of a collision disk must be 0");
+        }
+    }
+    capsule_first.assign(d.n_links + 1, 0);
+    if (has_capsules && (d.link_capsule_first || d.link_capsules)) {
+        if (!d.link_capsule_first || !d.link_capsules) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_capsule_first and link_capsules go together");
+        if (d.link_capsule_first[0] != 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_capsule_first[0] must be 0");
+        for (uint32_t i = 0; i < d.n_links; i++)
+            if (d.link_capsule_first[i + 1] < d.link_capsule_first[i]) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: link_capsule_first must be ascending");
+        capsule_first.assign(d.link_capsule_first, d.link_capsule_first + d.n_links + 1);
+        capsules.assign(d.link_capsules, d.link_capsules + (size_t)capsule_first[d.n_links] * 8);
+        for (size_t i = 0; i < capsules.size(); i += 8) {
+            for (int c = 0; c < 8; c++)
+                if (!std::isfinite(capsules[i + c])) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: a collision capsule is not finite");
+            if (!(capsules[i + 3] >= 0.0)) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the radius of a collision capsule must be >= 0");
+            if (capsules[i] == capsules[i + 4] && capsules[i + 1] == capsules[i + 5] && capsules[i + 2] == capsules[i + 6])
+                throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the two ends of a collision capsule coincide (a sphere is a point row of link_points)");
+            if (capsules[i + 7] != 0.0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "bioik_model_desc: the eighth number of a collision capsule must be 0");
         }
     }
     // A joint that mimics a joint that itself mimics another: resolved to the joint at the end of the chain with the composed factor and offset, as MoveIt's
@@ -235,6 +255,8 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         int point_first, point_count, disk_count;  // TouchGoal: its link's points in touch_points (rows of four doubles) and the disks behind them.  ClearanceGoal: its points, and in
                                                    // disk_count the first row of its obstacle block.  SelfClearanceGoal: the first row of its block (its link's rows, directly
                                                    // behind them the other link's), in point_count its link's rows, in disk_count the other link's
+        int capsule_count[2];                      // ClearanceGoal: [0] the capsules of its link, whose rows (two of four doubles each) lie behind its points.  SelfClearanceGoal: [0] its
+                                                   // link's, behind that link's points, [1] the other link's, behind that link's points.  0 for every other goal
         int base_tip;                              // a based goal (bioik_problem_desc::goal_base_link): the public tip of its base link, else -1
     };
     std::vector<G> goals;
@@ -244,7 +266,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
         const bioik_goal_desc& g = d.goals[gi];
         int np = goal_param_count(g.type);
         if (np < 0) throw Error(BIOIK_ERR_UNSUPPORTED, "goal type has no device implementation");
-        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0, 0, -1};
+        G info{g.type, -1, LONG_MIN, g.weight, g.secondary != 0, param_count, 0, 0, 0, {0, 0}, -1};
         if (g.link >= 0) {
             if (g.link >= nl) throw Error(BIOIK_ERR_NOT_FOUND, "link not found");
             info.tip = add_tip_link(g.link);
@@ -274,14 +296,20 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
                     throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: a row of the link in bioik_model_desc::link_points has the radius -1, the marker of a shape that is no "
                                                        "set of points or disks (a mesh without its vertices, a shape the caller did not convert -- a cylinder or a cone left as it was): no device implementation, not approximated");
             const int dfirst = m->disk_first[g.link], dcount = m->disk_first[g.link + 1] - dfirst;
-            if (count <= 0 && dcount <= 0)
+            // a capsule joins the points as its two end spheres A r and B r: its support function along any normal is the smaller of theirs (exact; no kernel change)
+            const int cfirst = m->capsule_first[g.link], ccount = m->capsule_first[g.link + 1] - cfirst;
+            if (count <= 0 && dcount <= 0 && ccount <= 0)
                 throw Error(BIOIK_ERR_INVALID_ARGUMENT, "TouchGoal: the link has no collision points (bioik_model_desc::link_points) and no disks (link_disks); the reference's cost would be DBL_MAX squared");
-            if ((long)count + (long)dcount > BIOIK_MAX_TOUCH_POINTS)
+            if ((long)count + 2 * (long)ccount + (long)dcount > BIOIK_MAX_TOUCH_POINTS)
                 throw Error(BIOIK_ERR_UNSUPPORTED, "TouchGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) +
-                                                       ") collision points and disks together: pass the mesh as its convex hull or decimated");
+                                                       ") collision points and disks together (a capsule counts as two points): pass the mesh as its convex hull or decimated");
             // (a disk is two rows of four doubles: the next goal's first row stays a whole number)
-            info.point_first = (int)(touch_points.size() / 4), info.point_count = count, info.disk_count = dcount;
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = count + 2 * ccount, info.disk_count = dcount;
             touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
+            for (int i = 0; i < ccount; i++) {
+                const double* c = &m->capsules[(size_t)(cfirst + i) * 8];
+                touch_points.insert(touch_points.end(), {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[3]});
+            }
             touch_points.insert(touch_points.end(), m->disks.begin() + (size_t)dfirst * 8, m->disks.begin() + (size_t)(dfirst + dcount) * 8);
         }
         clearance_block.push_back(-1);
@@ -294,11 +322,15 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
                                                        "set of spheres (a mesh without its vertices, a cylinder or a cone left as it was): no device implementation, not approximated");
             if (m->disk_first[g.link + 1] - m->disk_first[g.link] > 0)
                 throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link carries disks (bioik_model_desc::link_disks: a cylinder or a cone); only spheres have a device implementation, not approximated");
-            if (count <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "ClearanceGoal: the link has no collision points (bioik_model_desc::link_points)");
-            if (count > BIOIK_MAX_TOUCH_POINTS)
-                throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) + ") collision points");
-            info.point_first = (int)(touch_points.size() / 4), info.point_count = count;
+            const int cfirst = m->capsule_first[g.link], ccount = m->capsule_first[g.link + 1] - cfirst;
+            if (count <= 0 && ccount <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "ClearanceGoal: the link has no collision points (bioik_model_desc::link_points) and no capsules (link_capsules)");
+            if (ccount > BIOIK_MAX_LINK_CAPSULES)
+                throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link has more than BIOIK_MAX_LINK_CAPSULES (" + std::to_string(BIOIK_MAX_LINK_CAPSULES) + ") capsules");
+            if ((long)count + (long)ccount > BIOIK_MAX_TOUCH_POINTS)
+                throw Error(BIOIK_ERR_UNSUPPORTED, "ClearanceGoal: the link has more than BIOIK_MAX_TOUCH_POINTS (" + std::to_string(BIOIK_MAX_TOUCH_POINTS) + ") collision points and capsules together");
+            info.point_first = (int)(touch_points.size() / 4), info.point_count = count, info.capsule_count[0] = ccount;
             touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + count) * 4);
+            touch_points.insert(touch_points.end(), m->capsules.begin() + (size_t)cfirst * 8, m->capsules.begin() + (size_t)(cfirst + ccount) * 8);  // (two rows each)
             info.disk_count = (int)(touch_points.size() / 4);  // (DevGoal::pad: the first row of the obstacle block -- its count row, all zero bits: no obstacle)
             touch_points.insert(touch_points.end(), (size_t)(1 + BIOIK_MAX_OBSTACLES) * 4, 0.0);
             clearance_block.back() = info.disk_count;
@@ -309,7 +341,7 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             const int caps[2] = {BIOIK_MAX_TOUCH_POINTS, BIOIK_MAX_OBSTACLES};
             const char* const names[2] = {"the goal's link", "the other link"};
             const char* const cap_names[2] = {"BIOIK_MAX_TOUCH_POINTS", "BIOIK_MAX_OBSTACLES"};
-            int counts[2];
+            int counts[2], ccounts[2];
             for (int k = 0; k < 2; k++) {
                 const int first = m->point_first[links[k]], count = m->point_first[links[k] + 1] - first;
                 for (int i = 0; i < count; i++)
@@ -318,16 +350,33 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
                                                                "set of spheres (a mesh without its vertices, a cylinder or a cone left as it was): no device implementation, not approximated");
                 if (m->disk_first[links[k] + 1] - m->disk_first[links[k]] > 0)
                     throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " carries disks (bioik_model_desc::link_disks: a cylinder or a cone); only spheres have a device implementation, not approximated");
-                if (count <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + names[k] + " has no collision points (bioik_model_desc::link_points)");
-                if (count > caps[k])
-                    throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " has more than " + cap_names[k] + " (" + std::to_string(caps[k]) + ") collision points");
-                counts[k] = count;
+                const int ccount = m->capsule_first[links[k] + 1] - m->capsule_first[links[k]];
+                if (count <= 0 && ccount <= 0) throw Error(BIOIK_ERR_INVALID_ARGUMENT, who + names[k] + " has no collision points (bioik_model_desc::link_points) and no capsules (link_capsules)");
+                if (ccount > BIOIK_MAX_LINK_CAPSULES)
+                    throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " has more than BIOIK_MAX_LINK_CAPSULES (" + std::to_string(BIOIK_MAX_LINK_CAPSULES) + ") capsules");
+                if ((long)count + (long)ccount > caps[k])
+                    throw Error(BIOIK_ERR_UNSUPPORTED, who + names[k] + " has more than " + cap_names[k] + " (" + std::to_string(caps[k]) + ") collision points and capsules together");
+                counts[k] = count, ccounts[k] = ccount;
             }
+            // the block: the link's points, its capsules (two rows each), the other link's points, its capsules
             info.point_first = (int)(touch_points.size() / 4), info.point_count = counts[0], info.disk_count = counts[1];
+            info.capsule_count[0] = ccounts[0], info.capsule_count[1] = ccounts[1];
             for (int k = 0; k < 2; k++) {
-                const int first = m->point_first[links[k]];
+                const int first = m->point_first[links[k]], cfirst = m->capsule_first[links[k]];
                 touch_points.insert(touch_points.end(), m->points.begin() + (size_t)first * 4, m->points.begin() + (size_t)(first + counts[k]) * 4);
+                for (int i = 0; i < ccounts[k]; i++) {
+                    const double* c = &m->capsules[(size_t)(cfirst + i) * 8];
+                    if (k == 0) {  // the goal's link: the two ends, carried into the other link's frame on the device
+                        touch_points.insert(touch_points.end(), c, c + 8);
+                        continue;
+                    }
+                    // the other link's need no transform: first end, radius, u = b - a and ru = 1 / (u.u) -- the operations of CAPSULES (include/bioik_hip.h), done once here
+                    const double ux = c[4] - c[0], uy = c[5] - c[1], uz = c[6] - c[2];
+                    const double uu = bk_dot3(ux, uy, uz, ux, uy, uz);
+                    touch_points.insert(touch_points.end(), {c[0], c[1], c[2], c[3], ux, uy, uz, uu > 2.2250738585072014e-308 ? 1.0 / uu : 0.0});
+                }
             }
+            if (info.point_first >= (1 << 18)) throw Error(BIOIK_ERR_UNSUPPORTED, who + "the problem's collision tables are beyond 2^18 rows");  // (DevGoal::var_seed holds the row in 18 bits)
         }
         if (g.type == BIOIK_GOAL_BALANCE) {  // BalanceGoal::describe (goal_types.cpp:231-255): every link with mass becomes a tip, in link order
             if (g.secondary) throw Error(BIOIK_ERR_UNSUPPORTED, "BalanceGoal cannot be a secondary goal (the reference's has no such constructor)");
@@ -659,8 +708,10 @@ HostProblem::HostProblem(const HostModel* m, const bioik_problem_desc& d) : mode
             else o.var_seed = (int)(-1 - g.var);
         }
         if (g.type == BIOIK_GOAL_TOUCH || g.type == BIOIK_GOAL_CLEARANCE) o.var_op = g.point_first, o.var_seed = g.point_count, o.pad = g.disk_count;
+        if (g.type == BIOIK_GOAL_CLEARANCE) o.var_seed |= g.capsule_count[0] << 16;  // (its capsules, behind its points: bioik_types.h)
         // SelfClearanceGoal (always based: var_op is taken below): var_seed = the first row of its block in touch_points, pad = rows of its link | rows of the other link << 16 (bioik_types.h)
-        if (g.type == BIOIK_GOAL_SELF_CLEARANCE) o.var_seed = g.point_first, o.pad = g.point_count | (g.disk_count << 16);
+        if (g.type == BIOIK_GOAL_SELF_CLEARANCE)
+            o.var_seed = (int32_t)((uint32_t)g.point_first | ((uint32_t)g.capsule_count[0] << 18) | ((uint32_t)g.capsule_count[1] << 25)), o.pad = g.point_count | (g.disk_count << 16);
         if (g.base_tip >= 0 && g.tip >= 0) {  // var_op <= -2 marks a based goal (a link goal reads no variable): -2 - (held tip * 2 + "the held frame is the goal's own link's")
             const int own = dev.tip_of_out[g.tip], base = dev.tip_of_out[g.base_tip];
             o.tip = std::max(own, base);

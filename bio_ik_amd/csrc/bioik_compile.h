@@ -39,6 +39,8 @@ struct HostModel {
     std::vector<double> points;    // x y z r per collision point, link frame (TouchGoal)
     std::vector<int> disk_first;   // [links + 1] rows of `disks` (bioik_model_desc::link_disk_first); all zero: no link has disks
     std::vector<double> disks;     // cx cy cz r ax ay az 0 per disk, link frame (TouchGoal: the ends of a cylinder, the base of a cone)
+    std::vector<int> capsule_first;  // [links + 1] rows of `capsules` (bioik_model_desc::link_capsule_first); all zero: no link has capsules
+    std::vector<double> capsules;  // ax ay az r bx by bz 0 per capsule, link frame (ClearanceGoal, SelfClearanceGoal; TouchGoal reads each as its two end spheres)
     explicit HostModel(const bioik_model_desc& d);
 };
 

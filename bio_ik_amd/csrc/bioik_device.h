@@ -336,6 +336,64 @@ BIOIK_DEV double clearance_pair(double sum, const V3& w, double sm, double cx, d
     }
     return sum;
 }
+// CAPSULES (include/bioik_hip.h states every operation; this is its one implementation, used at every site of goal_eval_clearance and goal_eval_self_clearance).
+// A capsule is a segment and a radius.  Seg: what depends on the segment alone -- its first end a, u = b - a, u.u and ru = 1 / (u.u) (one division, correctly
+// rounded), or ru = 0 where u.u is not above DBL_MIN: the segment then counts as its first end (the zero quaternion of a linearised phenotype collapses every
+// segment of the link to a point, and 0 / 0 must not be formed).  A caller hoists it out of whatever loop does not change the segment.
+// seg_point_d2: t = clamp(e.u ru) with e = c - a, then x = c - (a + t u).  seg_seg_d2: clamped closest points of two segments -- s from the two-line solution where its
+// denominator is positive, else 0; t from s; where t leaves [0, 1] (or the second segment counts as a point) t is clamped and s solved again.  Every product that
+// feeds an addition is fused (fma), nothing else is.  e.u ru is finite or +-inf, never NaN (ru is finite), and fmin / fmax clamp an infinity: no finite input of
+// ordinary size yields a NaN.  The distance that comes out is the distance of two points ON the segments: never below the true minimum.
+// clearance_tail: the tail of clearance_pair, word for word.
+struct Seg {
+    V3 a, u;
+    double uu, ru;
+};
+BIOIK_DEV Seg seg_make(V3 a, V3 b) {
+    Seg g;
+    g.a = a, g.u = b - a;
+    g.uu = len2(g.u);
+    g.ru = g.uu > 2.2250738585072014e-308 ? 1.0 / g.uu : 0.0;
+    return g;
+}
+// a capsule of opcode 20's OTHER link needs no transform, so the problem compiler has made its Seg once, by the same operations, and the table row holds
+// a.x a.y a.z r u.x u.y u.z ru (bioik_types.h): every number a scalar register, and no division per pair
+BIOIK_DEV Seg seg_of_row(UniformF64 h) {
+    Seg g;
+    g.a = v3(h[0], h[1], h[2]), g.u = v3(h[4], h[5], h[6]);
+    g.uu = len2(g.u);
+    g.ru = h[7];
+    return g;
+}
+BIOIK_DEV double clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
+BIOIK_DEV double seg_point_d2(const Seg& g, V3 c) {
+    const V3 e = c - g.a;
+    const double t = clamp01(dot3(e, g.u) * g.ru);
+    return dist2(v3(BK_FMA(t, g.u.x, g.a.x), BK_FMA(t, g.u.y, g.a.y), BK_FMA(t, g.u.z, g.a.z)), c);  // (the closest point a + t u, then its distance from c: e is not held)
+}
+BIOIK_DEV double seg_seg_d2(const Seg& g, const Seg& h) {
+    const V3 w = g.a - h.a;
+    const double uv = dot3(g.u, h.u), uw = dot3(g.u, w), vw = dot3(h.u, w);
+    const double den = BK_FMA(g.uu, h.uu, -(uv * uv));
+    double s = 0.0;
+    if (den > 0.0) s = clamp01(BK_FMA(uv, vw, -(h.uu * uw)) / den);
+    const double t = BK_FMA(uv, s, vw) * h.ru;
+    const double tc = clamp01(t);
+    if (tc != t || h.ru == 0.0) s = clamp01(BK_FMA(uv, tc, -uw) * g.ru);
+    // (the two closest points, then their distance: w is not held across the division)
+    return dist2(v3(BK_FMA(tc, h.u.x, h.a.x), BK_FMA(tc, h.u.y, h.a.y), BK_FMA(tc, h.u.z, h.a.z)), v3(BK_FMA(s, g.u.x, g.a.x), BK_FMA(s, g.u.y, g.a.y), BK_FMA(s, g.u.z, g.a.z)));
+}
+BIOIK_DEV double clearance_tail(double sum, double s, double d2) {
+    if (s > 0.0 && d2 < s * s) {
+        const double pen = fmax(0.0, s - sqrt(d2));
+        sum = BK_FMA(pen, pen, sum);
+    }
+    return sum;
+}
+// goal_eval_clearance with capsules: `count` = n | k << 16 -- the link's n >= 0 points and directly behind them its k >= 0 capsules (rows ax ay az r bx by bz 0, two
+// rows of four doubles each; n + k >= 1).  The points run first, through the loop as it was; then each capsule, its two ends carried into the world ONCE
+// (p + rotate(q, .), as a point) and its Seg made in front of the obstacle loop, against every obstacle j ascending, into the same running sum.  One obstacle per
+// trip: a trip holds the capsule's eight numbers in vector registers beside the obstacle's four scalars.
 BIOIK_CALL double goal_eval_clearance(ProbPtr pb_, int first, int count, int block, const lds_f64* P, F7 fb) {
     const unsigned long long pba = (unsigned long long)pb_;
     const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
@@ -343,7 +401,10 @@ BIOIK_CALL double goal_eval_clearance(ProbPtr pb_, int first, int count, int blo
     const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
     const unsigned long long oaddr = (unsigned long long)(pb->touch_points + 4 * p_uniform(block));
     const UniformF64 head = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(oaddr >> 32)) << 32) | (unsigned int)p_uniform((int)oaddr));
-    const int n = p_uniform(count);
+    const int nk = p_uniform(count);
+    const int n = nk & 0xffff;
+    int k = (nk >> 16) & 0xffff;
+    k = k > BIOIK_DEV_MAX_LINK_CAPSULES ? BIOIK_DEV_MAX_LINK_CAPSULES : k;  // (never beyond what the problem compiler can have laid out)
     int m = p_uniform(*(UniformI32)head);
     m = m < 0 ? 0 : (m > BIOIK_DEV_MAX_OBSTACLES ? BIOIK_DEV_MAX_OBSTACLES : m);  // (never beyond the block, whatever the word holds)
     if (m == 0) return 0.0;
@@ -363,6 +424,16 @@ BIOIK_CALL double goal_eval_clearance(ProbPtr pb_, int first, int count, int blo
         if (j < m) {
             const UniformF64 c = o + 4 * j;
             sum = clearance_pair(sum, w, sm, c[0], c[1], c[2], c[3]);
+        }
+    }
+    const UniformF64 cap = v + 4 * n;
+    for (int i = 0; i < k; i++) {
+        const UniformF64 a = cap + 8 * i;
+        const Seg g = seg_make(fb.p + qrot(fb.q, v3(a[0], a[1], a[2])), fb.p + qrot(fb.q, v3(a[4], a[5], a[6])));
+        const double sm = margin + a[3];
+        for (int j = 0; j < m; j++) {
+            const UniformF64 c = o + 4 * j;
+            sum = clearance_tail(sum, sm + c[3], seg_point_d2(g, v3(c[0], c[1], c[2])));
         }
     }
     return sum;
@@ -681,7 +752,7 @@ BIOIK_DEV double goal_eval(PB pb, int type, int var_op, int var_seed, const doub
         default:  // the remaining link goals
             // TouchGoal: only in the general flavour (the launcher hands a problem with one to k_solve, never to a lean kernel: those stay as they were).  A link
             // goal has no variable: var_op / var_seed carry its first point and its number of points, aux (DevGoal::pad) its number of disks
-            // ClearanceGoal: likewise; var_op / var_seed its first point and its number of points, aux the first row of its obstacle block
+            // ClearanceGoal: likewise; var_op / var_seed its first point and its number of points (| its capsules << 16: bioik_types.h), aux the first row of its obstacle block
             if constexpr (pb_flavour<PB>::general) {
                 if (type == G_TOUCH) return goal_eval_touch(pb, var_op, var_seed, aux, (const lds_f64*)P, fb);
                 if (type == G_CLEARANCE) return goal_eval_clearance(pb, var_op, var_seed, aux, (const lds_f64*)P, fb);
@@ -743,39 +814,99 @@ BIOIK_CALL double based_goal_cost_slots(int type, int var_op, const lds_f64* P, 
 BIOIK_CALL double goal_eval_self_clearance(ProbPtr pb_, int first, int counts, double margin, F7 r) {
     const unsigned long long pba = (unsigned long long)pb_;
     const ProbPtr pb = (ProbPtr)(((unsigned long long)(unsigned int)p_uniform((int)(pba >> 32)) << 32) | (unsigned int)p_uniform((int)pba));
-    const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * p_uniform(first));
+    // CAPSULES: `first` = the first row | kl << 18 | ko << 25 -- kl capsules of the goal's link behind its n points, ko of the other link behind its m points (the
+    // block: n rows, 2 kl rows, m rows, 2 ko rows; n + kl >= 1, m + ko >= 1).  Without capsules the word is the row and the loop below runs as it did.
+    const unsigned int fw = (unsigned int)p_uniform(first);
+    int kl = (int)((fw >> 18) & 0x7f), ko = (int)((fw >> 25) & 0x7f);
+    kl = kl > BIOIK_DEV_MAX_LINK_CAPSULES ? BIOIK_DEV_MAX_LINK_CAPSULES : kl;
+    ko = ko > BIOIK_DEV_MAX_LINK_CAPSULES ? BIOIK_DEV_MAX_LINK_CAPSULES : ko;
+    const unsigned long long addr = (unsigned long long)(pb->touch_points + 4 * (int)(fw & 0x3ffff));
     const UniformF64 v = (UniformF64)(((unsigned long long)(unsigned int)p_uniform((int)(addr >> 32)) << 32) | (unsigned int)p_uniform((int)addr));
     const int nm = p_uniform(counts);
     int n = nm & 0xffff, m = (nm >> 16) & 0xffff;
     n = n > BIOIK_DEV_MAX_TOUCH_POINTS ? BIOIK_DEV_MAX_TOUCH_POINTS : n;  // (never beyond what the problem compiler can have laid out, whatever the word holds)
     m = m > BIOIK_DEV_MAX_OBSTACLES ? BIOIK_DEV_MAX_OBSTACLES : m;
-    if (n == 0 || m == 0) return 0.0;
-    const UniformF64 o = v + 4 * n;
+    const UniformF64 o = v + 4 * (n + 2 * kl);
     double sum = 0.0;
-    // the rows of the trip at hand (a: two rows, or one in a0 ... a3) and of the one behind it (b)
-    double a0 = o[0], a1 = o[1], a2 = o[2], a3 = o[3], a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
-    if (m >= 2) a4 = o[4], a5 = o[5], a6 = o[6], a7 = o[7];
+    if ((kl | ko) == 0) {  // no capsules: the loop as it was
+        if (n == 0 || m == 0) return 0.0;
+        // the rows of the trip at hand (a: two rows, or one in a0 ... a3) and of the one behind it (b)
+        double a0 = o[0], a1 = o[1], a2 = o[2], a3 = o[3], a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
+        if (m >= 2) a4 = o[4], a5 = o[5], a6 = o[6], a7 = o[7];
+        for (int i = 0; i < n; i++) {
+            const UniformF64 pt = v + 4 * i;
+            const V3 w = r.p + qrot(r.q, v3(pt[0], pt[1], pt[2]));
+            const double sm = margin + pt[3];
+            int j = 0;
+            for (; j + 2 <= m; j += 2) {
+                const int jn = j + 2 < m ? j + 2 : 0;  // (the next trip's first row: the leftover row, or back to row 0 for the next point)
+                const UniformF64 c = o + 4 * jn;
+                const double b0 = c[0], b1 = c[1], b2 = c[2], b3 = c[3];
+                double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+                if (jn + 2 <= m) b4 = c[4], b5 = c[5], b6 = c[6], b7 = c[7];
+                sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
+                sum = clearance_pair(sum, w, sm, a4, a5, a6, a7);
+                a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+            }
+            if (j < m) {  // the leftover row is at hand in a0 ... a3; behind it row 0 again
+                const double b0 = o[0], b1 = o[1], b2 = o[2], b3 = o[3];
+                double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+                if (m >= 2) b4 = o[4], b5 = o[5], b6 = o[6], b7 = o[7];
+                sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
+                a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+            }
+        }
+        return sum;
+    }
+    // With capsules: plain loops, one row per trip and no rows requested ahead -- the sixteen doubles that the loop above keeps in scalar registers, beside a
+    // capsule's eight, are more than the scalar file holds without spilling.  The same pairs in the same order by the same arithmetic: the same bits.
+    if ((n | kl) == 0 || (m | ko) == 0) return 0.0;
+    const UniformF64 ocap = o + 4 * m;
+#pragma unroll 1
     for (int i = 0; i < n; i++) {
         const UniformF64 pt = v + 4 * i;
         const V3 w = r.p + qrot(r.q, v3(pt[0], pt[1], pt[2]));
         const double sm = margin + pt[3];
-        int j = 0;
-        for (; j + 2 <= m; j += 2) {
-            const int jn = j + 2 < m ? j + 2 : 0;  // (the next trip's first row: the leftover row, or back to row 0 for the next point)
-            const UniformF64 c = o + 4 * jn;
-            const double b0 = c[0], b1 = c[1], b2 = c[2], b3 = c[3];
-            double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
-            if (jn + 2 <= m) b4 = c[4], b5 = c[5], b6 = c[6], b7 = c[7];
-            sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
-            sum = clearance_pair(sum, w, sm, a4, a5, a6, a7);
-            a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+#pragma unroll 1
+        for (int j = 0; j < m; j++) {
+            const UniformF64 c = o + 4 * j;
+            sum = clearance_pair(sum, w, sm, c[0], c[1], c[2], c[3]);
         }
-        if (j < m) {  // the leftover row is at hand in a0 ... a3; behind it row 0 again
-            const double b0 = o[0], b1 = o[1], b2 = o[2], b3 = o[3];
-            double b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
-            if (m >= 2) b4 = o[4], b5 = o[5], b6 = o[6], b7 = o[7];
-            sum = clearance_pair(sum, w, sm, a0, a1, a2, a3);
-            a0 = b0, a1 = b1, a2 = b2, a3 = b3, a4 = b4, a5 = b5, a6 = b6, a7 = b7;
+#pragma unroll 1
+        for (int c = 0; c < ko; c++) {  // the point against the other link's capsules, which need no transform
+            const UniformF64 h = ocap + 8 * c;
+            sum = clearance_tail(sum, sm + h[3], seg_point_d2(seg_of_row(h), w));
+        }
+    }
+    if (kl == 0) return sum;
+    // the link's capsules: both ends carried into the other link's frame once, the Seg made outside the inner loops.  The frame and the margin are needed once per
+    // capsule and wait in the lane's scratch memory meanwhile (eight doubles): the inner loops hold a pair of segments in registers, and what this body keeps in
+    // vector registers beyond what it kept without capsules, every site that calls it has to keep free (k_solve has none to spare)
+    volatile double parked[8];
+    parked[0] = r.p.x, parked[1] = r.p.y, parked[2] = r.p.z, parked[3] = r.q.x, parked[4] = r.q.y, parked[5] = r.q.z, parked[6] = r.q.w, parked[7] = margin;
+    const UniformF64 cap = v + 4 * n;
+#pragma unroll 1
+    for (int i = 0; i < kl; i++) {
+        const UniformF64 a = cap + 8 * i;
+        const F7 rr = F7{{parked[0], parked[1], parked[2]}, {parked[3], parked[4], parked[5], parked[6]}};
+        V3 ends[2] = {rr.p, rr.p};
+#pragma unroll 1
+        for (int e = 0; e < 2; e++) {  // (one end after the other: two rotations in flight at once are the widest point of this body)
+            const V3 x = rr.p + qrot(rr.q, v3(a[4 * e], a[4 * e + 1], a[4 * e + 2]));
+            if (e == 0) ends[0] = x;
+            else ends[1] = x;
+        }
+        const Seg g = seg_make(ends[0], ends[1]);
+        const double sm = parked[7] + a[3];
+#pragma unroll 1
+        for (int j = 0; j < m; j++) {
+            const UniformF64 c = o + 4 * j;
+            sum = clearance_tail(sum, sm + c[3], seg_point_d2(g, v3(c[0], c[1], c[2])));
+        }
+#pragma unroll 1
+        for (int c = 0; c < ko; c++) {
+            const UniformF64 h = ocap + 8 * c;
+            sum = clearance_tail(sum, sm + h[3], seg_seg_d2(g, seg_of_row(h)));
         }
     }
     return sum;

@@ -25,7 +25,8 @@
 static_assert((int)G_POSITION == (int)BIOIK_GOAL_POSITION && (int)G_POSE == (int)BIOIK_GOAL_POSE && (int)G_CONE == (int)BIOIK_GOAL_CONE &&
                   (int)G_JOINT_VARIABLE == (int)BIOIK_GOAL_JOINT_VARIABLE && (int)G_MINIMAL_DISPLACEMENT == (int)BIOIK_GOAL_MINIMAL_DISPLACEMENT &&
                   (int)G_AVOID_JOINT_LIMITS == (int)BIOIK_GOAL_AVOID_JOINT_LIMITS && (int)G_TOUCH == (int)BIOIK_GOAL_TOUCH && (int)G_CLEARANCE == (int)BIOIK_GOAL_CLEARANCE &&
-                  (int)G_SELF_CLEARANCE == (int)BIOIK_GOAL_SELF_CLEARANCE && BIOIK_DEV_MAX_OBSTACLES == BIOIK_MAX_OBSTACLES && BIOIK_DEV_MAX_TOUCH_POINTS == BIOIK_MAX_TOUCH_POINTS,
+                  (int)G_SELF_CLEARANCE == (int)BIOIK_GOAL_SELF_CLEARANCE && BIOIK_DEV_MAX_OBSTACLES == BIOIK_MAX_OBSTACLES && BIOIK_DEV_MAX_TOUCH_POINTS == BIOIK_MAX_TOUCH_POINTS &&
+                  BIOIK_DEV_MAX_LINK_CAPSULES == BIOIK_MAX_LINK_CAPSULES,
               "goal opcodes out of sync with include/bioik_hip.h");
 static_assert((int)FK_LINEAR == (int)BIOIK_FK_LINEAR && (int)FK_EXACT == (int)BIOIK_FK_EXACT, "fk modes out of sync");
 

@@ -89,6 +89,11 @@ struct DevGoal {
 // link and directly behind them the m rows of the other link, each in its link's frame, fixed when the problem is created (no count word, no obstacle block) -- and
 // pad = n | m << 16, 1 <= n <= BIOIK_DEV_MAX_TOUCH_POINTS (= BIOIK_MAX_TOUCH_POINTS), 1 <= m <= BIOIK_DEV_MAX_OBSTACLES
 #define BIOIK_DEV_MAX_TOUCH_POINTS 1024
+// CAPSULES (include/bioik_hip.h; rows ax ay az r bx by bz 0, two rows of four doubles each, in DevProblem::touch_points).  ClearanceGoal: its k capsules lie directly behind its n
+// points, in front of its obstacle block, and var_seed = n | k << 16.  SelfClearanceGoal: the block is its link's n points, that link's kl capsules, the other link's m
+// points, that link's ko capsules, and var_seed = first row | kl << 18 | ko << 25 (the row in 18 bits; pad = n | m << 16 as before).  n + k >= 1 on every side, n or m may
+// be 0.  A goal without capsules has the words it had.  TouchGoal: a capsule is two of its point rows (A r, B r), written by the problem compiler.
+#define BIOIK_DEV_MAX_LINK_CAPSULES 64
 
 struct DevProblem {
     // the scalars one code site reads together sit in one 16-byte group, so that they arrive with one scalar load

@@ -248,6 +248,68 @@ class PlaneGoal(LinkGoalBase):
         return np.concatenate([self.position, self.normal])
 
 
+_TINY = 2.2250738585072014e-308  # DBL_MIN: a segment whose squared length is not above it counts as its first end (include/bioik_hip.h: CAPSULES)
+
+
+def _clamp01(x):
+    return min(max(x, 0.0), 1.0)
+
+
+def segment_point_d2(a, b, c):
+    """CAPSULES (include/bioik_hip.h): the squared distance of the point c from the segment a b, the device's formula in float64 (unfused: equal up to rounding)"""
+    u, e = b - a, c - a
+    uu = float(u @ u)
+    t = _clamp01(float(e @ u) * (1.0 / uu)) if uu > _TINY else 0.0
+    x = e - t * u
+    return float(x @ x)
+
+
+def segment_segment_d2(a, b, c, d):
+    """CAPSULES (include/bioik_hip.h): the squared distance of the segments a b and c d by clamped closest points, the device's formula in float64 (unfused)"""
+    u, v, w = b - a, d - c, a - c
+    uu, uv, vv, uw, vw = float(u @ u), float(u @ v), float(v @ v), float(u @ w), float(v @ w)
+    ru = 1.0 / uu if uu > _TINY else 0.0
+    rv = 1.0 / vv if vv > _TINY else 0.0
+    den = uu * vv - uv * uv
+    s = _clamp01((uv * vw - vv * uw) / den) if den > 0.0 else 0.0
+    t = (uv * s + vw) * rv
+    tc = _clamp01(t)
+    if tc != t or rv == 0.0:
+        s = _clamp01((uv * tc - uw) * ru)
+    x = w + s * u - tc * v
+    return float(x @ x)
+
+
+def _rotate(q, v):  # v + 2 (w (u x v) + u x (u x v)), q as it is
+    t = np.cross(q[:3], v)
+    return v + 2.0 * (q[3] * t + np.cross(q[:3], t))
+
+
+def _pen2(s, d2):
+    return max(0.0, s - float(np.sqrt(d2))) ** 2 if s > 0 and d2 < s * s else 0.0
+
+
+def _clearance_with_capsules(margin, p, q, pts, caps, obs, ocaps):
+    """the part of the clearance cost that involves a capsule: the link's primitives (points, then capsules; carried over by p + rotate(q, .)) outermost, for each the
+    other side's points, then its capsules (as they are); the point-against-point pairs are the caller's"""
+    total = 0.0
+    for v in pts:
+        w = p + _rotate(q, v[:3])
+        for o in ocaps:
+            total += _pen2((margin + v[3]) + o[3], segment_point_d2(o[:3], o[4:7], w))
+    for k in caps:
+        a, b = p + _rotate(q, k[:3]), p + _rotate(q, k[4:7])
+        for o in obs:
+            total += _pen2((margin + k[3]) + o[3], segment_point_d2(a, b, o[:3]))
+        for o in ocaps:
+            total += _pen2((margin + k[3]) + o[3], segment_segment_d2(a, b, o[:3], o[4:7]))
+    return total
+
+
+def _rows(a, width):
+    return np.zeros((0, width)) if a is None else np.asarray(a, dtype=np.float64).reshape(-1, width)
+
+
 class TouchGoal(LinkGoalBase):
     """goal_types.h:330-377, goal_types.cpp:152-228: the collision shapes of the link touch the plane through `position` with `normal`.  The shapes are the
     link's collision points and disks of the robot model (RobotModel.add_collision_box / _sphere / _points / _cylinder / _cone, or the URDF reader): no FCL."""
@@ -267,11 +329,14 @@ class TouchGoal(LinkGoalBase):
     def params(self):
         return np.concatenate([self.position, self.normal])
 
-    def evaluate(self, frame, points, disks=None):
+    def evaluate(self, frame, points, disks=None, capsules=None):
         """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link), disks [m][8] =
-        RobotModel.collision_disks(link) (optional).  The device's formula in numpy."""
+        RobotModel.collision_disks(link) (optional), capsules [k][8] = RobotModel.collision_capsules(link) (optional: a capsule's support function is the smaller of
+        its two end spheres', so each joins the points as A r and B r -- exact).  The device's formula in numpy."""
         f = np.asarray(frame, dtype=np.float64)
         pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        for k in _rows(capsules, 8):
+            pts = np.vstack([pts, [k[0], k[1], k[2], k[3]], [k[4], k[5], k[6], k[3]]])
         dks = np.zeros((0, 8)) if disks is None else np.asarray(disks, dtype=np.float64).reshape(-1, 8)
         x, y, z, w = f[3:7]
         u = np.array([-x, -y, -z])  # tf2's inverse(): the conjugate
@@ -315,21 +380,26 @@ class ClearanceGoal(LinkGoalBase):
     def params(self):
         return np.array([self.margin_])
 
-    def evaluate(self, frame, points):
-        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link).  The device's formula in numpy
-        (plain multiplications and additions where the device fuses them: equal up to rounding)."""
+    def evaluate(self, frame, points, capsules=None):
+        """The cost on the host: frame = the link's px py pz qx qy qz qw, points [n][4] = RobotModel.collision_points(link), capsules [k][8] =
+        RobotModel.collision_capsules(link) (optional).  The device's formula in numpy (plain multiplications and additions where the device fuses them: equal up
+        to rounding): the points against every obstacle, then the capsules against every obstacle."""
         f = np.asarray(frame, dtype=np.float64)
         pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
+        caps = _rows(capsules, 8)
         obs = self.obstacles_
-        if obs.shape[0] == 0 or pts.shape[0] == 0:
+        if obs.shape[0] == 0 or pts.shape[0] + caps.shape[0] == 0:
             return 0.0
-        u, w = f[3:6], f[6]
-        t = np.cross(u[None], pts[:, :3])
-        world = f[None, :3] + pts[:, :3] + 2.0 * (w * t + np.cross(u[None], t))  # q as it is, not normalised
-        s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
-        d = np.linalg.norm(world[:, None, :] - obs[None, :, :3], axis=2)
-        pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
-        return float((pen * pen).sum())
+        total = 0.0
+        if pts.shape[0]:
+            u, w = f[3:6], f[6]
+            t = np.cross(u[None], pts[:, :3])
+            world = f[None, :3] + pts[:, :3] + 2.0 * (w * t + np.cross(u[None], t))  # q as it is, not normalised
+            s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
+            d = np.linalg.norm(world[:, None, :] - obs[None, :, :3], axis=2)
+            pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
+            total = float((pen * pen).sum())
+        return total + _clearance_with_capsules(self.margin_, f[:3], f[3:], np.zeros((0, 4)), caps, obs, np.zeros((0, 8)))
 
 
 class SelfClearanceGoal(LinkGoalBase):
@@ -358,29 +428,29 @@ class SelfClearanceGoal(LinkGoalBase):
     def params(self):
         return np.array([self.margin_])
 
-    def evaluate(self, frame, other_frame, points, other_points):
+    def evaluate(self, frame, other_frame, points, other_points, capsules=None, other_capsules=None):
         """The cost on the host: frame / other_frame = the link's and the other link's px py pz qx qy qz qw, points [n][4] / other_points [m][4] =
-        RobotModel.collision_points of the two.  The device's formula in numpy (plain multiplications and additions where the device fuses them: equal up to
-        rounding); quaternions as they are, not normalised."""
+        RobotModel.collision_points of the two, capsules [k][8] / other_capsules [k'][8] = RobotModel.collision_capsules of the two (optional).  The device's formula
+        in numpy (plain multiplications and additions where the device fuses them: equal up to rounding); quaternions as they are, not normalised."""
         b, a = np.asarray(frame, dtype=np.float64), np.asarray(other_frame, dtype=np.float64)
         pts = np.asarray(points, dtype=np.float64).reshape(-1, 4)
         obs = np.asarray(other_points, dtype=np.float64).reshape(-1, 4)
-        if obs.shape[0] == 0 or pts.shape[0] == 0:
+        caps, ocaps = _rows(capsules, 8), _rows(other_capsules, 8)
+        if obs.shape[0] + ocaps.shape[0] == 0 or pts.shape[0] + caps.shape[0] == 0:
             return 0.0
-
-        def rotate(q, v):  # v + 2 (w (u x v) + u x (u x v))
-            t = np.cross(q[:3], v)
-            return v + 2.0 * (q[3] * t + np.cross(q[:3], t))
 
         def mul(p, q):
             return np.append(p[3] * q[:3] + q[3] * p[:3] + np.cross(p[:3], q[:3]), p[3] * q[3] - p[:3] @ q[:3])
         c = a[3:] * np.array([-1.0, -1.0, -1.0, 1.0])  # R = concat(invert(A), B)
-        rp, rq = rotate(c, -a[:3]) + rotate(c, b[:3]), mul(c, b[3:])
-        centres = rp[None] + np.array([rotate(rq, v) for v in pts[:, :3]])
-        s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
-        d = np.linalg.norm(centres[:, None, :] - obs[None, :, :3], axis=2)
-        pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
-        return float((pen * pen).sum())
+        rp, rq = _rotate(c, -a[:3]) + _rotate(c, b[:3]), mul(c, b[3:])
+        total = 0.0
+        if pts.shape[0] and obs.shape[0]:
+            centres = rp[None] + np.array([_rotate(rq, v) for v in pts[:, :3]])
+            s = (self.margin_ + pts[:, 3])[:, None] + obs[None, :, 3]
+            d = np.linalg.norm(centres[:, None, :] - obs[None, :, :3], axis=2)
+            pen = np.where(s > 0, np.maximum(0.0, s - d), 0.0)
+            total = float((pen * pen).sum())
+        return total + _clearance_with_capsules(self.margin_, rp, rq, pts, caps, obs, ocaps)
 
 
 class _JointSetGoal(Goal):

@@ -58,6 +58,7 @@ class RobotModel:
         self.link_meshes = {}   # link index -> list of (filename, scale xyz, origin px py pz qx qy qz qw): <mesh> collisions a URDF names; the caller supplies their vertices
         self.link_unsupported = {}  # link index -> kinds of shapes without a point form (add_collision_unsupported)
         self.link_disks = {}    # link index -> list of (cx, cy, cz, r, ax, ay, az, 0): collision disks in the link frame (TouchGoal): the ends of cylinders, the bases of cones
+        self.link_capsules = {}  # link index -> list of (ax, ay, az, r, bx, by, bz, 0): collision capsules in the link frame (ClearanceGoal, SelfClearanceGoal, TouchGoal): a segment's two ends and a radius
         self.link_solids = {}   # link index -> list of (kind, radius, length, origin px py pz qx qy qz qw): <cylinder> collisions a URDF names (resolve_collision_solids)
         self.meshes_resolved = set()  # links of link_meshes whose vertices the caller has supplied (add_collision_points)
         self.groups = {}
@@ -207,13 +208,51 @@ class RobotModel:
         i = link if isinstance(link, int) else self.link_index(link)
         return np.asarray(self.link_disks.get(i, []), dtype=np.float64).reshape(-1, 8)
 
-    def resolve_collision_solids(self, link=None):
+    # ---- capsules: a segment with a radius, the shape ClearanceGoal and SelfClearanceGoal measure a link by (include/bioik_hip.h: CAPSULES) ----
+    def add_collision_capsules(self, link, rows, origin=None):
+        """Raw capsules of `link` (name or index): rows ax ay az r bx by bz (an eighth number, if given, must be 0) -- the two ends of the segment, radius >= 0.
+        The two ends must differ (a sphere is a point row: add_collision_sphere).  origin: as in add_collision_points; both ends are moved by it."""
+        i = link if isinstance(link, int) else self.link_index(link)
+        rows = np.asarray(rows, dtype=np.float64)
+        rows = rows.reshape(-1, 8 if rows.ndim == 2 and rows.shape[1] == 8 else 7)
+        if not np.all(np.isfinite(rows)) or np.any(rows[:, 3] < 0) or (rows.shape[1] == 8 and np.any(rows[:, 7] != 0)):
+            raise ValueError("collision capsules must be finite, their radii >= 0 and their eighth number 0")
+        if np.any(np.all(rows[:, :3] == rows[:, 4:7], axis=1)):
+            raise ValueError("the two ends of a collision capsule coincide: a sphere is a point row (add_collision_sphere)")
+        a, b = rows[:, :3], rows[:, 4:7]
+        if origin is not None and tuple(float(v) for v in origin) != (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0):
+            o = np.asarray(origin, dtype=np.float64).reshape(7)
+            a = np.array([quat_rotate(o[3:], v) + o[:3] for v in a]).reshape(-1, 3)
+            b = np.array([quat_rotate(o[3:], v) + o[:3] for v in b]).reshape(-1, 3)
+        self.link_capsules.setdefault(i, []).extend((float(u[0]), float(u[1]), float(u[2]), float(r), float(v[0]), float(v[1]), float(v[2]), 0.0)
+                                                    for u, r, v in zip(a, rows[:, 3], b))
+        self._keep = None
+
+    def add_collision_capsule(self, link, radius, length, origin=None):
+        """A capsule centred on its origin with its axis along z: the segment from z = -length / 2 to z = +length / 2 (`length` > 0 is the SEGMENT's length: the
+        capsule is length + 2 radius long overall) and every point within `radius` of it."""
+        h = 0.5 * float(length)
+        self.add_collision_capsules(link, [(0.0, 0.0, -h, float(radius), 0.0, 0.0, h)], origin)
+
+    def collision_capsules(self, link):
+        """[n][8] ax ay az r bx by bz 0 of `link` as the device will read them"""
+        i = link if isinstance(link, int) else self.link_index(link)
+        return np.asarray(self.link_capsules.get(i, []), dtype=np.float64).reshape(-1, 8)
+
+    def resolve_collision_solids(self, link=None, cylinders="disks"):
         """Turns every solid the URDF reader recorded (link_solids; of `link`, or of all links) into disks, and takes away exactly what the reader left in
-        its place: one marker row and one link_unsupported entry per solid.  After it a TouchGoal on the link is accepted (unless another marker remains)."""
+        its place: one marker row and one link_unsupported entry per solid.  After it a TouchGoal on the link is accepted (unless another marker remains).
+        cylinders="capsule": a <cylinder radius length> becomes its BOUNDING CAPSULE instead -- the same radius, the segment the cylinder's whole axis -- which is
+        what ClearanceGoal and SelfClearanceGoal can measure (they refuse disks).  AN APPROXIMATION, asked for by name and never taken silently: the capsule
+        contains the cylinder and overshoots it by the radius at each end (its rounded caps).  Cones become their disk and apex either way."""
+        if cylinders not in ("disks", "capsule"):
+            raise ValueError("cylinders: \"disks\" or \"capsule\"")
         links = list(self.link_solids) if link is None else [link if isinstance(link, int) else self.link_index(link)]
         for i in links:
             for kind, radius, length, origin in self.link_solids.pop(i, []):
-                if kind == "cylinder":
+                if kind == "cylinder" and cylinders == "capsule":
+                    self.add_collision_capsule(i, radius, length, origin)
+                elif kind == "cylinder":
                     self.add_collision_cylinder(i, radius, length, origin)
                 else:
                     self.add_collision_cone(i, radius, length, origin)
@@ -333,6 +372,9 @@ class RobotModel:
             drows = [self.link_disks.get(i, ()) for i in range(self.n_links)]
             k["link_disk_first"] = np.concatenate([[0], np.cumsum([len(r) for r in drows])]).astype(np.int32)
             k["link_disks"] = np.asarray([p for r in drows for p in r], dtype=np.float64).reshape(-1, 8)
+            crows = [self.link_capsules.get(i, ()) for i in range(self.n_links)]
+            k["link_capsule_first"] = np.concatenate([[0], np.cumsum([len(r) for r in crows])]).astype(np.int32)
+            k["link_capsules"] = np.asarray([p for r in crows for p in r], dtype=np.float64).reshape(-1, 8)
             self._keep = k
         return self._keep
 
@@ -364,6 +406,9 @@ class RobotModel:
         if len(k["link_disks"]):
             d.link_disk_first = abi.iptr(k["link_disk_first"])
             d.link_disks = abi.dptr(k["link_disks"])
+        if len(k["link_capsules"]):
+            d.link_capsule_first = abi.iptr(k["link_capsule_first"])
+            d.link_capsules = abi.dptr(k["link_capsules"])
         return d
 
 

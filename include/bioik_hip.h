@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: BIOIK_GOAL_SELF_CLEARANCE (opcode 20: the spheres of two links of the robot keep apart; the second link in goal_base_link).
+#define BIOIK_ABI_VERSION 6 /* 6, additions that break no caller of 6: bioik_model_desc::link_capsule_first / link_capsules behind the fields every caller of 6 fills (a shorter struct_size
+                               gets none), BIOIK_MAX_LINK_CAPSULES (CAPSULES: a segment with a radius as a link's collision shape; opcodes 17, 19 and 20 read it, no new opcode).
+                               6, additions that break no caller of 6: BIOIK_GOAL_SELF_CLEARANCE (opcode 20: the spheres of two links of the robot keep apart; the second link in goal_base_link).
                                6, additions that break no caller of 6: BIOIK_GOAL_CLEARANCE (opcode 19; 18 stays unknown), BIOIK_MAX_OBSTACLES, bioik_problem_set_obstacles,
                                bioik_problem_obstacle_count (a link's spheres keep clear of a table of obstacle spheres).
                                6, additions that break no caller of 6: bioik_problem_desc::goal_base_link behind the fields every caller of 6 fills (a shorter struct_size gets none),
@@ -103,8 +105,11 @@ enum {
                                             and the cost is d * d.  No FCL: a box is its 8 corners, a sphere one point with a radius, a mesh its
                                             vertices, a cylinder its two end disks, a cone its base disk and its apex (the support function along
                                             the normal, what the reference's hill climb returns; a disk's is exact in closed form, and n_l is not
-                                            assumed to be of unit length).  A link with neither points nor disks: BIOIK_ERR_INVALID_ARGUMENT; more
-                                            than BIOIK_MAX_TOUCH_POINTS points and disks together: BIOIK_ERR_UNSUPPORTED                        */
+                                            assumed to be of unit length).  A CAPSULE of the link (link_capsules: ends A, B, radius r) joins the points as
+                                            its two end spheres (A, r) and (B, r): along any normal the support of a capsule is the smaller of theirs, so
+                                            this is exact; bioik_problem_create appends the two rows per capsule behind the link's points.  A link with
+                                            neither points nor disks nor capsules: BIOIK_ERR_INVALID_ARGUMENT; more than BIOIK_MAX_TOUCH_POINTS points and
+                                            disks together, a capsule counting as two points: BIOIK_ERR_UNSUPPORTED                                */
     BIOIK_GOAL_TYPE_COUNT = 18,          /* the opcodes 0 ... 17 are the reference's closed-form classes.  OPCODE 18 IS NO GOAL AND STAYS UNKNOWN: bioik_goal_param_count(18) is -1
                                             and bioik_problem_create refuses it (callers and tests of ABI 6 rely on that) */
     BIOIK_GOAL_CLEARANCE = 19            /* no reference counterpart (there: a solution_callback behind the search).  params: margin.  The spheres of the link keep at least
@@ -126,9 +131,11 @@ enum {
                                             weighted cost < min(dpos, dtwist)^2 -- "clear of every obstacle by the margin, up to the threshold".  A secondary
                                             ClearanceGoal reads the null frame, like every secondary link goal of this library.  jac, gd*, ranked, bounded, migration,
                                             timeout and island_sync behave as for a problem with a TouchGoal; such a problem runs in the general kernel flavour.
-                                            Refused by bioik_problem_create: a link without points BIOIK_ERR_INVALID_ARGUMENT; a link that carries disks or a marker row
-                                            (r == -1: never approximated silently), more than BIOIK_MAX_TOUCH_POINTS points, a base link on the goal (self-collision):
-                                            BIOIK_ERR_UNSUPPORTED.  About nine FP64 issue slots per pair that does not penetrate and eighteen per point (counted in the
+                                            CAPSULES of the link (below the opcodes): its k capsules follow its n points -- each against every obstacle j, ascending, into
+                                            the same running sum.  Refused by bioik_problem_create: a link with neither points nor capsules
+                                            BIOIK_ERR_INVALID_ARGUMENT; a link that carries disks or a marker row (r == -1: never approximated silently), more than
+                                            BIOIK_MAX_LINK_CAPSULES capsules, more than BIOIK_MAX_TOUCH_POINTS points and capsules together, a base link on the goal
+                                            (self-collision): BIOIK_ERR_UNSUPPORTED.  About nine FP64 issue slots per pair that does not penetrate and eighteen per point (counted in the
                                             code, not timed): 8 points against 16 obstacles cost about as much as the chain walk of a 7-joint arm
                                             (measured rates: profiles/clearance_goal_metadata_and_bench.log) */
     ,
@@ -150,13 +157,46 @@ enum {
                                             for any problem with a based goal: BIOIK_MODE_JAC is refused at the solve call.  The goal (L, O) and the goal (O, L) state the
                                             same distances and differ in the order of summation: equal up to rounding, not bit for bit.
                                             Refused by bioik_problem_create, the message naming the goal's index: no other link (-1, a NULL goal_base_link, a struct_size
-                                            that ends in front of the field), a goal that names no link, the other link the goal's own, either link without points:
-                                            BIOIK_ERR_INVALID_ARGUMENT; either link with disks or a marker row (r == -1: never approximated), L with more than
-                                            BIOIK_MAX_TOUCH_POINTS points, O with more than BIOIK_MAX_OBSTACLES, a secondary goal, more than BIOIK_MAX_HELD_FRAMES held
-                                            links: BIOIK_ERR_UNSUPPORTED; an unknown other link: BIOIK_ERR_NOT_FOUND.  bioik_problem_set_obstacles and
-                                            bioik_problem_obstacle_count say "not a CLEARANCE goal" of it.  Such a problem runs in the general kernel flavour.  Not built:
-                                            capsules, a broad phase, pairs taken automatically from an SRDF's collision matrix
-                                            (measured: profiles/self_clearance_metadata_and_bench.log) */
+                                            that ends in front of the field), a goal that names no link, the other link the goal's own, either link with neither points
+                                            nor capsules: BIOIK_ERR_INVALID_ARGUMENT; either link with disks or a marker row (r == -1: never approximated), either link
+                                            with more than BIOIK_MAX_LINK_CAPSULES capsules, L with more than BIOIK_MAX_TOUCH_POINTS points and capsules together, O with
+                                            more than BIOIK_MAX_OBSTACLES, a secondary goal, more than BIOIK_MAX_HELD_FRAMES held links: BIOIK_ERR_UNSUPPORTED; an unknown
+                                            other link: BIOIK_ERR_NOT_FOUND.  bioik_problem_set_obstacles and bioik_problem_obstacle_count say "not a CLEARANCE goal" of
+                                            it.  Such a problem runs in the general kernel flavour.
+                                            CAPSULES of either link (below): L's primitives are outermost, its points, then its capsules; for each of them O's points come
+                                            first, then O's capsules; everything in O's frame through the same R; one running sum.  A capsule of O needs no transform
+                                            (its u, u.u and ru are formed once, when the problem is created, by the operations below: the same bits); a capsule of L has
+                                            its two ends carried over once, in front of the inner loops.  Not built: a broad phase, pairs taken automatically from an
+                                            SRDF's collision matrix, capsules or boxes in the obstacle table of opcode 19
+                                            (measured: profiles/self_clearance_metadata_and_bench.log, profiles/capsules_metadata_and_bench.log) */
+    /* CAPSULES (bioik_model_desc::link_capsules; no opcode of their own: opcodes 19 and 20 measure against them, opcode 17 reads each as two spheres).  A capsule is
+       a segment with a radius r >= 0: every point within r of the segment.  Write A, B for its two ends CARRIED INTO THE FRAME THE GOAL WORKS IN -- the world
+       through the link's frame (p, q) for opcode 19, O's frame through R for a capsule of L under opcode 20 -- by the same p + rotate(q, v) as a point's, with q as
+       it is, not normalised (the phenotypes of BIOIK_FK_LINEAR included); a capsule of O under opcode 20 is taken as it stands.  Every operation below is rounded
+       once; fma(a, b, c) = a b + c with one rounding; x.y of two vectors is fma(x.x, y.x, fma(x.y, y.y, x.z y.z)); clamp(x) = min(max(x, 0), 1).
+       Per segment (A, B), formed once per segment and not per pair:
+           u = B - A (three subtractions)      uu = u.u      ru = uu > DBL_MIN ? 1 / uu : 0          (one division, correctly rounded)
+       ru = 0 makes the segment count as its FIRST END: the zero quaternion of a linearised phenotype collapses every segment of a link to a point (A == B == p), and
+       0 / 0 is never formed.
+       SPHERE (c, R) AGAINST CAPSULE (A, B, r):
+           e = c - A (three subtractions)      t = clamp((e.u) ru)
+           X = A + t u:  fma(t, u.x, A.x) ... per component          x = c - X (three subtractions)          d2 = x.x
+       CAPSULE (A, B, r1) AGAINST CAPSULE (C, D, r2), (A, B) the capsule of the goal's link, with u, uu, ru of (A, B) and v, vv, rv of (C, D):
+           w = A - C (three subtractions)      uv = u.v      uw = u.w      vw = v.w
+           den = fma(uu, vv, -(uv uv))                                                                 (= uu vv sin^2 of the angle between the axes)
+           s = den > 0 ? clamp(fma(uv, vw, -(vv uw)) / den) : 0                                        the two-line solution; 0 for parallel axes
+           t = fma(uv, s, vw) rv               tc = clamp(t)
+           if (tc != t || rv == 0)  s = clamp(fma(uv, tc, -uw) ru)                                     t left [0, 1] (or (C, D) counts as a point): s solved again
+           X = A + s u,  Y = C + tc v  (fma per component, as above)          x = X - Y (three subtractions)          d2 = x.x
+       Then for both, with the radius of the GOAL'S LINK's primitive first (for opcode 20: L's, whether it is the sphere or the capsule):
+           s_pair = (margin + r_link) + r_other
+           if (s_pair > 0 && d2 < s_pair s_pair) { pen = max(0, s_pair - sqrt(d2));  sum = fma(pen, pen, sum); }     opcode 19's tail, word for word
+       d2 is the squared distance of two points that lie ON the two primitives, so it is never below the true squared distance; it exceeds it only through the
+       error of s, which is large relative to 1 only where den cancels (axes within about 1e-7 rad of parallel: up to a few 1e-8 m on segments of 0.3 m; exactly
+       parallel axes are exact, any s gives the same distance).  No finite input whose squares stay finite yields a NaN or an infinity: every quotient has a
+       denominator > 0 or is replaced by 0, and clamp() returns 0 or 1 for an infinite argument.
+       One routine per formula serves every site (bio_ik_amd/csrc/bioik_device.h: seg_make, seg_point_d2, seg_seg_d2, clearance_tail).  A model WITHOUT capsules
+       gives, for both opcodes, exactly the bits it gave before capsules existed (tests/golden/clearance_parent_bits.npz). */
     /* JointFunctionGoal / LinkFunctionGoal (std::function) have no device opcode: DESIGN.md §7. */
 };
 /* Obstacle spheres one BIOIK_GOAL_CLEARANCE may hold (every evaluation of every individual reads all of them against every point of the link). */
@@ -169,6 +209,9 @@ enum {
  * squared norm, fourteen for the square root (a reciprocal square root estimate, its refinement to the correctly rounded root and the scaling around it), three
  * for n . c, and the closing fused multiply-add, minimum and canonicalisation (again counted in the compiled loop, not timed). */
 #define BIOIK_MAX_TOUCH_POINTS 1024
+/* Capsules one goal may read from one link (CAPSULES at the goal opcodes).  Points and capsules of a goal's link together stay within BIOIK_MAX_TOUCH_POINTS, those of
+ * BIOIK_GOAL_SELF_CLEARANCE's other link within BIOIK_MAX_OBSTACLES; for BIOIK_GOAL_TOUCH a capsule counts as two points. */
+#define BIOIK_MAX_LINK_CAPSULES 64
 
 /* number of per-query parameter doubles of a goal opcode, or -1 for an unknown opcode */
 int bioik_goal_param_count(int goal_type);
@@ -247,7 +290,7 @@ typedef struct bioik_model_desc {
     const double* link_mass;             /* [n_links] urdf::Link::inertial->mass, 0 where the link has no <inertial>; NULL: no link
                                             has one (only BIOIK_GOAL_BALANCE reads it, goal_types.cpp:236-247)                  */
     const double* link_center;           /* [n_links*3] urdf::Link::inertial->origin.position (link frame); NULL with link_mass   */
-    /* Collision points of the links (only BIOIK_GOAL_TOUCH reads them), in compressed rows: link l owns the points link_point_first[l] ... link_point_first[l + 1]
+    /* Collision points of the links (BIOIK_GOAL_TOUCH reads them, BIOIK_GOAL_CLEARANCE and BIOIK_GOAL_SELF_CLEARANCE as spheres), in compressed rows: link l owns the points link_point_first[l] ... link_point_first[l + 1]
        - 1.  A point is x y z r IN THE LINK FRAME (the shape's collision origin already applied by the caller), r >= 0 the radius of a sphere around it.  A row with
        r == -1 exactly is no point but a MARKER (any other negative radius is BIOIK_ERR_INVALID_ARGUMENT): the link carries a mesh whose vertices are not there, or a shape the caller did not convert into points or disks (a cylinder or a cone it left as it was) -- the model is accepted, a BIOIK_GOAL_TOUCH that names
        the link is refused with BIOIK_ERR_UNSUPPORTED (such a shape is never approximated silently).  Both NULL: no link has shapes.  A caller whose struct_size ends in front of these two fields (a build against the header without them) gets none.                    */
@@ -260,6 +303,14 @@ typedef struct bioik_model_desc {
        link_point_first (builds against the two earlier headers), gets none; a size between two of the three is BIOIK_ERR_INVALID_ARGUMENT.                  */
     const int32_t* link_disk_first;      /* [n_links + 1] ascending, [0] = 0                                                       */
     const double* link_disks;            /* [link_disk_first[n_links] * 8]                                                         */
+    /* Collision capsules of the links (CAPSULES at the goal opcodes: BIOIK_GOAL_CLEARANCE and BIOIK_GOAL_SELF_CLEARANCE measure against them, BIOIK_GOAL_TOUCH reads each as its two
+       end spheres), rows like the disks': link l owns the capsules link_capsule_first[l] ... link_capsule_first[l + 1] - 1.  A capsule is ax ay az r bx by bz 0 IN THE
+       LINK FRAME: the two ends A and B of a segment, a radius r >= 0, and a zero that fills the row -- every point within r of the segment.  BIOIK_ERR_INVALID_ARGUMENT:
+       a number that is not finite, r < 0, an eighth number that is not 0, A == B (a sphere is a point row of link_points).  Both NULL: no link has capsules.  A caller
+       whose struct_size ends in front of these two fields (or in front of one of the two earlier pairs: builds against the three earlier headers) gets none; a size
+       between two of the four, or beyond the struct, is BIOIK_ERR_INVALID_ARGUMENT. */
+    const int32_t* link_capsule_first;   /* [n_links + 1] ascending, [0] = 0                                                       */
+    const double* link_capsules;         /* [link_capsule_first[n_links] * 8]                                                      */
 } bioik_model_desc;
 
 /* ---- one goal of the problem template (structure shared by every query of a batch; the numeric
@@ -397,6 +448,7 @@ void bioik_model_destroy(bioik_model* m);
  * chain in front of a branch counts once per branch), 63 active variables, 64 tip links, 24 primary + 24 secondary goals, 4 BalanceGoals,
  * BIOIK_MAX_TOUCH_POINTS collision points and disks together per TouchGoal (gathered once into a device buffer the handle owns: global memory, no LDS),
  * BIOIK_MAX_TOUCH_POINTS points per ClearanceGoal and BIOIK_MAX_OBSTACLES obstacles in its table (the same buffer; the table's storage is there at full capacity from the start).
+ * Capsules: BIOIK_MAX_LINK_CAPSULES per link a ClearanceGoal or SelfClearanceGoal reads, counted with that link's points towards the limits above.
  * Tips and joints are further bounded TOGETHER by the 160 KiB of LDS of a CU: the function-level entry points hold 7 x tips x joints doubles
  * of tables plus a genotype column per lane (64 tips on 12 joints: 71 KiB; 24 tips on 63 joints: about 137 KiB; 64 tips on 63 joints: about
  * 290 KiB), the solvers hold more.  A problem beyond that is accepted here and refused with BIOIK_ERR_UNSUPPORTED by every entry point that
