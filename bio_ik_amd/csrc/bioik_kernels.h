@@ -1973,123 +1973,294 @@ BIOIK_DEV void solve_memetic(Frame& F, SpeciesState& S, double*& popS, int rank_
                 if constexpr (DENSE) all = acc + 0.0;  // (the launcher gives the dense kernel problems without secondary goals only: the empty sum)
                 else all = want_all ? acc + secondary_shared(x, xsh, tm) : acc;
             };
-            for (int k = gtid; k < n_ops; k += Gw) s_gop[k] = 0.0;
-            const bool odd = gtid & 1;
-            bool descending = true;
-            double f2p = 0.0, fa = 0.0;  // primary fitness / all goals at the elite, as the last gradient round left them
-            for (int it = 0; it < 8 && descending; it++) {
-                PHASE_COUNT(PH_N_MEM_ITER);
-                // three rounds of the same shape -- op lanes prepare displacement vectors, component lanes run the chains, every
-                // lane evaluates the goals on its frames -- written as one loop so that each piece of code exists once:
-                //   round 0  gradient (:450-475): D + 1 evaluations, one per lane
-                //   round 1  L1 normalisation (:477-482) and the two support points x - g (even lanes), x + g (odd lanes) (:485-495)
-                //   round 2  step along the gradient (:498-568), clipped candidate, acceptance on primary fitness
-                // Round 6: round 2 IS the next iteration's round 0.  An accepted candidate becomes the elite, and the gradient round that follows evaluates
-                // that very vector (lane D) and the D vectors with one gene advanced by dp (lanes i < D) -- on the candidate's frames, which round 2 has
-                // just built: the same displacements x4 - base, the same chains, the same goals.  So round 2 evaluates all D + 1 of them (a wavefront
-                // instruction costs the same for one lane as for eight), lane D's primary fitness decides, and on acceptance the gradient of the next
-                // iteration is already there: every iteration but the first is two rounds instead of three.  A rejected candidate's gradient is dropped
-                // (the species stops).  Same operations on the same operands: the same bits.
-                double fnorm = 0.0;
-                bool nan_gene = false;  // (round 2: a gene of the candidate is not a number)
-                for (int round = it == 0 ? 0 : 1; round < 3; round++) {
-                    double* dv0 = s_dv + (round == 0 ? 0 : round == 1 ? 1 : 3) * M;
-                    double* fc0 = (L.fc >= 0 ? s_fc : popS + (S.cur ^ 1) * BF) + (round == 0 ? 0 : round == 1 ? 1 : 3) * FB;  // (make_layout: fc_in_pop)
-                    if (round == 0) {
-                        for (int k = gtid; k < n_ops; k += Gw) dv0[k] = ((active_mask >> k) & 1ull) ? el[k] - s_base[k] : 0.0;
-                    } else if (round == 1) {
-                        double sum = dp * dp;
-                        for (int i = 0; i < D; i++) sum += fabs(s_grad[i]);
-                        fnorm = 1.0 / sum * dp;
-                        PHASE_MARK(PH_MEM_NORM);
-                        for (int k = gtid; k < n_ops; k += Gw) {
-                            const double e = el[k], g = s_gop[k] * fnorm, b = s_base[k];
-                            const bool on = (active_mask >> k) & 1ull;
-                            const double xm = e - g, xp = e + g;
-                            s_xm[k] = xm, s_xp[k] = xp;
-                            dv0[k] = on ? xm - b : 0.0;
-                            dv0[M + k] = on ? xp - b : 0.0;
+            if constexpr (DENSE) {
+                // The dense build's own form of the loop below: the same rounds, the same floating-point operations on the same operands in the same order, written
+                // for what its launcher guarantees (dense_shape / dense_ok, bioik_hip.hip): a group is HALF a wavefront (32 lanes), the genes follow the ops, no
+                // secondary goal, a serial chain of at most 64 ops.  What the general form pays per round and this one does not:
+                //   op lanes     lane k owns op k for the whole phase: its bit of active_mask, its entries of s_base / s_clip and the elite's gene el[k] are read once
+                //                and kept in registers (the elite's gene follows an accepted candidate), and each preparation is one predicated statement instead
+                //                of a loop `for k = gtid; k < n_ops; k += Gw`.  (Ops 32 ... 63 of a longer chain: a second statement that reads what it needs from
+                //                LDS as the general form does -- the rare case keeps no registers.)
+                //   chains       one index over s_delta and the displacements, four ops per trip and a remainder loop of single ops: exactly n_ops fused
+                //                multiply-adds per chain in ascending op order from s_tips (no padded trip, no select, no `kk * 7`; four multiply-adds and two
+                //                address updates per trip); one or two chains per lane as two instantiations, not a test per op; the lane's component is set up
+                //                once per phase, not per round
+                //   gradient     g[k] = s_gop[k] * fnorm is computed in the support round and kept for the candidate's round (the same product of the same operands)
+                // The exchanges between lanes (s_ex, s_grad, s_gop) stay LDS writes and reads of one wavefront in program order: a lane read of a double for two
+                // halves is four v_readlane and two selects, more issue slots than the LDS round trip it would replace.
+                const bool in0 = gtid < n_ops, wide = n_ops > 32, in1 = wide && gtid + 32 < n_ops;
+                const int k1 = gtid + 32;
+                const bool on0 = in0 && ((active_mask >> gtid) & 1ull), on1 = in1 && ((active_mask >> k1) & 1ull);
+                const double base0 = in0 ? s_base[gtid] : 0.0, cmin0 = in0 ? s_clip[gtid] : 0.0, cmax0 = in0 ? s_clip[M + gtid] : 0.0;
+                double e0 = in0 ? el[gtid] : 0.0;  // the elite's gene of this lane's op
+                double* const fcb = L.fc >= 0 ? s_fc : popS + (S.cur ^ 1) * BF;  // (make_layout: fc_in_pop)
+                // component lanes: lane 8 t + c runs component c < 7 of tip t.  Up to four tips are one pass over the half, and the lane's own component -- where its
+                // chain starts and where its deltas lie -- is set up here, once for all rounds; components 32 and up (five tips or more) are set up where they run
+                const int n4 = n_ops & ~3;
+                const bool comp0 = gtid < FB && (gtid & 7) != 7;
+                const double tip0 = comp0 ? s_tips[(gtid >> 3) * 7 + (gtid & 7)] : 0.0;
+                const double* const dl0 = s_delta + ((gtid >> 3) * n_ops * 7 + (gtid & 7));
+                auto chain_of = [&](auto two, const double start, const double* dl, const double* u, double* out) {
+                    constexpr bool TWO = decltype(two)::value;
+                    const double* w = u + M;
+                    double a0 = start, a1 = start;
+                    for (int g = 0; g < n4; g += 4) {
+                        const double d_0 = dl[g * 7], d_1 = dl[g * 7 + 7], d_2 = dl[g * 7 + 14], d_3 = dl[g * 7 + 21];
+                        const double u_0 = u[g], u_1 = u[g + 1], u_2 = u[g + 2], u_3 = u[g + 3];
+                        a0 = BK_FMA(d_0, u_0, a0), a0 = BK_FMA(d_1, u_1, a0), a0 = BK_FMA(d_2, u_2, a0), a0 = BK_FMA(d_3, u_3, a0);
+                        if constexpr (TWO) {
+                            const double w_0 = w[g], w_1 = w[g + 1], w_2 = w[g + 2], w_3 = w[g + 3];
+                            a1 = BK_FMA(d_0, w_0, a1), a1 = BK_FMA(d_1, w_1, a1), a1 = BK_FMA(d_2, w_2, a1), a1 = BK_FMA(d_3, w_3, a1);
                         }
-                    } else {
-                        const double f1 = s_ex[2], f3 = s_ex[3], f2 = fa;
-                        double step_size;
-                        if (sp.memetic == 'q') {  // :498-539
-                            double v1 = f2 - f1, v2 = f3 - f2;
-                            double v = (v1 + v2) * 0.5, aa = v1 - v2;
-                            step_size = v / aa;
-                        } else {  // 'l' :545-568
-                            double cost_diff = (f3 - f1) * 0.5;
-                            step_size = -(f2 / cost_diff);
-                        }
-                        // A step that is not a number: three equal support values make the quadratic step 0 / 0, the linear one f2 / 0 -- and 0 * inf for
-                        // a gene the gradient does not move.  The reference's clip lets a NaN through (utils.h:328-333), its candidate's fitness is NaN and
-                        // fails the comparison below: the search stops.  fmin / fmax would make the lower limit of a NaN (-DBL_MAX for a joint without
-                        // limits) and the candidate a jump there; so a candidate with a NaN gene is no candidate.  (Where a goal hides the NaN -- max(0, .)
-                        // of its error -- the literal reference ACCEPTS the NaN genes and can return them: quirk Q5)
-                        // A step without bound -- v / 0 of a model without curvature -- puts a joint WITHOUT limits at its clip range's end, +-DBL_MAX
-                        // (robot_info.h:109-113), where the linear model overflows; the literal reference may accept that vector and return it (quirk Q7,
-                        // DESIGN.md section 3).  A candidate with a gene of magnitude BIOIK_CANDIDATE_BOUND or more is no candidate either: the search stops.  (The bound is
-                        // the end of the shared sincos's domain, 2^47: a rotation is periodic, so a candidate at 1e10 rad is an ordinary pose -- and must be the pose
-                        // the caller's own trigonometry makes of that value; half angle = factor x gene / 2, inside the domain for mimic factors up to 2.)
-                        bool nan_here = false;
-                        for (int k = gtid; k < n_ops; k += Gw) {
-                            const double e = el[k], gv = s_gop[k] * fnorm;
-                            const bool on = (active_mask >> k) & 1ull;
-                            const double raw = e + gv * step_size;
-                            const bool is_nan = on && !(raw == raw);
-                            const double x4 = (on && !is_nan) ? fmin(fmax(raw, s_clip[k]), s_clip[M + k]) : e;
-                            nan_here = nan_here || is_nan || (on && fabs(x4) >= BIOIK_CANDIDATE_BOUND);
-                            s_x4[k] = x4;
-                            dv0[k] = on ? x4 - s_base[k] : 0.0;
-                        }
-                        nan_gene = (p_ballot(nan_here) & (G >= 64 ? ~0ull : 0xffffffffull << (tid & 32))) != 0ull;
                     }
-                    p_wave_sync();
-                    PHASE_MARK(PH_MEM_SUPPORT_COLS);
-                    chains(dv0, fc0, round == 1 ? dv0 + M : nullptr, fc0 + FB);
-                    p_wave_sync();
-                    double vprim, vall;
-                    // what joint-value goals read: the lane's own vector -- in the gradient round the elite with its gene advanced by dp
-                    // (computed where it is read, no column), else the shared support point / candidate
-                    const bool grad_round = round != 1;  // (the candidate's round too: lanes i < D advance gene i on the candidate's frames)
-                    const PerturbX xq{round == 0 ? el : (round == 2 ? s_x4 : (odd ? s_xp : s_xm)), grad_round ? my_op : -1, grad_round ? dp : 0.0};
-                    // (the vectors whose terms the lanes share: the elite / the candidate, or the two support points -- even lanes read the first's sums, odd lanes the second's)
-                    const PerturbX xs{round == 0 ? el : (round == 2 ? s_x4 : s_xm), grad_round ? my_op : -1, grad_round ? dp : 0.0, round == 1 ? s_xp : nullptr};
-                    goals_on(fc0 + ((round == 1 && odd) ? FB : 0), grad_round ? my_op : -1, grad_round ? dp : 0.0, xq, vprim, vall, true, xs,
-                             s_tm + ((round == 1 && odd) ? 3 * M : 0));
-                    PHASE_MARK(PH_MEM_SUPPORT_EVAL);
-                    if (round == 0) {
-                        if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;
-                        p_wave_sync();
-                        f2p = s_ex[0], fa = s_ex[1];
-                        if (my_op >= 0) {
-                            s_grad[gtid] = vall - fa;
-                            s_gop[my_op] = vall - fa;
+                    for (int g = n4; g < n_ops; g++) {
+                        const double d_0 = dl[g * 7];
+                        a0 = BK_FMA(d_0, u[g], a0);
+                        if constexpr (TWO) a1 = BK_FMA(d_0, w[g], a1);
+                    }
+                    out[0] = a0;
+                    if constexpr (TWO) out[FB] = a1;
+                };
+                auto chains_n = [&](auto two, const double* dvp, double* fcp) {
+                    if (comp0) chain_of(two, tip0, dl0, dvp, fcp + gtid);
+                    if (FB > 32)
+                        for (int idx = gtid + 32; idx < FB; idx += 32) {
+                            const int t = idx >> 3, c = idx & 7;
+                            if (c != 7) chain_of(two, s_tips[t * 7 + c], s_delta + (t * n_ops * 7 + c), dvp, fcp + idx);
                         }
-                        p_wave_sync();
-                        PHASE_MARK(PH_MEM_GRAD);
-                    } else if (round == 1) {
-                        if (gtid < 2) s_ex[2 + gtid] = vall;
-                        p_wave_sync();
-                    } else {
-                        if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;  // the candidate itself (the other lanes: the candidate with a gene advanced)
-                        p_wave_sync();
-                        const double cprim = s_ex[0], call = s_ex[1];
-                        const bool accept = !nan_gene && cprim < f2p;  // accept iff the primary fitness improves, else stop (:527-538)
-                        // (a half-wave group shares its wavefront with the other species: it stays in step with it and merely
-                        // repeats the rejected iteration from its support points on, which changes nothing -- its elite, its gradient and the
-                        // fitness values that belong to them stay as they are -- until the other species has stopped as well)
-                        if (G >= 64 ? !accept : p_ballot(accept) == 0ull) descending = false;
-                        if (accept) {
-                            for (int k = gtid; k < n_ops; k += Gw) el[k] = s_x4[k];
-                            f2p = cprim, fa = call;  // the candidate is the elite: what the gradient round of the next iteration would compute
-                            if (my_op >= 0) {
-                                s_grad[gtid] = vall - call;
-                                s_gop[my_op] = vall - call;
+                };
+                if (in0) s_gop[gtid] = 0.0;
+                if (in1) s_gop[k1] = 0.0;
+                const bool odd = gtid & 1;
+                bool descending = true;
+                double f2p = 0.0, fa = 0.0;  // primary fitness / all goals at the elite, as the last gradient round left them
+                for (int it = 0; it < 8 && descending; it++) {
+                    PHASE_COUNT(PH_N_MEM_ITER);
+                    double fnorm = 0.0, g0 = 0.0, x40 = 0.0;  // (g0: this lane's entry of the normalised gradient; x40: of the candidate)
+                    bool nan_gene = false;
+                    for (int round = it == 0 ? 0 : 1; round < 3; round++) {
+                        const int row = round == 0 ? 0 : round == 1 ? 1 : 3;
+                        double* dv0 = s_dv + row * M;
+                        double* fc0 = fcb + row * FB;
+                        if (round == 0) {
+                            if (in0) dv0[gtid] = on0 ? e0 - base0 : 0.0;
+                            if (in1) dv0[k1] = on1 ? el[k1] - s_base[k1] : 0.0;
+                        } else if (round == 1) {
+                            double sum = dp * dp;
+                            const int D4 = D & ~3;  // (one sum, gene after gene: four reads at constant offsets per trip, then the last one to three)
+                            for (int i = 0; i < D4; i += 4) sum += fabs(s_grad[i]), sum += fabs(s_grad[i + 1]), sum += fabs(s_grad[i + 2]), sum += fabs(s_grad[i + 3]);
+                            for (int i = D4; i < D; i++) sum += fabs(s_grad[i]);
+                            fnorm = 1.0 / sum * dp;
+                            PHASE_MARK(PH_MEM_NORM);
+                            if (in0) {
+                                g0 = s_gop[gtid] * fnorm;
+                                const double xm = e0 - g0, xp = e0 + g0;
+                                s_xm[gtid] = xm, s_xp[gtid] = xp;
+                                dv0[gtid] = on0 ? xm - base0 : 0.0;
+                                dv0[M + gtid] = on0 ? xp - base0 : 0.0;
                             }
+                            if (in1) {
+                                const double e = el[k1], g = s_gop[k1] * fnorm, b = s_base[k1];
+                                const double xm = e - g, xp = e + g;
+                                s_xm[k1] = xm, s_xp[k1] = xp;
+                                dv0[k1] = on1 ? xm - b : 0.0;
+                                dv0[M + k1] = on1 ? xp - b : 0.0;
+                            }
+                        } else {
+                            const double f1 = s_ex[2], f3 = s_ex[3], f2 = fa;
+                            double step_size;
+                            if (sp.memetic == 'q') {  // :498-539
+                                double v1 = f2 - f1, v2 = f3 - f2;
+                                double v = (v1 + v2) * 0.5, aa = v1 - v2;
+                                step_size = v / aa;
+                            } else {  // 'l' :545-568
+                                double cost_diff = (f3 - f1) * 0.5;
+                                step_size = -(f2 / cost_diff);
+                            }
+                            // (the rule for a step that is not a number or without bound: see the general form below)
+                            bool nan_here = false;
+                            {
+                                const double raw = e0 + g0 * step_size;
+                                const bool is_nan = on0 && !(raw == raw);
+                                x40 = (on0 && !is_nan) ? p_clamp(raw, cmin0, cmax0) : e0;
+                                nan_here = is_nan || (on0 && fabs(x40) >= BIOIK_CANDIDATE_BOUND);
+                                if (in0) s_x4[gtid] = x40, dv0[gtid] = on0 ? x40 - base0 : 0.0;
+                            }
+                            if (in1) {
+                                const double e = el[k1], gv = s_gop[k1] * fnorm;
+                                const double raw = e + gv * step_size;
+                                const bool is_nan = on1 && !(raw == raw);
+                                const double x4 = (on1 && !is_nan) ? fmin(fmax(raw, s_clip[k1]), s_clip[M + k1]) : e;
+                                nan_here = nan_here || is_nan || (on1 && fabs(x4) >= BIOIK_CANDIDATE_BOUND);
+                                s_x4[k1] = x4;
+                                dv0[k1] = on1 ? x4 - s_base[k1] : 0.0;
+                            }
+                            nan_gene = (p_ballot(nan_here) & (0xffffffffull << (tid & 32))) != 0ull;
                         }
                         p_wave_sync();
-                        PHASE_MARK(PH_MEM_ACCEPT);
+                        PHASE_MARK(PH_MEM_SUPPORT_COLS);
+                        if (round == 1) chains_n(std::true_type{}, dv0, fc0);
+                        else chains_n(std::false_type{}, dv0, fc0);
+                        p_wave_sync();
+                        double vprim, vall;
+                        const bool grad_round = round != 1;  // (the candidate's round too: lanes i < D advance gene i on the candidate's frames)
+                        const PerturbX xq{round == 0 ? el : (round == 2 ? s_x4 : (odd ? s_xp : s_xm)), grad_round ? my_op : -1, grad_round ? dp : 0.0};
+                        goals_on(fc0 + ((round == 1 && odd) ? FB : 0), grad_round ? my_op : -1, grad_round ? dp : 0.0, xq, vprim, vall, true, xq, s_tm);
+                        PHASE_MARK(PH_MEM_SUPPORT_EVAL);
+                        if (round == 0) {
+                            if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;
+                            p_wave_sync();
+                            f2p = s_ex[0], fa = s_ex[1];
+                            if (my_op >= 0) {
+                                s_grad[gtid] = vall - fa;
+                                s_gop[my_op] = vall - fa;
+                            }
+                            p_wave_sync();
+                            PHASE_MARK(PH_MEM_GRAD);
+                        } else if (round == 1) {
+                            if (gtid < 2) s_ex[2 + gtid] = vall;
+                            p_wave_sync();
+                        } else {
+                            if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;  // the candidate itself (the other lanes: the candidate with a gene advanced)
+                            p_wave_sync();
+                            const double cprim = s_ex[0], call = s_ex[1];
+                            const bool accept = !nan_gene && cprim < f2p;  // accept iff the primary fitness improves, else stop (:527-538)
+                            // (the half that has stopped stays in step with the other and repeats its rejected iteration from the support points on: see below)
+                            if (p_ballot(accept) == 0ull) descending = false;
+                            if (accept) {
+                                if (in0) el[gtid] = x40;
+                                if (in1) el[k1] = s_x4[k1];
+                                e0 = x40;
+                                f2p = cprim, fa = call;  // the candidate is the elite: what the gradient round of the next iteration would compute
+                                if (my_op >= 0) {
+                                    s_grad[gtid] = vall - call;
+                                    s_gop[my_op] = vall - call;
+                                }
+                            }
+                            p_wave_sync();
+                            PHASE_MARK(PH_MEM_ACCEPT);
+                        }
+                    }
+                }
+            } else {
+                for (int k = gtid; k < n_ops; k += Gw) s_gop[k] = 0.0;
+                const bool odd = gtid & 1;
+                bool descending = true;
+                double f2p = 0.0, fa = 0.0;  // primary fitness / all goals at the elite, as the last gradient round left them
+                for (int it = 0; it < 8 && descending; it++) {
+                    PHASE_COUNT(PH_N_MEM_ITER);
+                    // three rounds of the same shape -- op lanes prepare displacement vectors, component lanes run the chains, every
+                    // lane evaluates the goals on its frames -- written as one loop so that each piece of code exists once:
+                    //   round 0  gradient (:450-475): D + 1 evaluations, one per lane
+                    //   round 1  L1 normalisation (:477-482) and the two support points x - g (even lanes), x + g (odd lanes) (:485-495)
+                    //   round 2  step along the gradient (:498-568), clipped candidate, acceptance on primary fitness
+                    // Round 6: round 2 IS the next iteration's round 0.  An accepted candidate becomes the elite, and the gradient round that follows evaluates
+                    // that very vector (lane D) and the D vectors with one gene advanced by dp (lanes i < D) -- on the candidate's frames, which round 2 has
+                    // just built: the same displacements x4 - base, the same chains, the same goals.  So round 2 evaluates all D + 1 of them (a wavefront
+                    // instruction costs the same for one lane as for eight), lane D's primary fitness decides, and on acceptance the gradient of the next
+                    // iteration is already there: every iteration but the first is two rounds instead of three.  A rejected candidate's gradient is dropped
+                    // (the species stops).  Same operations on the same operands: the same bits.
+                    double fnorm = 0.0;
+                    bool nan_gene = false;  // (round 2: a gene of the candidate is not a number)
+                    for (int round = it == 0 ? 0 : 1; round < 3; round++) {
+                        double* dv0 = s_dv + (round == 0 ? 0 : round == 1 ? 1 : 3) * M;
+                        double* fc0 = (L.fc >= 0 ? s_fc : popS + (S.cur ^ 1) * BF) + (round == 0 ? 0 : round == 1 ? 1 : 3) * FB;  // (make_layout: fc_in_pop)
+                        if (round == 0) {
+                            for (int k = gtid; k < n_ops; k += Gw) dv0[k] = ((active_mask >> k) & 1ull) ? el[k] - s_base[k] : 0.0;
+                        } else if (round == 1) {
+                            double sum = dp * dp;
+                            for (int i = 0; i < D; i++) sum += fabs(s_grad[i]);
+                            fnorm = 1.0 / sum * dp;
+                            PHASE_MARK(PH_MEM_NORM);
+                            for (int k = gtid; k < n_ops; k += Gw) {
+                                const double e = el[k], g = s_gop[k] * fnorm, b = s_base[k];
+                                const bool on = (active_mask >> k) & 1ull;
+                                const double xm = e - g, xp = e + g;
+                                s_xm[k] = xm, s_xp[k] = xp;
+                                dv0[k] = on ? xm - b : 0.0;
+                                dv0[M + k] = on ? xp - b : 0.0;
+                            }
+                        } else {
+                            const double f1 = s_ex[2], f3 = s_ex[3], f2 = fa;
+                            double step_size;
+                            if (sp.memetic == 'q') {  // :498-539
+                                double v1 = f2 - f1, v2 = f3 - f2;
+                                double v = (v1 + v2) * 0.5, aa = v1 - v2;
+                                step_size = v / aa;
+                            } else {  // 'l' :545-568
+                                double cost_diff = (f3 - f1) * 0.5;
+                                step_size = -(f2 / cost_diff);
+                            }
+                            // A step that is not a number: three equal support values make the quadratic step 0 / 0, the linear one f2 / 0 -- and 0 * inf for
+                            // a gene the gradient does not move.  The reference's clip lets a NaN through (utils.h:328-333), its candidate's fitness is NaN and
+                            // fails the comparison below: the search stops.  fmin / fmax would make the lower limit of a NaN (-DBL_MAX for a joint without
+                            // limits) and the candidate a jump there; so a candidate with a NaN gene is no candidate.  (Where a goal hides the NaN -- max(0, .)
+                            // of its error -- the literal reference ACCEPTS the NaN genes and can return them: quirk Q5)
+                            // A step without bound -- v / 0 of a model without curvature -- puts a joint WITHOUT limits at its clip range's end, +-DBL_MAX
+                            // (robot_info.h:109-113), where the linear model overflows; the literal reference may accept that vector and return it (quirk Q7,
+                            // DESIGN.md section 3).  A candidate with a gene of magnitude BIOIK_CANDIDATE_BOUND or more is no candidate either: the search stops.  (The bound is
+                            // the end of the shared sincos's domain, 2^47: a rotation is periodic, so a candidate at 1e10 rad is an ordinary pose -- and must be the pose
+                            // the caller's own trigonometry makes of that value; half angle = factor x gene / 2, inside the domain for mimic factors up to 2.)
+                            bool nan_here = false;
+                            for (int k = gtid; k < n_ops; k += Gw) {
+                                const double e = el[k], gv = s_gop[k] * fnorm;
+                                const bool on = (active_mask >> k) & 1ull;
+                                const double raw = e + gv * step_size;
+                                const bool is_nan = on && !(raw == raw);
+                                const double x4 = (on && !is_nan) ? fmin(fmax(raw, s_clip[k]), s_clip[M + k]) : e;
+                                nan_here = nan_here || is_nan || (on && fabs(x4) >= BIOIK_CANDIDATE_BOUND);
+                                s_x4[k] = x4;
+                                dv0[k] = on ? x4 - s_base[k] : 0.0;
+                            }
+                            nan_gene = (p_ballot(nan_here) & (G >= 64 ? ~0ull : 0xffffffffull << (tid & 32))) != 0ull;
+                        }
+                        p_wave_sync();
+                        PHASE_MARK(PH_MEM_SUPPORT_COLS);
+                        chains(dv0, fc0, round == 1 ? dv0 + M : nullptr, fc0 + FB);
+                        p_wave_sync();
+                        double vprim, vall;
+                        // what joint-value goals read: the lane's own vector -- in the gradient round the elite with its gene advanced by dp
+                        // (computed where it is read, no column), else the shared support point / candidate
+                        const bool grad_round = round != 1;  // (the candidate's round too: lanes i < D advance gene i on the candidate's frames)
+                        const PerturbX xq{round == 0 ? el : (round == 2 ? s_x4 : (odd ? s_xp : s_xm)), grad_round ? my_op : -1, grad_round ? dp : 0.0};
+                        // (the vectors whose terms the lanes share: the elite / the candidate, or the two support points -- even lanes read the first's sums, odd lanes the second's)
+                        const PerturbX xs{round == 0 ? el : (round == 2 ? s_x4 : s_xm), grad_round ? my_op : -1, grad_round ? dp : 0.0, round == 1 ? s_xp : nullptr};
+                        goals_on(fc0 + ((round == 1 && odd) ? FB : 0), grad_round ? my_op : -1, grad_round ? dp : 0.0, xq, vprim, vall, true, xs,
+                                 s_tm + ((round == 1 && odd) ? 3 * M : 0));
+                        PHASE_MARK(PH_MEM_SUPPORT_EVAL);
+                        if (round == 0) {
+                            if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;
+                            p_wave_sync();
+                            f2p = s_ex[0], fa = s_ex[1];
+                            if (my_op >= 0) {
+                                s_grad[gtid] = vall - fa;
+                                s_gop[my_op] = vall - fa;
+                            }
+                            p_wave_sync();
+                            PHASE_MARK(PH_MEM_GRAD);
+                        } else if (round == 1) {
+                            if (gtid < 2) s_ex[2 + gtid] = vall;
+                            p_wave_sync();
+                        } else {
+                            if (gtid == D) s_ex[0] = vprim, s_ex[1] = vall;  // the candidate itself (the other lanes: the candidate with a gene advanced)
+                            p_wave_sync();
+                            const double cprim = s_ex[0], call = s_ex[1];
+                            const bool accept = !nan_gene && cprim < f2p;  // accept iff the primary fitness improves, else stop (:527-538)
+                            // (a half-wave group shares its wavefront with the other species: it stays in step with it and merely
+                            // repeats the rejected iteration from its support points on, which changes nothing -- its elite, its gradient and the
+                            // fitness values that belong to them stay as they are -- until the other species has stopped as well)
+                            if (G >= 64 ? !accept : p_ballot(accept) == 0ull) descending = false;
+                            if (accept) {
+                                for (int k = gtid; k < n_ops; k += Gw) el[k] = s_x4[k];
+                                f2p = cprim, fa = call;  // the candidate is the elite: what the gradient round of the next iteration would compute
+                                if (my_op >= 0) {
+                                    s_grad[gtid] = vall - call;
+                                    s_gop[my_op] = vall - call;
+                                }
+                            }
+                            p_wave_sync();
+                            PHASE_MARK(PH_MEM_ACCEPT);
+                        }
                     }
                 }
             }

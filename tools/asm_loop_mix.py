@@ -15,6 +15,11 @@ v_readlane / v_writelane, vint = every other VALU instruction; salu, smem, lds, 
 lists instead every loop of the kernel that holds a run of N (default 4) or more consecutive v_mov_b32 / v_mov_b64 from a VGPR to a VGPR -- values carried
 from one set of registers to another, which the `mov` class above does not tell from constants being materialised: the loop's header and depth, the block
 of the run, whether that block is the loop's latch (it branches back to the header), the run's length in instructions and in dwords, and its source line.
+
+    python tools/asm_loop_mix.py /tmp/k.s _Z19k_solve_lean_cl64w49SolveArgs --lines LO HI
+
+lists the VALU instructions per loop and per line LO ... HI of bioik_kernels.h -- the lines of ONE phase's function, each instruction charged to the line of that
+function its inlined-at chain names -- so that the instructions along the path one trip takes can be added up by hand (profiles/dense_line_search.log).
 """
 import collections
 import re
@@ -110,7 +115,50 @@ def copy_runs(lines, start, end, files, least):
     return [(h, d, b, bool(latch.get(b)), n, w, src) for h, d, b, n, w, src in runs]
 
 
+def line_counts(lines, start, end, lo, hi):
+    """VALU instructions per (loop header, depth, line): every instruction is charged to the first bioik_kernels.h line in [lo, hi] that the inlined-at chain of its
+    .loc names -- the line of the phase's own function, whatever was inlined into it (a .loc of line 0 keeps the line in front of it; code of other phases is left out)"""
+    header, cur = ("top", 0), None
+    count = collections.Counter()
+    for i in range(start, end):
+        t = lines[i]
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", t)
+        if m:
+            comment = m.group(2) or ""
+            j = i + 1
+            while j < end and lines[j].lstrip().startswith(";"):
+                comment += lines[j]
+                j += 1
+            own = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", comment)
+            inside = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", comment)
+            header = (m.group(1)[2:], int(own.group(1))) if own else ((inside.group(1), int(inside.group(2))) if inside else ("top", 0))
+            continue
+        t = t.strip()
+        if t.startswith(".loc"):
+            named = [int(x) for x in re.findall(r"bioik_kernels\.h:(\d+)", t)]
+            inside_range = [x for x in named if lo <= x <= hi]
+            if inside_range:
+                cur = inside_range[0]
+            elif named and 0 not in named:
+                cur = None
+            continue
+        if not t or t[0] in ";." or t.split()[0].endswith(":"):
+            continue
+        if cur is not None and classify(t.split()[0]) in VALU:
+            count[(header[0], header[1], cur)] += 1
+    return count
+
+
 def main():
+    if "--lines" in sys.argv:  # asm_loop_mix.py listing.s kernel --lines LO HI
+        k = sys.argv.index("--lines")
+        lo, hi = int(sys.argv[k + 1]), int(sys.argv[k + 2])
+        lines = open(sys.argv[1]).read().split("\n")
+        start = next(i for i, l in enumerate(lines) if l.startswith(sys.argv[2] + ":"))
+        end = next(i for i, l in enumerate(lines) if i > start and l.startswith(".Lfunc_end"))
+        for (h, d, line), n in sorted(line_counts(lines, start, end, lo, hi).items()):
+            print("loop %-10s depth %d  bioik_kernels.h:%d  VALU %d" % (h, d, line, n))
+        return
     if "--copies" in sys.argv:
         k = sys.argv.index("--copies")
         least = int(sys.argv[k + 1]) if len(sys.argv) > k + 1 else 4
