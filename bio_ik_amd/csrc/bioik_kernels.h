@@ -298,6 +298,59 @@ BIOIK_DEV unsigned long long half_min_u64(unsigned long long k) {
     o = p_quad_xor<1>(k), k = o < k ? o : k;
     return k;
 }
+// The two least of N keys a lane holds in registers (N a power of two; keys are unique apart from padding, ~0, which loses every comparison or ties with
+// itself): a fixed tournament -- neighbours are put in order, then (least, second) pairs are merged two by two: the least of a merged pair is the lesser
+// of the two leaders, its second the lesser of the other leader and the winner's own second.  One compare per decision, no loop-carried insert.
+template <int N>
+BIOIK_DEV void top2_of_keys(const unsigned long long (&k)[N], unsigned long long& k1, unsigned long long& k2) {
+    static_assert(N >= 2 && (N & (N - 1)) == 0, "a tournament over a power of two of keys");
+    unsigned long long a[N / 2], b[N / 2];  // (least, second) of each pair
+#pragma unroll
+    for (int i = 0; i < N / 2; i++) {
+        const bool w = k[2 * i + 1] < k[2 * i];
+        a[i] = w ? k[2 * i + 1] : k[2 * i], b[i] = w ? k[2 * i] : k[2 * i + 1];
+    }
+#pragma unroll
+    for (int n = N / 2; n > 1; n >>= 1) {
+#pragma unroll
+        for (int i = 0; i < n / 2; i++) {
+            const bool w = a[2 * i + 1] < a[2 * i];
+            const unsigned long long lead = w ? a[2 * i + 1] : a[2 * i], other = w ? a[2 * i] : a[2 * i + 1], second = w ? b[2 * i + 1] : b[2 * i];
+            a[i] = lead, b[i] = second < other ? second : other;
+        }
+    }
+    k1 = a[0], k2 = b[0];
+}
+// (dense kernel) the word of a species' and generation's random stream where solve_generation parked it -- the first word of the group's reduction scratch --
+// and a child of that stream (make_child_t behind its hash)
+BIOIK_DEV uint32_t dense_stream_word(const double* s_red) { return *(const uint32_t*)s_red; }
+template <class PB>
+BIOIK_DEV ChildT<PB> child_t_of_stream(PB pb, uint32_t stream, uint32_t child_index, const double* p0g, const double* pgtable, int M) {
+    ChildT<PB> c;
+    c.pb = pb, c.p0g = p0g;
+    c.pgrow = pgtable + (int)(child_index % 2u) * M;
+    c.base = rng_child_base(stream, child_index);
+    c.mutation_rate = rng_child_rate(c.base);
+    c.gradient_factor = (double)(child_index % 3u);
+    return c;
+}
+// (dense kernel) half_min_u64 as two minimum reductions of 32-BIT WORDS: the high words first, then the low words of the lanes that hold the least high word
+// (the others offer ~0).  Still integer minima of the key's own bits -- a key built from +inf is a NaN pattern and no operand for a floating-point minimum --
+// but an unsigned 32-bit minimum takes the DPP operand itself, where the 64-bit compare needs both halves moved into registers first (five instructions a stage).
+BIOIK_DEV uint32_t half_min_u32(uint32_t v) {
+    uint32_t o = (uint32_t)p_shfl_xor((int)v, 16);
+    v = o < v ? o : v;
+    o = (uint32_t)p_row_mirror<0>((int)v), v = o < v ? o : v;
+    o = (uint32_t)p_row_mirror<1>((int)v), v = o < v ? o : v;
+    o = (uint32_t)p_quad_xor<2>((int)v), v = o < v ? o : v;
+    o = (uint32_t)p_quad_xor<1>((int)v), v = o < v ? o : v;
+    return v;
+}
+BIOIK_DEV unsigned long long half_min_u64_by_words(unsigned long long k) {
+    const uint32_t hi = (uint32_t)(k >> 32), least_hi = half_min_u32(hi);
+    const uint32_t least_lo = half_min_u32(hi == least_hi ? (uint32_t)k : 0xffffffffu);
+    return ((unsigned long long)least_hi << 32) | least_lo;
+}
 // the least key of a lane group of 32 or 64 lanes (half a wavefront or a whole one), known to all of its lanes
 BIOIK_DEV unsigned long long group_min_u64(unsigned long long k, int G) {
     if (G >= 64) {
@@ -1505,7 +1558,13 @@ BIOIK_DEV void solve_walks(Frame& F, SpeciesState& S, double*& popS, int rank_it
                     const int c0 = has_sec ? s_order[ra] : ra, c1 = has_sec ? s_order[rb] : rb;
                     const uint32_t ctr1t = rng_ctr1(gctr, (uint32_t)species_load(rank_now()).id, RNG_REPRODUCE);  // (= ctr1, from the record: the stream's hash is not carried over the walks)
                     // (FIXED: the launcher hands these kernels serial chains only, DevProblem::serial_chain -- the usual robot arm: one chain, nothing parked)
-                    if constexpr (DENSE || WAVE2) {
+                    if constexpr (DENSE) {
+                        const double* const pgt = popS + (S.cur ^ 1) * BF;  // (the table of the parents' mixed momentum, built where the generation begins)
+                        const uint32_t stream = dense_stream_word(s_red);   // (... and the stream's word, hashed there once for the trips and the winners' copy)
+                        const ChildT<PB> cx[2] = {child_t_of_stream(pb, stream, (uint32_t)c0 + 2u, p0g, pgt, M), child_t_of_stream(pb, stream, (uint32_t)c1 + 2u, p0g, pgt, M)};
+                        PHASE_MARK(PH_REPRODUCE);
+                        eval_exact_primary_n<2, true, true>(pb, cx, qc, s_slots, 0, f, s_prefix);
+                    } else if constexpr (WAVE2) {
                         const double* const pgt = popS + (S.cur ^ 1) * BF;  // (the table of the parents' mixed momentum, built where the generation begins)
                         const ChildT<PB> cx[2] = {make_child_t(pb, key, ctr1t, (uint32_t)c0 + 2u, p0g, pgt, M), make_child_t(pb, key, ctr1t, (uint32_t)c1 + 2u, p0g, pgt, M)};
                         PHASE_MARK(PH_REPRODUCE);
@@ -1613,7 +1672,57 @@ BIOIK_DEV void solve_select_and_copy(Frame& F, SpeciesState& S, double*& popS, i
     if constexpr (DENSE || JH) coarse_parked(gtid);  // (the other kernels: in front of their lanes' offers)
     // (the joint walk has reduced over the whole wavefront already; under SLIM it parks its values like the other walks, and the reduction
     // inside the half stands here, between the lanes' reads of the species record above and its update below)
-    if constexpr (DENSE || JH) {
+    if constexpr (DENSE) {
+        // The dense build's own form of the selection by keys below: the same keys, the same two minimum reductions, the same decision and the same exact
+        // path behind it, written for what its launcher guarantees (dense_shape, bioik_hip.hip): a group is HALF a wavefront, 128 <= lambda <= 256 children
+        // and no pre-selection, so a lane holds four to eight keys -- in REGISTERS (nothing of the walks is live here), built once:
+        //   keys         a parked value is read once; the mask of the dropped bits is two wavefront-uniform words (an AND and an AND-OR per key, no 64-bit
+        //                vector shift); a uniform branch picks the form of four keys (lambda = 128: the product) or of eight (padding: ~0, as in the loop)
+        //   two least    a fixed tournament of compare-exchanges over the registers (top2_of_keys), no running insert inside a runtime loop
+        //   half minima  each 64-bit minimum as two minima of 32-bit words (half_min_u64_by_words): the same least key, v_min_u32 with its DPP operand
+        //   doubt test   "how many candidates share the runner-up's upper bits" asks (key ^ B2) < 2^drop of every held key -- a compare against a uniform
+        //                bound whose result IS the ballot; `one` (the lanes with such a candidate) and `more` (with two or more) are sums over those lane
+        //                masks in scalar registers: no second pass over LDS, no second key
+        const double* const s_fit2 = gbase + L.fitp;
+        const int drop = a.sort_key_drop;
+        const unsigned long long low = (1ull << drop) - 1ull;  // (uniform: the bits a key gives up; the bound of the doubt test is low + 1)
+        const uint32_t keep_lo = (uint32_t)~low, keep_hi = (uint32_t)(~low >> 32);
+        unsigned long long B1, B2, one = 0ull, more = 0ull;
+        auto by_keys = [&](auto n_keys) {
+            constexpr int NK = decltype(n_keys)::value;
+            unsigned long long k[NK];
+            bool held[NK];
+#pragma unroll
+            for (int i = 0; i < NK; i++) {
+                const int r = gtid + 32 * i;
+                held[i] = i < 4 || r < n_eval;  // (at least 128 children: a lane's first four entries are always there)
+                unsigned long long b;
+                __builtin_memcpy(&b, &s_fit2[held[i] ? r : gtid], 8);
+                const uint32_t lo = ((uint32_t)b & keep_lo) | (uint32_t)(r + 2), hi = (uint32_t)(b >> 32) & keep_hi;  // (sort_key: r + 2 < 1024 <= 2^drop)
+                k[i] = held[i] ? ((unsigned long long)hi << 32) | lo : ~0ull;
+            }
+            unsigned long long k1, k2;
+            top2_of_keys<NK>(k, k1, k2);
+            B1 = half_min_u64_by_words(k1);
+            B2 = half_min_u64_by_words(k1 == B1 ? k2 : k1);
+#pragma unroll
+            for (int i = 0; i < NK; i++) {
+                const unsigned long long m = p_ballot(held[i] && (k[i] ^ B2) <= low);  // (this candidate shares the runner-up's upper bits)
+                more |= one & m, one |= m;
+            }
+        };
+        if (n_eval <= 128) by_keys(std::integral_constant<int, 4>{});
+        else by_keys(std::integral_constant<int, 8>{});
+        const uint32_t mine = grp ? (uint32_t)(one >> 32) : (uint32_t)one;
+        const bool in_doubt = B2 != ~0ull && ((mine & (mine - 1u)) != 0u);
+        if (p_ballot(in_doubt) == 0ull && more == 0ull) {  // (the halves of the wavefront decide together: one path through the code)
+            b1p = (int)(B1 & 1023ull), b1f = s_fit2[b1p - 2];
+            if (B2 != ~0ull) b2p = (int)(B2 & 1023ull), b2f = s_fit2[b2p - 2];
+        } else {
+            for (int r = gtid; r < n_eval; r += G) offer(s_fit2[r], r + 2);
+            top2_wave(b1f, b1p, b2f, b2p, G);
+        }
+    } else if constexpr (JH) {
         // The two best children of a half-wavefront's species from KEYS (sort_key: the fitness's upper bits and the position): a lane's candidates
         // are its entries of the parked values, the group's least key and the least of the rest are two minimum reductions of one 64-bit number
         // each (against a butterfly that merges sorted (fitness, position) pairs: half the instructions).  Exact unless a second candidate
@@ -1723,6 +1832,60 @@ BIOIK_DEV void solve_select_and_copy(Frame& F, SpeciesState& S, double*& popS, i
     double* nb = popS + (S.cur ^ 1) * BF;
     // (a half-wave group has 32 lanes: sixteen per winner where the ops are no more than that, else one winner per pass)
     const bool both_at_once = G >= 64 || M <= 16;
+    if constexpr (DENSE) {
+        // The dense build's own form of the copy below (a group is half a wavefront; children are never stored, always re-derived).  A winning child is
+        // re-derived from what the trips built: the mix of the parents' momentum comes from the table of the generation's set-up (solve_generation: the
+        // very operations of ChildX, once per op and parity) -- one LDS read instead of two and four FP64 instructions --, the clip range from the table
+        // the line search keeps in LDS (s_clip: the numbers of pb->ops[k], staged once per query) instead of two per-lane loads from the problem block.
+        // The table lies in the buffer the winners go to (rows 0 and 1 of it: the first winner's place), so every lane reads before any lane writes
+        // (p_wave_sync), and where a pass takes one winner (more than 16 ops) the second winner goes first: lane k then overwrites only what lane k read.
+        const double* const pgt = nb;
+        for (int pass = 0; pass < (both_at_once ? 1 : 2); pass++) {
+            BIOIK_LANE_SCOPE;
+            const int i = both_at_once ? gtid >> 4 : 1 - pass, k0 = both_at_once ? gtid & 15 : gtid;
+            const int id = i == 0 ? first.id : second.id;
+            double* dst = nb + i * 2 * M;
+            double v[2][2] = {{0.0, 0.0}, {0.0, 0.0}};  // (gene, momentum) of ops k0 and k0 + 32
+            const bool wide = n_ops > 32;
+            if (id < 2) {
+                const double* src = cb + id * 2 * M;
+                if (k0 < M) v[0][0] = src[k0], v[0][1] = src[M + k0];
+                if (wide && k0 + 32 < M) v[1][0] = src[k0 + 32], v[1][1] = src[M + k0 + 32];
+            } else {
+                BIOIK_FP_STRICT
+                const uint32_t child = (uint32_t)(id - 2) + 2u;
+                const ChildT<PB> cx = child_t_of_stream(pb, dense_stream_word(s_red), child, p0g, pgt, M);
+                auto derive = [&](int k, double (&o)[2]) {
+                    // (ChildT::at with the clip range as vector operands: lane k its op k)
+                    const double parent_gene = p0g[k], parent_gradient = cx.pgrow[k];
+                    const int g = pb->ops[k].gene;
+                    double gene = parent_gene, mom = 0.0;
+                    if (g >= 0) {
+                        const uint32_t word = rng_child_word(cx.base, (uint32_t)(g + 1));
+                        const double r = rng_gauss32(word);
+                        const double f = cx.mutation_rate * op_limit<LIM_SPAN>(pb, k);
+                        double gn = parent_gene;
+                        gn += r * f;
+                        const double g2 = parent_gradient * cx.gradient_factor;
+                        gn += g2;
+                        gene = p_clamp(gn, s_clip[k], s_clip[M + k]);
+                        mom = parent_gradient * (1.0 - 0.3) + (gene - parent_gene) * 0.3;  // (bit k of active_mask IS ops[k].gene >= 0: DevProblem::active_mask)
+                    }
+                    o[0] = gene, o[1] = mom;
+                };
+                if (k0 < n_ops) derive(k0, v[0]);
+                if (wide && k0 + 32 < n_ops) derive(k0 + 32, v[1]);
+            }
+            p_wave_sync();  // (the table has been read by every lane that needs it)
+            if (id < 2) {
+                if (k0 < M) dst[k0] = v[0][0], dst[M + k0] = v[0][1];
+                if (wide && k0 + 32 < M) dst[k0 + 32] = v[1][0], dst[M + k0 + 32] = v[1][1];
+            } else {
+                if (k0 < n_ops) dst[k0] = v[0][0], dst[M + k0] = v[0][1];
+                if (wide && k0 + 32 < n_ops) dst[k0 + 32] = v[1][0], dst[M + k0 + 32] = v[1][1];
+            }
+        }
+    } else
     for (int pass = 0; pass < (both_at_once ? 1 : 2); pass++) {
         BIOIK_LANE_SCOPE;
         if (gtid >= 64) break;
@@ -1812,6 +1975,10 @@ BIOIK_DEV void solve_generation(Frame& F, SpeciesState& S, double*& popS, int ra
                 inside = pb->ops[k].gene >= 0 && !op_unbounded(pb, k) && avoid_limits_surely_free(p0g[k], pg0, pg1, op_limit<LIM_VMIN>(pb, k), op_limit<LIM_VMAX>(pb, k), op_limit<LIM_SPAN>(pb, k));
         }
         if constexpr (WAVE2) inside_mask = has_sec ? p_ballot(inside) : 0ull;  // (a group is one wavefront and an op a lane: at most 64 ops)
+        // (DENSE: the word of this species' and generation's random stream, hashed ONCE -- the two trips of the walks and the winners' copy read it back instead
+        // of hashing the record's species number again each.  Its place is the group's reduction scratch, which a group of one half-wavefront has no use for.)
+        if constexpr (DENSE)
+            if (gtid == 0) *(uint32_t*)s_red = rng_child_stream(key, ctr1);
         group_sync(G);
     }
     if (has_sec) solve_preselect(F, S, popS, step, gen, ctr1, inside_mask, n_eval);
