@@ -21,6 +21,7 @@
 #include "bioik_compile.h"
 #include "bioik_gradient.h"
 #include "bioik_kernels.h"
+#include "bioik_layouts.h"
 
 static_assert((int)G_POSITION == (int)BIOIK_GOAL_POSITION && (int)G_POSE == (int)BIOIK_GOAL_POSE && (int)G_CONE == (int)BIOIK_GOAL_CONE &&
                   (int)G_JOINT_VARIABLE == (int)BIOIK_GOAL_JOINT_VARIABLE && (int)G_MINIMAL_DISPLACEMENT == (int)BIOIK_GOAL_MINIMAL_DISPLACEMENT &&
@@ -368,8 +369,7 @@ struct bioik_problem {
         // the solve in flight on this slot, if any: where its results go when it completes
         bool pending = false;
         uint64_t ticket = 0;
-        size_t o_sol = 0, o_fit = 0, o_suc = 0, o_steps = 0, o_cnt = 0;
-        size_t rows = 1;  // result rows per query (a ranked solve: k)
+        bioik::IoArenaLayout arena;  // of `host`: its result blocks
         SolveArrays caller{};  // (its inputs were copied at the submission: only n and the result arrays are used)
         // a solve of this slot that ended in a device error: remembered for ITS ticket's wait (the slot itself is free again)
         uint64_t failed_ticket = 0;
@@ -407,6 +407,10 @@ struct bioik_problem {
         // Eager calls only: a captured call sets its words up inside its graph, on every replay (graphs on one pinned buffer lay it out each their own way)
         void* ctl_base = nullptr;
         size_t ctl_n = 0;
+        // how many words of each kind rest at this buffer's start for an EAGER call on it (a pinned buffer is never an eager call's)
+        size_t words_at_rest() const { return !pinned && ctl_base == base ? ctl_n : 0; }
+        void words_set_up(void* at, size_t n) { ctl_base = at, ctl_n = n; }
+        void forget_words() { ctl_base = nullptr, ctl_n = 0; }  // (a call that lays the buffer out its own way, a solve that broke off)
     };
     std::map<std::pair<stream_t, int>, Scratch> scratch;
     // The launcher's MEASURED mapping choice (solve_dispatch): per kind of call -- (children per species, FK mode, islands or not) under the latency schedule --
@@ -596,7 +600,13 @@ struct DeviceGuard {
 
 struct DevBuf {
     void* p = nullptr;
-    explicit DevBuf(size_t bytes) : p(be_alloc(bytes)) {}
+    const size_t bytes;
+    explicit DevBuf(size_t bytes_) : p(be_alloc(bytes_)), bytes(bytes_) {}
+    // ... filled from `src` on the default stream (null: left as allocated)
+    DevBuf(const void* src, size_t bytes_) : DevBuf(bytes_) {
+        if (src) be_h2d(p, src, bytes, 0);
+    }
+    void download(void* dst) const { be_d2h(dst, p, bytes, 0); }  // (enqueued: the caller waits for the default stream)
     ~DevBuf() { be_free(p); }
     DevBuf(const DevBuf&) = delete;
     template <class T>
@@ -642,10 +652,10 @@ static bool lean_capable(const DevProblem& d) {
 }
 
 // the timeout of a solve on the device clock (bioik_problem: clock_*)
-static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t stream, SolveArgs& a) {
+static void set_deadline(bioik_problem* p, const DevSolveParams& sp, stream_t stream, bool captured, SolveArgs& a) {
     a.launch_clock = nullptr, a.deadline = 0ull;
     if (sp.timeout_ticks == 0) return;
-    if (be_stream_capturing(stream)) {
+    if (captured) {
         if (p->clock_next >= bioik_problem::kCaptureClocks) throw Error(BIOIK_ERR_UNSUPPORTED, "more than 64 solves with a timeout captured into hipGraphs on one problem handle");
         a.launch_clock = p->d_clocks + p->clock_next++;
         be_zero_async(a.launch_clock, sizeof(unsigned long long), stream);
@@ -685,6 +695,7 @@ struct SolveLauncher {
     const SolveArrays call;  // (device pointers, or the page-locked arena of a host-pointer call)
     const size_t n;
     stream_t stream;
+    const bool captured;  // the stream is being captured into a hipGraph (asked once per solve, by launch_solve's caller)
     const SolveSwitches& sw;
     unsigned int* error_word;
     const DevProblem& dp;
@@ -699,14 +710,14 @@ struct SolveLauncher {
     int nth = 0, groups = 1;
     size_t lds = 0;
     bool exact = false, quat = false, manual = false, can_columnless = false, prefer_cl4 = false, small_sec_cl4 = false, small_linear = false, throughput = false, dense_ok = false,
-         capturing = false, latency_drain = false, dense = false, lean = false, halves_ok = false, halves_shape = false, dense_shape = false;
+         one_launch_capture = false, latency_drain = false, dense = false, lean = false, halves_ok = false, halves_shape = false, dense_shape = false;
     // the launches (plan_handovers)
     std::vector<int> handovers;  // the steps after which the unsolved units pass to the next launch (ascending)
     bool when_draining = false;  // ... or: whenever the chip runs empty (SolveArgs::resident), every unit from the step it is at
     bool migrating = false;      // ... or: the boundaries of bioik_solve_params::island_migration, with k_migrate_mark and k_migrate between two launches
 
-    SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t s, const SolveSwitches& w, unsigned int* err)
-        : p(p_), sp(sp_in), call(arrays), n(arrays.n), stream(s), sw(w), error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus), bounded(arrays.bounded()) {
+    SolveLauncher(bioik_problem* p_, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t s, bool captured_, const SolveSwitches& w, unsigned int* err)
+        : p(p_), sp(sp_in), call(arrays), n(arrays.n), stream(s), captured(captured_), sw(w), error_word(err), dp(p_->host.dev), kLds(p_->model->dev.lds_cu), kCus((uint64_t)p_->model->dev.cus), bounded(arrays.bounded()) {
         if (dp.n_secondary > 0 && sp.lambda < 2) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "population must be >= 2 when secondary goals are present");
         units = (uint64_t)n * sp.islands;
         if (units > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many (query, island) units for one launch: split the batch");
@@ -729,7 +740,7 @@ struct SolveLauncher {
         if (it != p->scratch.end()) {
             bioik_problem::Scratch& sc = it->second;
             if (entry) *entry = &sc;
-            if (be_stream_capturing(stream)) {
+            if (captured) {
                 for (const auto& r : p->retired_scratch)
                     if (r.stream == stream && r.purpose == purpose && r.capacity >= bytes) return r.base;  // (pinned by an earlier capture on this stream)
                 if (sc.capacity >= bytes) {
@@ -760,45 +771,44 @@ struct SolveLauncher {
             args.solutions = call.solutions, args.fitness = call.fitness, args.success = call.success, args.steps = call.steps;
             return;
         }
-        const size_t per = (size_t)dp.V * 8 + 8 + 4 + 4;
         const size_t ctl_n = fused ? std::max<size_t>(n, 256) : 0;  // (the control words of the fused form: room for calls of up to this many queries)
-        const auto ctl_bytes = [](size_t words) { return (2 * words * 4 + 63) / 64 * 64; };
-        // Eager: control words at rest from an earlier fused call with a larger ctl_n stay where they are, and this call's arrays go behind THEM -- the request
-        // counts that offset.  Captured: the graph sets up its own words on every replay (other graphs on the same pinned buffer lay it out their own way).
-        const bool capturing_now = be_stream_capturing(stream);
+        const auto layout = [&](size_t ctl_words) { return bioik::island_scratch_layout(n, (size_t)sp.islands, (size_t)dp.V, ctl_words, sp.island_sync != 0); };
+        // Eager: control words at rest from an earlier fused call with a larger ctl_n stay where they are, and this call's arrays go behind THEM -- the layout the
+        // buffer is requested with counts them.  Captured: the graph sets up its own words on every replay (other graphs on the same pinned buffer lay it out their own way).
         size_t prior = 0;
-        if (fused && !capturing_now) {
+        if (fused && !captured) {
             auto it = p->scratch.find(std::make_pair(stream, 0));
-            if (it != p->scratch.end() && !it->second.pinned && it->second.ctl_base == it->second.base) prior = it->second.ctl_n;
+            if (it != p->scratch.end()) prior = it->second.words_at_rest();
         }
+        bioik::IslandScratchLayout L = layout(std::max(prior, ctl_n));
         bioik_problem::Scratch* sc = nullptr;
-        char* w = (char*)scratch(0, ctl_bytes(std::max(prior, ctl_n)) + units * per + 64 + n * 4, island_ws, &sc);
-        if (sc && sc->base != (void*)w) sc = nullptr;  // (a retired buffer: pinned, no eager call's)
+        void* const w = scratch(0, L.bytes, island_ws, &sc);
+        if (sc && sc->base != w) sc = nullptr;  // (a retired buffer: pinned, no eager call's)
         if (fused) {
-            size_t have = !capturing_now && sc && sc->ctl_base == (void*)w ? sc->ctl_n : 0;
-            if (have < n) {  // a new buffer, a larger call, a call of the other kind in between, or a capture: set the words up (the kernels keep them from then on)
-                be_fill_ff_async(w, ctl_n * 4, stream);
-                be_zero_async(w + ctl_n * 4, ctl_n * 4, stream);
-                have = ctl_n;
-                if (sc) sc->ctl_base = capturing_now ? nullptr : (void*)w, sc->ctl_n = capturing_now ? 0 : ctl_n;  // (a pinned buffer is never an eager call's again)
+            size_t have = !captured && sc ? sc->words_at_rest() : 0;
+            const bool set_up = have < n;  // a new buffer, a larger call, a call of the other kind in between, or a capture: set the words up (the kernels keep them from then on)
+            if (set_up) have = ctl_n;
+            if (have > L.ctl_words) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "internal: the islands' scratch was requested for fewer control words than it is laid out with");
+            if (have < L.ctl_words) L = layout(have);  // (a buffer that had to grow holds no earlier call's words: this call's own, in fewer bytes than were asked for)
+            if (set_up) {
+                be_fill_ff_async(L.first_success.at(w), L.first_success.bytes(), stream);
+                be_zero_async(L.island_done.at(w), L.island_done.bytes(), stream);
+                if (sc && captured) sc->forget_words();  // (a pinned buffer is never an eager call's again)
+                else if (sc) sc->words_set_up(w, ctl_n);
             }
             if (sw.report) std::fprintf(stderr, "[bioik] islands: reduced by the last island in the launch (control words of %zu queries)\n", have);
-            if (sp.island_sync) args.first_success = (unsigned int*)w;
-            args.island_done = (unsigned int*)(w + have * 4);
+            if (L.sync) args.first_success = L.first_success.at(w);
+            args.island_done = L.island_done.at(w);
             args.final_solutions = call.solutions, args.final_fitness = call.fitness, args.final_success = call.success, args.final_steps = call.steps;
-            w += ctl_bytes(have);
             fused_select = true;
-        } else if (sc) {
-            sc->ctl_base = nullptr, sc->ctl_n = 0;  // (this call lays the buffer out its own way)
+        } else {
+            if (sc) sc->forget_words();  // (this call lays the buffer out its own way)
+            if (L.sync) {  // "any island succeeds => all stop": the least step count of a passing island, per query (0xffffffff: none yet)
+                args.first_success = L.first_success.at(w);
+                be_fill_ff_async(args.first_success, L.first_success.bytes(), stream);
+            }
         }
-        args.solutions = (double*)w, w += units * dp.V * 8;
-        args.fitness = (double*)w, w += units * 8;
-        args.success = (int32_t*)w, w += units * 4;
-        args.steps = (int32_t*)w, w += units * 4;
-        if (!fused && sp.island_sync) {  // "any island succeeds => all stop": the least step count of a passing island, per query (0xffffffff: none yet)
-            args.first_success = (unsigned int*)w;
-            be_fill_ff_async(args.first_success, n * 4, stream);
-        }
+        args.solutions = L.solutions.at(w), args.fitness = L.fitness.at(w), args.success = L.success.at(w), args.steps = L.steps.at(w);
     }
     void select_islands(const SolveArgs& args) {  // ik_parallel.h:220-269: the best island of every query
         if (ranked) {  // ... or its k best distinct ones, in that order (islands = 1: the solve wrote the row itself, the kernel adds the count)
@@ -830,7 +840,7 @@ struct SolveLauncher {
         pa.var_lo = call.var_lo, pa.var_hi = call.var_hi;
         result_arrays(pa, false);
         pa.phase_cycles = nullptr;
-        set_deadline(p, sp, stream, pa);
+        set_deadline(p, sp, stream, captured, pa);
         const SolveKernel kind = bounded ? SolveKernel::k_solve_point_bounded : SolveKernel::k_solve_point;
         if (sw.report) std::fprintf(stderr, "[bioik] launch: %s, 64 lanes, %zu B of LDS\n", kSolveKernelNames[(int)kind], lds_point);
         launch_kernel(kind, pa, units, 64, lds_point, stream);
@@ -942,9 +952,9 @@ struct SolveLauncher {
         // (BIOIK_SOLVE_CAPTURE_ONE_LAUNCH=1: round 4's rule -- a call on a stream that is being captured gets a one-launch mapping.  The replay defect it worked around
         // was the runtime's memset NODE in front of the kernels, not the hand-over; the library fills its words with a kernel of its own now
         // and captured calls take the same mapping as eager ones)
-        capturing = sw.capture_one_launch && be_stream_capturing(stream);
+        one_launch_capture = sw.capture_one_launch && captured;
         latency_drain = sp.schedule != BIOIK_SCHEDULE_THROUGHPUT && prefer_cl4 && dense_ok && units >= (uint64_t)(sp.islands <= 2 ? sw.drain_min_units : 3072) * kCus / 256 && sw.drain_below > 0 && sp.max_steps > sw.drain_min_steps + 1 &&
-                                   !sw.two_phase_set && !capturing;
+                                   !sw.two_phase_set && !one_launch_capture;
         dense = (throughput || latency_drain) && dense_ok;
         if (sw.columnless > 0 && can_columnless) {
             sp.columnless = 1, sp.child_cols = 1;
@@ -1029,7 +1039,7 @@ struct SolveLauncher {
         // island migration: the boundaries E, 2E, ... < max_steps, BIOIK_MAX_MIGRATIONS at most, instead of every other plan (one island, or no boundary below max_steps: the
         // call's plan is the one E = 0 takes)
         if (sp.island_migration > 0 && sp.islands > 1 && sp.solver == 0 && sp.island_migration < sp.max_steps) {
-            if (be_stream_capturing(stream)) throw Error(BIOIK_ERR_UNSUPPORTED, "island_migration > 0 on a stream that is being captured into a hipGraph is not supported");
+            if (captured) throw Error(BIOIK_ERR_UNSUPPORTED, "island_migration > 0 on a stream that is being captured into a hipGraph is not supported");
             migrating = true;
             for (long long k = sp.island_migration; k < (long long)sp.max_steps && handovers.size() < (size_t)BIOIK_MAX_MIGRATIONS; k += sp.island_migration) handovers.push_back((int)k);
             return;
@@ -1044,11 +1054,11 @@ struct SolveLauncher {
         } else if (throughput) {
             // the dense mapping retires most steps per ms but its steps are 2.5 x as long: the stragglers of a batch may pass to the latency mapping
             if (sw.dense_handover > 0 && sw.dense_handover < sp.max_steps) handovers.push_back(sw.dense_handover);
-            else if (dense && prefer_cl4 && units >= 8 * kCus && sw.drain_throughput && sw.drain_below > 0 && sw.drain_below_throughput > 0 && sp.max_steps > sw.drain_min_steps + 1 && !capturing)
+            else if (dense && prefer_cl4 && units >= 8 * kCus && sw.drain_throughput && sw.drain_below > 0 && sw.drain_below_throughput > 0 && sp.max_steps > sw.drain_min_steps + 1 && !one_launch_capture)
                 when_draining = true, handovers.push_back(sp.max_steps);
         } else if (latency_drain) {
             when_draining = true, handovers.push_back(sp.max_steps);
-        } else if (lean && dense_shape && !manual && !prefer_cl4 && units >= 8 * kCus && sp.max_steps >= 24 && !capturing) {
+        } else if (lean && dense_shape && !manual && !prefer_cl4 && units >= 8 * kCus && sp.max_steps >= 24 && !one_launch_capture) {
             // (not under k_solve_lean_cl4's mapping: there one launch is faster -- three in flight 9.9e5 against 9.3e5, an isolated call 8.9 against 9.3 ms,
             // profiles/r04_ab_latency_schedule_kernel.log)
             handovers.push_back(1);
@@ -1073,17 +1083,15 @@ struct SolveLauncher {
             launch(a, nth, lds);
         } else {
             const size_t nh = handovers.size();
-            const size_t carry_n = (size_t)carry_doubles(dp.n_ops);
-            const size_t list_bytes = (units * 4 + 63) / 64 * 64;
-            const size_t list_off = (units * carry_n * 8 + 63) / 64 * 64, count_off = list_off + nh * list_bytes;
-            const size_t mark_off = count_off + nh * 64, mark_bytes = migrating ? list_bytes : 0;  // (migration: one word per unit, the number of the last boundary it was live at)
+            // (migration: one word per unit behind the counters, the number of the last boundary it was live at)
+            const bioik::HandoverLayout H = bioik::handover_layout((size_t)units, (size_t)carry_doubles(dp.n_ops), nh, migrating);
             void* ws_async = nullptr;
             AsyncFree ws_guard{ws_async, stream};
-            void* ws = scratch(1, mark_off + mark_bytes, ws_async);
-            be_zero_async((char*)ws + count_off, nh * 64 + mark_bytes, stream);  // (the counters and, behind them, the marks)
+            void* ws = scratch(1, H.bytes, ws_async);
+            be_zero_async(H.cleared.at(ws), H.cleared.bytes(), stream);
             if (!sw.handover_dump.empty())
                 if (FILE* f = std::fopen(sw.handover_dump.c_str(), "a")) {
-                    std::fprintf(f, "%llu %zu %zu %llu %zu\n", (unsigned long long)(size_t)ws, list_off, count_off, (unsigned long long)units, carry_n);
+                    std::fprintf(f, "%llu %zu %zu %llu %zu\n", (unsigned long long)(size_t)ws, H.lists_off, H.counters_off, (unsigned long long)units, H.carry_doubles);
                     std::fclose(f);
                 }
             for (size_t j = 0; j <= nh; j++) {  // launch j runs the steps [handovers[j-1], handovers[j])
@@ -1091,7 +1099,7 @@ struct SolveLauncher {
                 int lanes = nth;
                 size_t lds_j = lds;
                 if (j == 0 && halves_ok && !manual) halves(aj, lanes, lds_j);
-                aj.carry = (double*)ws;
+                aj.carry = H.rows.at(ws);
                 if (when_draining) {  // (the last launch counts its wavefronts too; it has no list to leave for)
                     aj.resident = p->d_resident;
                     {  // (per XCD -- eight on MI355X --, the threshold itself scaled to the chip's CUs: BIOIK_SOLVE_DRAIN_BELOW names it for 256 of them)
@@ -1103,19 +1111,19 @@ struct SolveLauncher {
                 }
                 if (j > 0) {
                     aj.step_begin = when_draining ? -1 : handovers[j - 1];
-                    aj.unit_list = (const int32_t*)((char*)ws + list_off + (j - 1) * list_bytes);
-                    aj.unit_count = (const unsigned int*)((char*)ws + count_off + (j - 1) * 64);
+                    aj.unit_list = H.list(j - 1).at(ws);
+                    aj.unit_count = H.counter(j - 1).at(ws);
                 }
                 if (j < nh) {
                     aj.step_end = handovers[j];
-                    aj.carry_list = (int32_t*)((char*)ws + list_off + j * list_bytes);
-                    aj.carry_count = (unsigned int*)((char*)ws + count_off + j * 64);
+                    aj.carry_list = H.list(j).at(ws);
+                    aj.carry_count = H.counter(j).at(ws);
                 }
                 launch(aj, lanes, lds_j);  // (always a grid of `units` workgroups: those beyond the list's length leave at once)
                 if (migrating && j < nh) {     // boundary j + 1: mark the units this launch handed over, then a wavefront per query rewrites its recipients' rows
                     MigrateArgs m;
                     m.islands = sp.islands, m.n_ops = dp.n_ops, m.exact = exact ? 1 : 0, m.mark = (int)j + 1, m.n = n;
-                    m.list = aj.carry_list, m.count = aj.carry_count, m.live = (int32_t*)((char*)ws + mark_off), m.rows = (double*)ws;
+                    m.list = aj.carry_list, m.count = aj.carry_count, m.live = H.marks.at(ws), m.rows = H.rows.at(ws);
                     if (sw.report) std::fprintf(stderr, "[bioik] launch: k_migrate_mark + k_migrate, boundary %d after step %d, islands %d\n", (int)j + 1, handovers[j], (int)sp.islands);
                     LAUNCH(k_migrate_mark, migrate_mark(m, b_ * 256 + (uint64_t)p_tid()), (units + 255) / 256, 256, 0, stream, m);
                     LAUNCH(k_migrate, migrate_coop(m, b_, p_tid()), n, 64, 0, stream, m);
@@ -1125,12 +1133,13 @@ struct SolveLauncher {
     }
 };
 
-static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t stream, const SolveSwitches& sw, unsigned int* error_word,
+// (captured: be_stream_capturing(stream), which the caller has asked -- once per solve)
+static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const SolveArrays& arrays, stream_t stream, bool captured, const SolveSwitches& sw, unsigned int* error_word,
                          const RankedArgs* ranked = nullptr) {
     if (sp_in.solver == 2 && has_based_goal(p->host.dev))
         throw Error(BIOIK_ERR_UNSUPPORTED, "BIOIK_MODE_JAC on a problem with a based goal (bioik_problem_desc::goal_base_link): its tip objectives are world poses; gd, gd_r and gd_c work");
     if (arrays.n == 0) return;
-    SolveLauncher s(p, sp_in, arrays, stream, sw, error_word);
+    SolveLauncher s(p, sp_in, arrays, stream, captured, sw, error_word);
     s.ranked = ranked;
     if (s.sp.solver != 0) return s.solve_point();
     s.choose_mapping();
@@ -1147,7 +1156,7 @@ static void launch_solve(bioik_problem* p, const DevSolveParams& sp_in, const So
     a.preselect = sw.preselect | (sw.tie_test_bits << 8);
     a.error = error_word;
     a.debug_flags = sw.debug_flags;
-    set_deadline(p, s.sp, stream, a);
+    set_deadline(p, s.sp, stream, captured, a);
 #if defined(BIOIK_PHASE_TIMING)
     DevBuf phase_buf(s.units * PHASE_SLOTS * sizeof(unsigned long long));
     const char* phase_path = sw.phase_dump.empty() ? nullptr : sw.phase_dump.c_str();
@@ -1198,11 +1207,12 @@ static SolveSwitches preset_switches(const SolveSwitches& base, int i) {
 }
 static void solve_dispatch(bioik_problem* p, const DevSolveParams& sp, const SolveArrays& arrays, stream_t stream, bool may_wait, unsigned int* error_word) {
     const SolveSwitches sw = switches();  // (the diagnostic switches as last parsed: no environment access on the launch path)
-    auto run = [&](const SolveSwitches& w) { launch_solve(p, sp, arrays, stream, w, error_word); };
+    const bool captured = be_stream_capturing(stream);
+    auto run = [&](const SolveSwitches& w) { launch_solve(p, sp, arrays, stream, captured, w, error_word); };
     const uint64_t units = (uint64_t)arrays.n * (uint64_t)sp.islands;
     const bool kind_ok = !arrays.bounded() /* (a bounded call neither takes nor changes the measured choice, as the ranked entries) */ && sw.autotune > 0 && !sw.manual() && !sw.general_set && !sw.two_phase_set && sw.drain_test == 0 && sw.dense_handover == 0 && sp.solver == 0 &&
                          sp.schedule != BIOIK_SCHEDULE_THROUGHPUT && sp.timeout_ticks == 0 && units >= 8 * (uint64_t)p->model->dev.cus && sp.max_steps >= 8;
-    if (!kind_ok || be_stream_capturing(stream)) {
+    if (!kind_ok || captured) {
         run(sw);
         return;
     }
@@ -1259,7 +1269,7 @@ static void report_stale_error(bioik_problem* p) {
 }
 // a solve that broke off may have left the control words of the handle's scratch buffers anywhere: every buffer sets them up again (bioik_problem::Scratch)
 static void reset_control_words(bioik_problem* p) {
-    for (auto& kv : p->scratch) kv.second.ctl_base = nullptr;
+    for (auto& kv : p->scratch) kv.second.forget_words();
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1537,15 +1547,13 @@ static void io_finish(bioik_problem* p, bioik_problem::IoSlot& sl) {
         sl.failed_message = "a rendezvous between the wavefronts of a workgroup timed out (k_solve_lean_cl4h): the results of this solve are not valid";
         return;
     }
-    const size_t V = p->host.dev.V;
-    const char* hd = (const char*)sl.host;
+    const bioik::IoArenaLayout& A = sl.arena;
     const SolveArrays& to = sl.caller;
-    const size_t rows = to.n * sl.rows;
-    std::memcpy(to.solutions, hd + sl.o_sol, rows * V * 8);
-    std::memcpy(to.fitness, hd + sl.o_fit, rows * 8);
-    std::memcpy(to.success, hd + sl.o_suc, rows * 4);
-    std::memcpy(to.steps, hd + sl.o_steps, rows * 4);
-    if (to.count) std::memcpy(to.count, hd + sl.o_cnt, to.n * 4);
+    std::memcpy(to.solutions, A.solutions.at(sl.host), A.solutions.bytes());
+    std::memcpy(to.fitness, A.fitness.at(sl.host), A.fitness.bytes());
+    std::memcpy(to.success, A.success.at(sl.host), A.success.bytes());
+    std::memcpy(to.steps, A.steps.at(sl.host), A.steps.bytes());
+    if (to.count) std::memcpy(to.count, A.count.at(sl.host), A.count.bytes());
 }
 // io_begin: copy in, enqueue the transfer in, the solve and the transfer out on the slot's stream; returns without waiting.
 // A solve still pending on the slot is completed first (its results reach its caller's arrays).  Called with p->mtx held.
@@ -1553,50 +1561,43 @@ static void io_begin(bioik_problem* p, bioik_problem::IoSlot& sl, uint64_t ticke
                      const RankedCall* ranked = nullptr) {
     io_finish(p, sl);
     DeviceGuard on_device(p->model->device);
-    const size_t V = p->host.dev.V, P = p->host.dev.P, n = caller.n;
-    // arena layout: [seeds | goal_params] in, [solutions | fitness | success | steps] out, every block 64-byte aligned
-    auto up = [](size_t b) { return (b + 63) / 64 * 64; };
-    const size_t nb = caller.bounded() ? n * V * 8 : 0;  // (a bounded call: its two arrays of bounds behind the goal parameters; they stay in the arena as long as the call's launches)
-    const size_t o_seeds = 0, o_par = o_seeds + up(n * V * 8), o_lo = o_par + up(n * P * 8), o_hi = o_lo + up(nb), in_bytes = o_hi + up(nb);
-    const size_t K = ranked ? (size_t)ranked->k : 1;  // result rows per query; a ranked solve adds count [n]
-    const size_t o_sol = in_bytes, o_fit = o_sol + up(n * K * V * 8), o_suc = o_fit + up(n * K * 8), o_steps = o_suc + up(n * K * 4), o_cnt = o_steps + up(n * K * 4),
-                 total = o_cnt + (ranked ? up(n * 4) : 0);
-    if (sl.bytes < total) {
+    const size_t n = caller.n;
+    // (a bounded call: its two arrays of bounds behind the goal parameters, where they stay as long as the call's launches; a ranked call: k result rows per query, and count [n])
+    const bioik::IoArenaLayout A = bioik::io_arena_layout(n, (size_t)p->host.dev.V, (size_t)p->host.dev.P, ranked ? (size_t)ranked->k : 1, caller.bounded(), ranked != nullptr);
+    if (sl.bytes < A.bytes) {
         be_free(sl.dev);
         be_free_pinned(sl.host);
         sl.dev = sl.host = nullptr, sl.bytes = 0;
-        const size_t cap = total + total / 4;
+        const size_t cap = A.bytes + A.bytes / 4;
         sl.dev = be_alloc(cap);
         sl.host = be_alloc_pinned(cap);
         sl.bytes = cap;
     }
-    char* hd = (char*)sl.host;
-    char* dd = (char*)sl.dev;
+    void* const hd = sl.host;
     if (!sl.stream_made) sl.stream = be_stream_create(), sl.stream_made = true;
     const stream_t st = sl.stream;
-    std::memcpy(hd + o_seeds, caller.seeds, n * V * 8);
-    if (P) std::memcpy(hd + o_par, caller.goal_params, n * P * 8);
-    if (nb) std::memcpy(hd + o_lo, caller.var_lo, nb), std::memcpy(hd + o_hi, caller.var_hi, nb);
+    std::memcpy(A.seeds.at(hd), caller.seeds, A.seeds.bytes());
+    if (A.goal_params.count) std::memcpy(A.goal_params.at(hd), caller.goal_params, A.goal_params.bytes());
+    if (A.var_lo.count) std::memcpy(A.var_lo.at(hd), caller.var_lo, A.var_lo.bytes()), std::memcpy(A.var_hi.at(hd), caller.var_hi, A.var_hi.bytes());
     // (a call of a few queries -- MoveIt's one pose per call -- reads its inputs where they lie: the page-locked arena is mapped into the device's address space, and a
     // few hundred bytes per workgroup over the bus cost less than a DMA transfer in front of the launch)
     const bool direct_inputs = n <= 16;
-    if (!direct_inputs) be_h2d(dd, hd, in_bytes, st);
-    const char* in_base = direct_inputs ? hd : dd;
+    if (!direct_inputs) be_h2d(sl.dev, hd, A.in_bytes, st);
+    const void* in_base = direct_inputs ? hd : sl.dev;
     DevSolveParams sp = ranked ? ranked->sp : bioik::normalize_params(params, first_query, n, 8 * (size_t)p->model->dev.cus);
     // The results go from the kernels straight into the page-locked arena (it is mapped into the device's address space; 1.5 MB per 4096 queries,
     // written once per query).  A transfer out enqueued behind the solve would sit at the head of a DMA queue until the solve is over -- 12 ms
     // for a one-launch solve -- with the transfers in of the handle's next solves behind it: nothing would overlap
     // (profiles/r03_inflight_and_schedule.log, host pipeline).
-    const SolveArrays arena{n, (const double*)(in_base + o_seeds), (const double*)(in_base + o_par), (double*)(hd + o_sol), (double*)(hd + o_fit), (int32_t*)(hd + o_suc),
-                            (int32_t*)(hd + o_steps), ranked ? (int32_t*)(hd + o_cnt) : nullptr, nb ? (const double*)(in_base + o_lo) : nullptr, nb ? (const double*)(in_base + o_hi) : nullptr};
+    const SolveArrays arena{n, A.seeds.at(in_base), A.goal_params.at(in_base), A.solutions.at(hd), A.fitness.at(hd), A.success.at(hd), A.steps.at(hd),
+                            ranked ? A.count.at(hd) : nullptr, A.var_lo.count ? A.var_lo.at(in_base) : nullptr, A.var_hi.count ? A.var_hi.at(in_base) : nullptr};
     if (ranked) {  // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
         const RankedArgs r = ranked_args(ranked->k, ranked->min_distance, arena);
-        launch_solve(p, sp, arena, st, switches(), p->h_error + (&sl - p->io), &r);
+        launch_solve(p, sp, arena, st, be_stream_capturing(st), switches(), p->h_error + (&sl - p->io), &r);
     } else {
         solve_dispatch(p, sp, arena, st, true, p->h_error + (&sl - p->io));
     }
-    sl.pending = true, sl.ticket = ticket, sl.rows = K, sl.caller = caller;
-    sl.o_sol = o_sol, sl.o_fit = o_fit, sl.o_suc = o_suc, sl.o_steps = o_steps, sl.o_cnt = o_cnt;
+    sl.pending = true, sl.ticket = ticket, sl.arena = A, sl.caller = caller;
 }
 static void solve_host(bioik_problem* p, const bioik_solve_params& params, uint64_t first_query, const SolveArrays& caller, const RankedCall* ranked = nullptr) {
     if (caller.n == 0) return;
@@ -1643,7 +1644,7 @@ int bioik_solve_batch_ranked_device(bioik_problem* p, const bioik_solve_params* 
     report_stale_error(p);
     const RankedArgs r = ranked_args(k, min_distance, arrays);
     // (the rules alone: the measured mapping choice is neither taken nor made by a ranked call)
-    launch_solve(p, sp, arrays, (stream_t)hip_stream, switches(), p->h_error + bioik_problem::kIoSlots, &r);
+    launch_solve(p, sp, arrays, (stream_t)hip_stream, be_stream_capturing((stream_t)hip_stream), switches(), p->h_error + bioik_problem::kIoSlots, &r);
     API_END
 }
 int bioik_solve_batch_ranked(bioik_problem* p, const bioik_solve_params* params, size_t n, int32_t k, double min_distance, const double* seeds,
@@ -1773,13 +1774,11 @@ int bioik_eval_fk(bioik_problem* p, size_t n, const double* seed, const double* 
     const int nth = 64;
     const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
-    DevBuf dseed(V * 8), dgenes(n * D * 8), dout(n * T * 7 * 8);
-    be_h2d(dseed.p, seed, V * 8, 0);
-    be_h2d(dgenes.p, genes, n * D * 8, 0);
+    DevBuf dseed(seed, V * 8), dgenes(genes, n * D * 8), dout(n * T * 7 * 8);
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.genes = dgenes.as<double>(), a.out0 = dout.as<double>();
     LAUNCH(k_eval_fk, eval_fk_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
-    be_d2h(tip_frames, dout.p, n * T * 7 * 8, 0);
+    dout.download(tip_frames);
     be_sync(0);
     API_END
 }
@@ -1797,17 +1796,13 @@ int bioik_eval_fitness(bioik_problem* p, int fk_mode, size_t n, const double* se
     const int nth = 64;
     const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
-    DevBuf dseed(V * 8), dpar(P * 8), dbase(D * 8), dgenes(n * D * 8), d0(n * 8), d1(n * 8);
-    be_h2d(dseed.p, seed, V * 8, 0);
-    be_h2d(dpar.p, goal_params, P * 8, 0);
-    if (base_genes) be_h2d(dbase.p, base_genes, D * 8, 0);
-    be_h2d(dgenes.p, genes, n * D * 8, 0);
+    DevBuf dseed(seed, V * 8), dpar(goal_params, P * 8), dbase(base_genes, D * 8), dgenes(genes, n * D * 8), d0(n * 8), d1(n * 8);
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.params = dpar.as<double>(), a.genes = dgenes.as<double>(), a.base = dbase.as<double>();
     a.out0 = d0.as<double>(), a.out1 = d1.as<double>(), a.fk_mode = fk_mode;
     LAUNCH(k_eval_fitness, eval_fitness_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
-    be_d2h(primary, d0.p, n * 8, 0);
-    be_d2h(secondary, d1.p, n * 8, 0);
+    d0.download(primary);
+    d1.download(secondary);
     be_sync(0);
     API_END
 }
@@ -1820,14 +1815,12 @@ int bioik_eval_approximator(bioik_problem* p, const double* seed, const double* 
     const int nth = 64;
     const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, T = p->host.dev.T;
-    DevBuf dseed(V * 8), dbase(D * 8), d0(T * 7 * 8), d1(T * D * 7 * 8);
-    be_h2d(dseed.p, seed, V * 8, 0);
-    be_h2d(dbase.p, base_genes, D * 8, 0);
+    DevBuf dseed(seed, V * 8), dbase(base_genes, D * 8), d0(T * 7 * 8), d1(T * D * 7 * 8);
     EvalArgs a = eval_args(p);
     a.n = 1, a.seed = dseed.as<double>(), a.base = dbase.as<double>(), a.out0 = d0.as<double>(), a.out1 = d1.as<double>();
     LAUNCH(k_eval_approximator, eval_approximator_body(a, l_), 1, nth, lds, 0, a);
-    be_d2h(tip_frames, d0.p, T * 7 * 8, 0);
-    be_d2h(deltas, d1.p, T * D * 7 * 8, 0);
+    d0.download(tip_frames);
+    d1.download(deltas);
     be_sync(0);
     API_END
 }
@@ -1842,15 +1835,14 @@ int bioik_eval_reproduce(bioik_problem* p, int population, uint32_t rng_key, int
     const size_t M = p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1;
     const size_t lds = eval_lds(p, (4 * M + 2 * M * nth) * 8);  // (eval_reproduce_body: the parents, then a genotype and a gradient column per lane)
     const size_t D = p->host.dev.D, n = (size_t)population;
-    DevBuf dpar(4 * D * 8), d0(n * D * 8), d1(n * D * 8);
-    be_h2d(dpar.p, parents, 4 * D * 8, 0);
+    DevBuf dpar(parents, 4 * D * 8), d0(n * D * 8), d1(n * D * 8);
     EvalArgs a = eval_args(p);
     a.n = n, a.genes = dpar.as<double>(), a.out0 = d0.as<double>(), a.out1 = d1.as<double>();
     a.rng_key = rng_key;
     a.rng_ctr1 = (generation << 4) | ((uint32_t)species << 3) | 0u;
     LAUNCH(k_eval_reproduce, eval_reproduce_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
-    be_d2h(children_genes, d0.p, n * D * 8, 0);
-    be_d2h(children_gradients, d1.p, n * D * 8, 0);
+    d0.download(children_genes);
+    d1.download(children_gradients);
     be_sync(0);
     API_END
 }
@@ -1867,15 +1859,12 @@ int bioik_eval_check(bioik_problem* p, const bioik_solve_params* params, size_t 
     const int nth = 64;
     const size_t lds = eval_lds(p, eval_lds_bytes(p, nth));
     const size_t V = p->host.dev.V, D = p->host.dev.D, P = p->host.dev.P;
-    DevBuf dseed(V * 8), dpar(P * 8), dgenes(n * D * 8), dok(n * 4);
-    be_h2d(dseed.p, seed, V * 8, 0);
-    be_h2d(dpar.p, goal_params, P * 8, 0);
-    be_h2d(dgenes.p, genes, n * D * 8, 0);
+    DevBuf dseed(seed, V * 8), dpar(goal_params, P * 8), dgenes(genes, n * D * 8), dok(n * 4);
     EvalArgs a = eval_args(p);
     a.n = n, a.seed = dseed.as<double>(), a.params = dpar.as<double>(), a.genes = dgenes.as<double>(), a.outi = dok.as<int32_t>();
     a.dpos = sp.dpos, a.drot = sp.drot, a.dtwist = sp.dtwist;
     LAUNCH(k_eval_check, eval_check_body(a, b_, l_), (n + nth - 1) / nth, nth, lds, 0, a);
-    be_d2h(ok, dok.p, n * 4, 0);
+    dok.download(ok);
     be_sync(0);
     API_END
 }
@@ -1888,13 +1877,11 @@ int bioik_eval_bounds(bioik_problem* p, size_t n, const double* var_lo, const do
     std::lock_guard<std::mutex> lock(p->mtx);
     DeviceGuard on_device(p->model->device);
     const size_t V = p->host.dev.V, M = p->host.dev.n_ops > 0 ? p->host.dev.n_ops : 1;
-    DevBuf dlo(n * V * 8), dhi(n * V * 8), dout(n * M * 6 * 8);
-    be_h2d(dlo.p, var_lo, n * V * 8, 0);
-    be_h2d(dhi.p, var_hi, n * V * 8, 0);
+    DevBuf dlo(var_lo, n * V * 8), dhi(var_hi, n * V * 8), dout(n * M * 6 * 8);
     BoundsArgs a;
     a.pb = p->pb(), a.n = n, a.var_lo = dlo.as<double>(), a.var_hi = dhi.as<double>(), a.out = dout.as<double>();
     LAUNCH(k_eval_bounds, eval_bounds_body(a, b_, p_tid()), n, 64, 0, 0, a);
-    be_d2h(out, dout.p, n * M * 6 * 8, 0);
+    dout.download(out);
     be_sync(0);
     API_END
 }
@@ -1909,14 +1896,13 @@ int bioik_eval_arith(int device, int op, size_t n, const double* in, double* out
     if (nd <= 0) throw Error(BIOIK_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
     if (device < 0 || device >= nd) throw Error(BIOIK_ERR_NO_DEVICE, "HIP device index out of range");
     DeviceGuard on_device(device);
-    DevBuf din(n * ni * 8), dout(n * no * 8);
-    be_h2d(din.p, in, n * ni * 8, 0);
+    DevBuf din(in, n * ni * 8), dout(n * no * 8);
     ArithArgs a;
     a.op = op, a.pad = 0, a.n = n, a.in = din.as<double>(), a.out = dout.as<double>();
     const uint64_t grid = (n + 255) / 256;
     if (grid > 0x7fffffffull) throw Error(BIOIK_ERR_INVALID_ARGUMENT, "too many elements for one launch");
     LAUNCH(k_eval_arith, arith_body(a, b_ * 256 + (uint64_t)p_tid()), grid, 256, 0, 0, a);
-    be_d2h(out, dout.p, n * no * 8, 0);
+    dout.download(out);
     be_sync(0);
     API_END
 }
@@ -1939,15 +1925,13 @@ int bioik_eval_migrate(bioik_problem* p, int32_t islands, size_t n_queries, cons
     const size_t R = (size_t)bioik_problem_carry_doubles(p);
     std::vector<int32_t> marks(units);  // (the solve's marks hold the boundary's number: here 1 for a live island)
     for (uint64_t u = 0; u < units; u++) marks[u] = live[u] != 0 ? 1 : 0;
-    DevBuf dlive(units * 4), drows(units * R * 8);
-    be_h2d(dlive.p, marks.data(), units * 4, 0);
-    be_h2d(drows.p, rows, units * R * 8, 0);
+    DevBuf dlive(marks.data(), units * 4), drows(rows, units * R * 8);
     MigrateArgs m;
     std::memset(&m, 0, sizeof(m));
     m.islands = islands, m.n_ops = p->host.dev.n_ops, m.exact = 1, m.mark = 1, m.n = n_queries;
     m.live = dlive.as<int32_t>(), m.rows = drows.as<double>();
     LAUNCH(k_migrate, migrate_coop(m, b_, p_tid()), n_queries, 64, 0, 0, m);
-    be_d2h(rows, drows.p, units * R * 8, 0);
+    drows.download(rows);
     be_sync(0);
     API_END
 }
